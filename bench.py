@@ -11,6 +11,11 @@ region), so every step does identical work — the first LM iteration the refere
 ranks; rank 0 prints ONE JSON line.  Workload = BASELINE.json configs[3] (1 000 cameras / 100 000 points / 1 000 000 projection
 factors, seed 42), which fits one GPU; N > 1 shards the point subtrees over the ranks and sums the camera-separator
 contributions with RCCL, i.e. STRONG scaling of the same graph.  Inputs are resident in HBM before the timed region.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else this
+workload reports: per-kernel times and rooflines (HIP events inside the timed region, one more fully instrumented
+iteration behind it), the device micro-benchmarks, the CPU baseline and, with --gpus > 1 or --window, the scaling model.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see write_outputs).
 """
 from __future__ import annotations
 
@@ -25,6 +30,33 @@ sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X datasheet FP64 matrix peak (not listed in MI355X_MICROARCH.md; measured alongside)
 HBM_PEAK_GBPS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+
+
+def write_outputs(dirname, values, scalars):
+    """--dump-outputs: what a caller of the timed path receives after its last step.  The optimizer's Values become one float64
+    array per variable type, values_<type>.npy, rows in ascending key order, each row a packed value (graph.VAR_STORE); every
+    scalar becomes a one-element float64 array.  Above DUMP_LIMIT_BYTES in all, each values_<type> keeps a fixed seeded sample of
+    its rows, whose indices go to values_<type>_rows.npy."""
+    import numpy as np
+    from gtsam_personal_amd.graph import VAR_STORE
+    type_names = ("pose2", "pose3", "point3", "camera", "point2", "cal3_s2")  # graph.POSE2 ... graph.CAL3_S2
+    rows = {}
+    for k in values.keys():
+        rows.setdefault(values.type(k), []).append(values.at(k))
+    out = {f"values_{type_names[t]}": np.asarray(r, dtype=np.float64).reshape(len(r), VAR_STORE[t]) for t, r in sorted(rows.items())}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(0)
+        frac = DUMP_LIMIT_BYTES / (2.0 * total)  # half the budget for the sampled rows, at most half of that again for their indices
+        for name in list(out):
+            a = out[name]
+            keep = np.sort(rng.choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            out[name], out[name + "_rows"] = a[keep], keep.astype(np.float64)
+    out.update({k: np.array([v], dtype=np.float64) for k, v in scalars.items()})
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # the real reference's own numbers on this workload (BASELINE.md section 2: libgtsam built from /root/reference in the survey container,
@@ -171,6 +203,8 @@ def slam_bench(args):
         inner += opt.timings()["inner_iterations"]
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, opt.values(), {"error": opt.error(), "lambda": opt.lambda_()})
     opt.set_kernel_timing(True)
     opt.restore_values(st)
     opt.iterate()
@@ -452,6 +486,13 @@ def main():
     ap.add_argument("--no-peaks", action="store_true", help="skip the device micro-benchmarks (profiling runs: hundreds of extra launches under PMC)")
     ap.add_argument("--split-root", action="store_true",
                     help="1-GPU rehearsal of the multi-rank data path: one-rank RCCL communicator, chunked all-reduce of the root")
+    ap.add_argument("--full", action="store_true",
+                    help="--workload bal: besides the headline figure, per-kernel times and rooflines, the device micro-benchmarks, the CPU "
+                         "baseline and (--gpus > 1 or --window) the scaling model; --no-kernel-timing / --no-peaks / --no-cpu-baseline "
+                         "leave parts of it out.  The side lines (--workload other than bal) always report everything")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the optimizer's values by variable type, its error and "
+                         "lambda) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.dev_library:
@@ -460,6 +501,8 @@ def main():
     if args.workload != "bal":
         if args.gpus != 1:
             raise SystemExit("--workload sphere2500 / city10000 / victoria_park / isam2 is a single-GPU side line")
+        if args.workload == "isam2" and args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the LM workloads (--workload bal / sphere2500 / city10000 / victoria_park)")
         return isam2_bench(args) if args.workload == "isam2" else slam_bench(args)
     if args.ordering == "colamd":
         raise SystemExit("--ordering colamd is offered for --workload sphere2500 / city10000 (the BAL fixtures carry METIS and Schur)")
@@ -528,7 +571,8 @@ def main():
     for _ in range(args.warmup):
         opt.restore_values(state0)
         opt.iterate()
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         # HIP events around the two roofline kernels only, live in the timed region; the other categories (whose events would cost the
         # timed region ~0.08 ms of idle device time per step) are measured on one more iteration behind it
         opt.set_kernel_timing(2)
@@ -549,7 +593,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    kt = opt.kernel_times() if not args.no_kernel_timing else None
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, opt.values(), {"error": opt.error(), "lambda": opt.lambda_()})
+    kt = opt.kernel_times() if kernel_timing else None
     e_final = opt.error()  # error after ONE LM iteration from the initial estimate
     kt_all, kt_all_inner = None, 1
     if kt is not None:  # every category, outside the timed region
@@ -584,7 +630,7 @@ def main():
                                                                       "for one rank replicated after ncclAllReduce of their partial assemblies",
                        # what the ownership rule gives this graph with more ranks (structure-only model; the dense C4 root is all of the work above the
                        # leaves and stays replicated: <= ~1.2x; with --window the camera subtrees shard)
-                       **({} if (world == 1 and args.window is None) else {"scaling_model": scaling_model(graph, initial, ordering)})},
+                       **({} if not args.full or (world == 1 and args.window is None) else {"scaling_model": scaling_model(graph, initial, ordering)})},
             "ms_per_linearize": phases["linearize_ms"] / steps,
             "ms_per_eliminate": phases["eliminate_ms"] / max(1, inner),
             "ms_per_backsub": phases["backsub_ms"] / max(1, inner),
@@ -629,7 +675,7 @@ def main():
         from gtsam_personal_amd import _lib
         lib = _lib.load()
         v = ct.c_double()
-        if args.no_peaks:
+        if args.no_peaks or not args.full:
             lib = None
         if lib is not None and lib.lmgpu_peak_mfma_f64(local_rank, 4000, ct.byref(v)) == 0:
             out["measured_peak_mfma_f64_tflops"] = v.value
@@ -656,7 +702,7 @@ def main():
             out["measured_hbm_copy_gbps"] = v.value
             if "roofline_linearize" in out and v.value > 0:
                 out["roofline_linearize"]["frac_of_measured_copy"] = out["roofline_linearize"]["achieved"] / v.value
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             size_key = (args.cams, args.points, args.obs, args.seed)
             full_tag = {(1000, 100000, 10, 42): "c4_seed42", (100, 10000, 10, 42): "bal100_seed42"}.get(size_key) if args.window is None else \
                 {(1000, 100000, 10, 42, 40): "c4band_seed42"}.get(size_key + (args.window,))

@@ -201,7 +201,7 @@ def test_block_backsolve_runs_over_levels_are_bitwise_the_per_level_launches(mon
 
 
 def test_kernel_timers_modes():
-    """lmgpu_set_kernel_timing: 1 = every category, 2 = only the roofline kernels (what bench.py keeps inside its timed region); the
+    """lmgpu_set_kernel_timing: 1 = every category, 2 = only the roofline kernels (what bench.py --full keeps inside its timed region); the
     timers never change results"""
     graph, initial, _, ordering = make_bal(n_cam=64, n_pt=1600, obs_per_point=8, seed=17)
     outs = {}

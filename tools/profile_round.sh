@@ -5,9 +5,9 @@ R=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$R
 mkdir -p $O
-python bench.py --steps 20 > $O/bench_c4.json 2> $O/bench_c4.err
-python bench.py --ordering schur --steps 20 --no-cpu-baseline > $O/bench_c4_schur.json 2>> $O/bench_c4.err
-python bench.py --window 40 --steps 10 --no-cpu-baseline > $O/bench_c4band_metis.json 2>> $O/bench_c4.err
+python bench.py --full --steps 20 > $O/bench_c4.json 2> $O/bench_c4.err
+python bench.py --full --ordering schur --steps 20 --no-cpu-baseline > $O/bench_c4_schur.json 2>> $O/bench_c4.err
+python bench.py --full --window 40 --steps 10 --no-cpu-baseline > $O/bench_c4band_metis.json 2>> $O/bench_c4.err
 for w in sphere2500 city10000 victoria_park; do for o in colamd metis; do python bench.py --workload $w --ordering $o --steps 20 > $O/bench_${w}_${o}.json 2>> $O/bench_slam.err; done; done
 python bench.py --workload isam2 --steps 5 > $O/bench_isam2.json 2>> $O/bench_slam.err
 echo "bench lines done" >> $O/progress.txt
