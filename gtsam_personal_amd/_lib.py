@@ -61,6 +61,20 @@ class lmgpu_timings(ct.Structure):
                 ("retract_error_ms", ct.c_double), ("total_ms", ct.c_double), ("inner_iterations", ct.c_int32)]
 
 
+LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY, LMGPU_SOLVER_PCG = 0, 1
+LMGPU_PRECOND_DUMMY, LMGPU_PRECOND_BLOCK_JACOBI = 0, 1
+
+
+class lmgpu_pcg_params(ct.Structure):
+    _fields_ = [("preconditioner", ct.c_int32), ("minIterations", ct.c_int32), ("maxIterations", ct.c_int32), ("reset", ct.c_int32),
+                ("epsilon_rel", ct.c_double), ("epsilon_abs", ct.c_double)]
+
+
+class lmgpu_pcg_stats(ct.Structure):
+    _fields_ = [("iterations", ct.c_int32), ("host_waits", ct.c_int32), ("gamma0", ct.c_double), ("gamma", ct.c_double),
+                ("threshold", ct.c_double), ("precond_ms", ct.c_double), ("iterate_ms", ct.c_double)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -93,6 +107,8 @@ SYMBOLS = {
     "lmgpu_dl_iterate": (ct.c_int, [_H, ct.POINTER(lmgpu_lm_state)]),
     "lmgpu_dl_optimize": (ct.c_int, [_H, ct.POINTER(lmgpu_lm_params), ct.POINTER(lmgpu_lm_state)]),
     "lmgpu_get_timings": (ct.c_int, [_H, ct.POINTER(lmgpu_timings)]),
+    "lmgpu_set_linear_solver": (ct.c_int, [_H, ct.c_int32, ct.POINTER(lmgpu_pcg_params)]),
+    "lmgpu_get_pcg_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_pcg_stats)]),
     "lmgpu_set_kernel_timing": (ct.c_int, [_H, ct.c_int32]),
     "lmgpu_get_kernel_times": (ct.c_int, [_H, _D, _D, ct.POINTER(ct.c_int64)]),
     "lmgpu_get_jacobian": (ct.c_int, [_H, ct.c_int32, _D, _I, _I]),

@@ -35,6 +35,7 @@
 #include "kernels_level.hpp"
 #include "kernels_bayes.hpp"
 #include "kernels_schur.hpp"
+#include "kernels_pcg.hpp"
 #include "plan.hpp"
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
@@ -366,6 +367,26 @@ struct lmgpu_handle {
   ncclComm_t comm_data = nullptr;  // the chunked all-reduce of a replicated front's partial assembly: issued on the communication stream only
                                    // (a communicator of its own, so that no communicator is ever driven from two streams at once)
   lmgpu_local_group* lgroup = nullptr;  // test-only in-process communicator (lmgpu_comm_init_local)
+
+  // ---- PCG (kernels_pcg.hpp; lmgpu_set_linear_solver)
+  int solver = LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY;
+  lmgpu_pcg_params pcgp{LMGPU_PRECOND_BLOCK_JACOBI, 1, 500, 501, 1e-3, 1e-3};
+  bool pcg_structure = false;   // finalized under PCG: no symbolic analysis, no fronts
+  bool pcg_ready = false;       // the PCG buffers below exist
+  bool pcg_gram_valid = false;  // pcg_H / pcg_rhs hold the blocks of the current linearization
+  bool pcg_have_stats = false;
+  bool pcg_fused = false;       // LMGPU_PCG_FUSED=1 (test library): the forward product recomputed inside the transpose gather (A/B)
+  int pcg_cap = 0;              // iterations pcg_gam / pcg_done can hold
+  int32_t* pcg_xoff = nullptr;
+  int64_t *pcg_loff = nullptr, *pcg_yoff = nullptr;
+  double *pcg_H = nullptr, *pcg_L = nullptr, *pcg_rhs = nullptr, *pcg_r = nullptr, *pcg_p = nullptr, *pcg_q = nullptr, *pcg_y = nullptr,
+         *pcg_part = nullptr, *pcg_gam = nullptr;
+  int32_t* pcg_done = nullptr;
+  PcgCtl* pcg_ctl = nullptr;
+  PcgCtl* h_pcg_ctl = nullptr;   // pinned
+  int32_t* h_pcg_done = nullptr; // pinned
+  hipEvent_t pcg_ev[3] = {nullptr, nullptr, nullptr};
+  lmgpu_pcg_stats pcg_stats{};
 };
 
 namespace {
@@ -543,6 +564,7 @@ int do_linearize(lmgpu_handle* h) {
   HIPCHECK(hipGetLastError());
   h->linearized = true;
   h->have_jacobians = true;
+  h->pcg_gram_valid = false;
   return LMGPU_OK;
 }
 
@@ -1187,6 +1209,185 @@ int do_backsub(lmgpu_handle* h) {
 __global__ void set_scalar_kernel(double* p, double v) { *p = v; }
 
 
+// ---- PCG (kernels_pcg.hpp): buffers at first use (a handle finalized for Cholesky may switch over later)
+int pcg_ensure(lmgpu_handle* h) {
+  if (h->pcg_ready) return LMGPU_OK;
+  const Plan& P = h->plan;
+  std::vector<int32_t> xo(P.xoff.begin(), P.xoff.begin() + P.n_vars + 1);
+  std::vector<int64_t> loff(P.n_vars);
+  int64_t lsz = 0;
+  for (int s = 0; s < P.n_vars; s++) {
+    loff[s] = lsz;
+    lsz += (int64_t)P.dims[s] * P.dims[s];
+  }
+  std::vector<FacDesc> fd(h->nfac);
+  HIPCHECK(hipMemcpy(fd.data(), h->d_fd, fd.size() * sizeof(FacDesc), hipMemcpyDeviceToHost));
+  std::vector<int64_t> yoff(h->nfac);
+  int64_t ysz = 0;
+  for (int f = 0; f < h->nfac; f++) {
+    yoff[f] = ysz;
+    ysz += fd[f].rows;
+  }
+  int rc;
+  if ((rc = upload(h, &h->pcg_xoff, xo))) return rc;
+  if ((rc = upload(h, &h->pcg_loff, loff))) return rc;
+  if ((rc = upload(h, &h->pcg_yoff, yoff))) return rc;
+  const size_t n = std::max(1, h->ntot);
+  HIPCHECK(hipMalloc((void**)&h->pcg_H, std::max<int64_t>(1, lsz) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_L, std::max<int64_t>(1, lsz) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_rhs, n * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_r, n * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_p, n * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_q, n * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_y, std::max<int64_t>(1, ysz) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_part, 3 * PCG_MAXPART * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->pcg_ctl, sizeof(PcgCtl)));
+  HIPCHECK(hipHostMalloc((void**)&h->h_pcg_ctl, sizeof(PcgCtl), hipHostMallocDefault));
+  HIPCHECK(hipHostMalloc((void**)&h->h_pcg_done, sizeof(int32_t), hipHostMallocDefault));
+  for (int i = 0; i < 3; i++) HIPCHECK(hipEventCreate(&h->pcg_ev[i]));
+  h->pcg_ready = true;
+  return LMGPU_OK;
+}
+
+__global__ void pcg_reset_ctl_kernel(PcgCtl* c) {
+  c->status = 0x7fffffff;
+  c->iters = 0;
+}
+
+// One PCG solve into h->delta, then the two linear errors like solve_sequence.  The loop is queued 16 iterations at a time with one
+// host wait per chunk (a chunk queued after convergence would do nothing: every kernel of iteration k first reads done[k - 1]).
+int pcg_solve_enqueue(lmgpu_handle* h, double lambda) {
+  int rc = pcg_ensure(h);
+  if (rc) return rc;
+  const lmgpu_pcg_params& pp = h->pcgp;
+  if (pp.maxIterations + 1 > h->pcg_cap) {
+    if (h->pcg_gam) (void)hipFree(h->pcg_gam);
+    if (h->pcg_done) (void)hipFree(h->pcg_done);
+    h->pcg_gam = nullptr;
+    h->pcg_done = nullptr;
+    h->pcg_cap = 0;
+    HIPCHECK(hipMalloc((void**)&h->pcg_gam, (size_t)(pp.maxIterations + 1) * sizeof(double)));
+    HIPCHECK(hipMalloc((void**)&h->pcg_done, (size_t)(pp.maxIterations + 1) * sizeof(int32_t)));
+    h->pcg_cap = pp.maxIterations + 1;
+  }
+  hipStream_t s = h->stream;
+  const bool bj = pp.preconditioner == LMGPU_PRECOND_BLOCK_JACOBI;
+  const int nv = h->plan.n_vars, ntot = h->ntot, nfac = h->nfac;
+  const PcgVars V{nv, h->pcg_xoff, h->pcg_loff};
+  const int gs = std::max(1, std::min(PCG_MAXPART, (ntot + 255) / 256));  // scalar kernels (their partials: p . q)
+  const int gv = std::max(1, std::min(PCG_MAXPART, (nv + 255) / 256));    // variable kernels (their partials: r . r)
+  const int gf = std::max(1, (nfac + 255) / 256);
+  double* part_pq = h->pcg_part;
+  double* part_rr = h->pcg_part + PCG_MAXPART;
+  double* part_rs = h->pcg_part + 2 * PCG_MAXPART;  // r . r of the initial / a reset residual
+  const double* L = h->pcg_L;
+  double* x = h->delta;
+  (void)hipEventRecord(h->ev[1], s);
+  (void)hipEventRecord(h->pcg_ev[0], s);
+  hipLaunchKernelGGL(pcg_reset_ctl_kernel, dim3(1), dim3(1), 0, s, h->pcg_ctl);
+  if (!h->pcg_gram_valid && ntot > 0) {
+    hipLaunchKernelGGL(pcg_gram_kernel, dim3((ntot + 255) / 256), dim3(256), 0, s, ntot, (const int32_t*)h->d_scalar_var,
+                       (const int32_t*)h->d_scalar_col, (const int32_t*)h->d_vi_ptr, (const int32_t*)h->d_vi_fac, (const int8_t*)h->d_vi_pos,
+                       (const FacDesc*)h->d_fd, (const double*)h->pool, V, h->pcg_H, h->pcg_rhs);
+    h->pcg_gram_valid = true;
+  }
+  if (bj) hipLaunchKernelGGL(pcg_chol_kernel, dim3((nv + 255) / 256), dim3(256), 0, s, V, (const double*)h->pcg_H, lambda, (const double*)h->dampw, h->pcg_L, h->pcg_ctl);
+  (void)hipEventRecord(h->pcg_ev[1], s);
+  if (bj)
+    hipLaunchKernelGGL((pcg_precond_kernel<true, true>), dim3(gv), dim3(256), 0, s, V, L, (const double*)h->pcg_rhs, x, h->pcg_r, h->pcg_p, part_rs, (const int32_t*)nullptr, 0);
+  else
+    hipLaunchKernelGGL((pcg_precond_kernel<true, false>), dim3(gv), dim3(256), 0, s, V, L, (const double*)h->pcg_rhs, x, h->pcg_r, h->pcg_p, part_rs, (const int32_t*)nullptr, 0);
+  hipLaunchKernelGGL(pcg_start_kernel, dim3(1), dim3(256), 0, s, (const double*)part_rs, gv, pp.epsilon_rel, pp.epsilon_abs, pp.minIterations,
+                     pp.maxIterations, h->pcg_gam, h->pcg_done, h->pcg_ctl);
+  int waits = 0;
+  const bool fz = h->pcg_fused;
+  for (int k = 1; k <= pp.maxIterations;) {
+    const int kend = std::min(pp.maxIterations, k + 15);
+    for (; k <= kend; k++) {
+      const int rs = (k % pp.reset == 0) ? 1 : 0;
+      const int32_t* dn = h->pcg_done;
+      if (rs) {  // r = L^-1 (b - A x), p = L^-T r, gamma = r . r  (ConjugateGradientSolver.h:149-154)
+        if (!fz)
+          hipLaunchKernelGGL(pcg_forward_kernel, dim3(gf), dim3(256), 0, s, (const FacDesc*)h->d_fd, nfac, (const int64_t*)h->pcg_yoff,
+                             (const double*)h->pool, (const double*)x, h->pcg_y, dn, k);
+        hipLaunchKernelGGL((fz ? pcg_transpose_kernel<true, true> : pcg_transpose_kernel<true, false>), dim3(gs), dim3(256), 0, s, ntot, (const int32_t*)h->d_scalar_var, (const int32_t*)h->d_scalar_col,
+                           (const int32_t*)h->d_vi_ptr, (const int32_t*)h->d_vi_fac, (const int8_t*)h->d_vi_pos, (const FacDesc*)h->d_fd,
+                           (const double*)h->pool, (const int64_t*)h->pcg_yoff, (const double*)h->pcg_y, (const double*)x, lambda,
+                           (const double*)h->dampw, (const double*)h->pcg_rhs, h->pcg_q, (double*)nullptr, dn, k);
+        if (bj)
+          hipLaunchKernelGGL((pcg_precond_kernel<false, true>), dim3(gv), dim3(256), 0, s, V, L, (const double*)h->pcg_q, x, h->pcg_r, h->pcg_p, part_rs, dn, k);
+        else
+          hipLaunchKernelGGL((pcg_precond_kernel<false, false>), dim3(gv), dim3(256), 0, s, V, L, (const double*)h->pcg_q, x, h->pcg_r, h->pcg_p, part_rs, dn, k);
+      }
+      // q = A p
+      if (!fz)
+        hipLaunchKernelGGL(pcg_forward_kernel, dim3(gf), dim3(256), 0, s, (const FacDesc*)h->d_fd, nfac, (const int64_t*)h->pcg_yoff,
+                           (const double*)h->pool, (const double*)h->pcg_p, h->pcg_y, dn, k);
+      hipLaunchKernelGGL((fz ? pcg_transpose_kernel<false, true> : pcg_transpose_kernel<false, false>), dim3(gs), dim3(256), 0, s, ntot, (const int32_t*)h->d_scalar_var, (const int32_t*)h->d_scalar_col,
+                         (const int32_t*)h->d_vi_ptr, (const int32_t*)h->d_vi_fac, (const int8_t*)h->d_vi_pos, (const FacDesc*)h->d_fd,
+                         (const double*)h->pool, (const int64_t*)h->pcg_yoff, (const double*)h->pcg_y, (const double*)h->pcg_p, lambda,
+                         (const double*)h->dampw, (const double*)h->pcg_rhs, h->pcg_q, part_pq, dn, k);
+      if (bj) {
+        hipLaunchKernelGGL(pcg_update_kernel<true>, dim3(gv), dim3(256), 0, s, V, L, (const double*)part_pq, gs, (const double*)part_rs, gv,
+                           (const double*)h->pcg_gam, (const double*)h->pcg_p, (const double*)h->pcg_q, x, h->pcg_r, part_rr, dn, k, rs);
+        hipLaunchKernelGGL(pcg_direction_kernel<true>, dim3(gv), dim3(256), 0, s, V, L, (const double*)part_rr, gv, (const double*)part_rs, gv,
+                           h->pcg_gam, (const double*)h->pcg_r, h->pcg_p, h->pcg_done, h->pcg_ctl, k, rs, pp.minIterations, pp.maxIterations);
+      } else {
+        hipLaunchKernelGGL(pcg_update_kernel<false>, dim3(gv), dim3(256), 0, s, V, L, (const double*)part_pq, gs, (const double*)part_rs, gv,
+                           (const double*)h->pcg_gam, (const double*)h->pcg_p, (const double*)h->pcg_q, x, h->pcg_r, part_rr, dn, k, rs);
+        hipLaunchKernelGGL(pcg_direction_kernel<false>, dim3(gv), dim3(256), 0, s, V, L, (const double*)part_rr, gv, (const double*)part_rs, gv,
+                           h->pcg_gam, (const double*)h->pcg_r, h->pcg_p, h->pcg_done, h->pcg_ctl, k, rs, pp.minIterations, pp.maxIterations);
+      }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(h->h_pcg_done, h->pcg_done + kend, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(&h->h_pcg_ctl->status, &h->pcg_ctl->status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    waits++;
+    if (h->h_pcg_ctl->status != 0x7fffffff) break;  // an indefinite diagonal block: the iterations are meaningless
+    if (*h->h_pcg_done) break;
+  }
+  (void)hipEventRecord(h->pcg_ev[2], s);
+  (void)hipEventRecord(h->ev[2], s);
+  (void)hipEventRecord(h->ev[3], s);  // no back-substitution: backsub_ms = 0
+  if (nfac > 0)
+    hipLaunchKernelGGL(linear_error_kernel, dim3((nfac + 255) / 256), dim3(256), 0, s, (const FacDesc*)h->d_fd, nfac, (const double*)h->pool,
+                       (const double*)x, h->ebuf0, h->ebuf1);
+  reduce_to(h, h->ebuf0, h->n_counted, h->dscal + 1);
+  reduce_to(h, h->ebuf1, h->n_counted, h->dscal + 2);
+  (void)hipEventRecord(h->ev[4], s);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(h->h_scal + 1, h->dscal + 1, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(h->h_pcg_ctl, h->pcg_ctl, sizeof(PcgCtl), hipMemcpyDeviceToHost, s));
+  h->pcg_stats.host_waits = waits + 1;  // + the wait of do_solve_finish
+  return LMGPU_OK;
+}
+
+int pcg_solve_finish(lmgpu_handle* h) {
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->kt.resolve();
+  h->solved = true;
+  const PcgCtl& c = *h->h_pcg_ctl;
+  lmgpu_pcg_stats& st = h->pcg_stats;
+  st.iterations = c.iters;
+  st.gamma0 = c.gamma0;
+  st.gamma = c.gamma;
+  st.threshold = c.threshold;
+  float ms = 0;
+  st.precond_ms = (hipEventElapsedTime(&ms, h->pcg_ev[0], h->pcg_ev[1]) == hipSuccess) ? ms : 0.0;
+  st.iterate_ms = (hipEventElapsedTime(&ms, h->pcg_ev[1], h->pcg_ev[2]) == hipSuccess) ? ms : 0.0;
+  h->pcg_have_stats = true;
+  if (c.status != 0x7fffffff) {
+    h->failed_slot = c.status;
+    h->err = "PCG: the diagonal block of variable slot " + std::to_string(c.status) + " is not positive definite";
+    return LMGPU_INDETERMINATE;
+  }
+  return LMGPU_OK;
+}
+
+// the solver a solve of this handle takes (the marginal covariances always eliminate: they need the direct path's unit-gradient solves)
+static bool use_pcg(const lmgpu_handle* h) { return h->solver == LMGPU_SOLVER_PCG && !h->gex_active; }
+
 // everything of one damped solve that is queued on the stream
 int solve_sequence(lmgpu_handle* h, bool phase_events, double lambda_v, const double* lambda_p) {
   hipStream_t s = h->stream;
@@ -1221,6 +1422,7 @@ static bool graph_eligible(const lmgpu_handle* h) {
 }
 
 int do_solve_enqueue(lmgpu_handle* h, double lambda) {
+  if (use_pcg(h)) return pcg_solve_enqueue(h, lambda);
   hipStream_t s = h->stream;
   (void)hipEventRecord(h->ev[1], s);
   int rc;
@@ -1256,6 +1458,7 @@ int do_solve_enqueue(lmgpu_handle* h, double lambda) {
 }
 
 int do_solve_finish(lmgpu_handle* h) {
+  if (use_pcg(h)) return pcg_solve_finish(h);
   HIPCHECK(hipStreamSynchronize(h->stream));
   h->kt.resolve();
   h->solved = true;
@@ -1542,6 +1745,10 @@ int dl_iterate(lmgpu_handle* h) {
     h->err = "Dogleg is single-rank in this round";
     return LMGPU_INVALID;
   }
+  if (h->solver == LMGPU_SOLVER_PCG) {  // DoglegOptimizer.cpp:108-113 throws for iterative linear solvers
+    h->err = "Dogleg is not compatible with the conjugate gradient solver (it needs the Bayes tree of the direct solver)";
+    return LMGPU_INVALID;
+  }
   hipStream_t s = h->stream;
   std::memset(&h->tim, 0, sizeof(h->tim));
   if (!h->bt_vec) HIPCHECK(hipMalloc((void**)&h->bt_vec, std::max(1, h->ntot) * sizeof(double)));
@@ -1738,6 +1945,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) h->wide16_max = atoi(e);
   h->bsd_ticket = dev_switch("LMGPU_BSD_TICKET") != nullptr;
   h->no_gather_write = dev_switch("LMGPU_NO_GATHER_WRITE") != nullptr;
+  h->pcg_fused = dev_switch("LMGPU_PCG_FUSED") != nullptr;
   if (dev_switch("LMGPU_NO_MERGE")) h->chain_merge = false;
   if (const char* e = dev_switch("LMGPU_CHAIN_SPLIT")) h->chain_split_pct = std::max(0, std::min(100, atoi(e)));
   if (const char* e = dev_switch("LMGPU_CHAIN_FAR")) h->chain_far_pct = std::max(10, std::min(100, atoi(e)));
@@ -1800,6 +2008,12 @@ int lmgpu_destroy(lmgpu_handle* h) {
     fr(h->gex); fr(h->delta); fr(h->dampw); fr(h->hdiag); fr(h->ebuf0); fr(h->ebuf1); fr(h->partial); fr(h->dscal); fr(h->ywork); fr(h->d_status);
     fr(h->d_fd); fr(h->d_fronts); fr(h->d_ffac); fr(h->d_childs); fr(h->d_cmap); fr(h->d_fxoff); fr(h->d_sxoff); fr(h->d_lists); fr(h->d_hbm_small); fr(h->d_med_list); fr(h->d_med_fronts); fr(h->inv16_med); fr(h->bt_ebuf); fr(h->bt_vec); fr(h->bt_part); fr(h->d_bt_part_off); fr(h->d_bt_ptr); fr(h->d_bt_idx); fr(h->d_f_ld); fr(h->d_f_off);
     fr(h->d_scalar_var); fr(h->d_scalar_col); fr(h->d_vi_ptr); fr(h->d_vi_fac); fr(h->d_vi_pos);
+    fr(h->pcg_xoff); fr(h->pcg_loff); fr(h->pcg_yoff); fr(h->pcg_H); fr(h->pcg_L); fr(h->pcg_rhs); fr(h->pcg_r); fr(h->pcg_p); fr(h->pcg_q);
+    fr(h->pcg_y); fr(h->pcg_part); fr(h->pcg_gam); fr(h->pcg_done); fr(h->pcg_ctl);
+    if (h->h_pcg_ctl) (void)hipHostFree(h->h_pcg_ctl);
+    if (h->h_pcg_done) (void)hipHostFree(h->h_pcg_done);
+    for (int i = 0; i < 3; i++)
+      if (h->pcg_ev[i]) (void)hipEventDestroy(h->pcg_ev[i]);
     for (Bucket& b : h->buckets) {
       fr(b.d_vidx); fr(b.d_meas); fr(b.d_noise); fr(b.d_epos);
     }
@@ -1903,13 +2117,97 @@ int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, con
   return LMGPU_OK;
 }
 
+// the device arrays every solver needs: per-bucket inputs, values, the variable -> factor incidence (hessianDiagonal, PCG), vectors
+static int finalize_vectors(lmgpu_handle* h) {
+  const Plan& P = h->plan;
+  const int NFAC = (int)P.factors.size();
+  int rc;
+  // per-bucket arrays, compacted to this rank's factors
+  {
+    std::vector<std::vector<int32_t>> epos(h->buckets.size());
+    for (size_t bi = 0; bi < h->buckets.size(); bi++) epos[bi].resize(h->buckets[bi].n_loc);
+    for (int i = 0; i < NFAC; i++)
+      if (h->fac_local[i] >= 0) epos[P.factors[i].bucket][h->buckets[P.factors[i].bucket].loc_of[P.factors[i].idx]] = h->fac_local[i];
+    for (size_t bi = 0; bi < h->buckets.size(); bi++) {
+      Bucket& b = h->buckets[bi];
+      const int ar = kFactorArity[b.type], ml = kFactorMeas[b.type];
+      const int nl = b.noise_kind == LMGPU_N_DIAG ? b.rows : (b.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
+      std::vector<int32_t> vidx((size_t)b.n_loc * ar);
+      std::vector<double> meas((size_t)b.n_loc * ml), noise((size_t)b.n_loc * nl);
+      for (int i = 0; i < b.n; i++) {
+        const int l = b.loc_of[i];
+        if (l < 0) continue;
+        for (int k = 0; k < ar; k++) vidx[(size_t)l * ar + k] = P.tidx[b.slots[(size_t)i * ar + k]];
+        std::memcpy(&meas[(size_t)l * ml], &b.meas[(size_t)i * ml], ml * sizeof(double));
+        if (nl) std::memcpy(&noise[(size_t)l * nl], &b.noise[(size_t)i * nl], nl * sizeof(double));
+      }
+      if ((rc = upload(h, &b.d_vidx, vidx))) return rc;
+      if ((rc = upload(h, &b.d_meas, meas))) return rc;
+      if (nl && (rc = upload(h, &b.d_noise, noise))) return rc;
+      if ((rc = upload(h, &b.d_epos, epos[bi]))) return rc;
+    }
+  }
+  // values, per type
+  for (int t = 0; t < kNumVarTypes; t++) {
+    const size_t bytes = std::max<size_t>(1, (size_t)P.type_count[t] * kVarStore[t]) * sizeof(double);
+    HIPCHECK(hipMalloc((void**)&h->vals[0][t], bytes));
+    HIPCHECK(hipMalloc((void**)&h->vals[1][t], bytes));
+    std::vector<int32_t> xo(P.type_count[t]);
+    for (int s = 0; s < P.n_vars; s++)
+      if (P.types[s] == t) xo[P.tidx[s]] = P.xoff[s];
+    if ((rc = upload(h, &h->type_xoff[t], xo))) return rc;
+  }
+  // hessian-diagonal CSR over the factors COUNTED on this rank (summed over ranks by all-reduce)
+  {
+    std::vector<int32_t> scalar_var(h->ntot), scalar_col(h->ntot), vi_ptr(P.n_vars + 1, 0), vi_fac;
+    std::vector<int8_t> vi_pos;
+    for (int s = 0; s < P.n_vars; s++)
+      for (int d = 0; d < P.dims[s]; d++) {
+        scalar_var[P.xoff[s] + d] = s;
+        scalar_col[P.xoff[s] + d] = d;
+      }
+    std::vector<std::vector<std::pair<int32_t, int8_t>>> vi(P.n_vars);
+    for (int i = 0; i < NFAC; i++) {
+      const int l = h->fac_local[i];
+      if (l < 0 || l >= h->n_counted) continue;
+      for (int k = 0; k < kMaxArity; k++)
+        if (P.factors[i].slots[k] >= 0) vi[P.factors[i].slots[k]].push_back({l, (int8_t)k});
+    }
+    for (int s = 0; s < P.n_vars; s++) {
+      vi_ptr[s] = (int32_t)vi_fac.size();
+      for (auto& pr : vi[s]) {
+        vi_fac.push_back(pr.first);
+        vi_pos.push_back(pr.second);
+      }
+    }
+    vi_ptr[P.n_vars] = (int32_t)vi_fac.size();
+    if ((rc = upload(h, &h->d_scalar_var, scalar_var))) return rc;
+    if ((rc = upload(h, &h->d_scalar_col, scalar_col))) return rc;
+    if ((rc = upload(h, &h->d_vi_ptr, vi_ptr))) return rc;
+    if ((rc = upload(h, &h->d_vi_fac, vi_fac))) return rc;
+    if ((rc = upload(h, &h->d_vi_pos, vi_pos))) return rc;
+  }
+  HIPCHECK(hipMalloc((void**)&h->delta, h->ntot * sizeof(double)));
+  HIPCHECK(hipMemset(h->delta, 0, h->ntot * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->dampw, h->ntot * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->hdiag, h->ntot * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->ebuf0, std::max(1, h->nfac) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->ebuf1, std::max(1, h->nfac) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->partial, 256 * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->dscal, 8 * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->ywork, std::max(1, P.max_front_n) * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->d_status, 2 * sizeof(int)));
+  return LMGPU_OK;
+}
+
 int lmgpu_finalize_structure(lmgpu_handle* h) {
   if (!h) return LMGPU_INVALID;
   if (h->finalized) {
     h->err = "lmgpu_finalize_structure: refused (h->finalized)";
     return LMGPU_INVALID;
   }
-  std::string e = h->plan.build(kLdsLimitN);
+  h->pcg_structure = h->solver == LMGPU_SOLVER_PCG;  // PCG selected before finalize: no symbolic analysis, no fronts
+  std::string e = h->plan.build(kLdsLimitN, !h->pcg_structure);
   if (!e.empty()) {
     h->err = e;
     return LMGPU_INVALID;
@@ -1937,6 +2235,10 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
       fac_active[f] = 1;
       fac_counted[f] = counted;
     }
+  }
+  if (h->pcg_structure) {  // every factor is local and counted (single rank)
+    std::fill(fac_active.begin(), fac_active.end(), 1);
+    std::fill(fac_counted.begin(), fac_counted.end(), 1);
   }
   h->fac_local.assign(NFAC, -1);
   int nloc = 0;
@@ -2335,6 +2637,10 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
   // once: entries the kernels read but never write (lower triangles inside diagonal tiles, padding columns) must be finite
   HIPCHECK(hipMemset(h->pool, 0, h->pool_doubles * sizeof(double)));
   int rc;
+  if (h->pcg_structure) {  // Jacobians, factor descriptors, incidence list and vectors only
+    if ((rc = upload(h, &h->d_fd, fd))) return rc;
+    return finalize_vectors(h);
+  }
   if (!dev_switch("LMGPU_NO_LEAFPACK")) {  // packed records of the LDS fronts, launch by launch
     std::vector<char> packs;
     for (LevelWork& L : h->levels)
@@ -2573,81 +2879,7 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
   if ((rc = upload(h, &h->d_gvblk, gvblk))) return rc;
   if ((rc = upload(h, &h->d_gvent, gvent))) return rc;
   HIPCHECK(hipMalloc((void**)&h->d_gcorner, std::max<size_t>(1, (size_t)n_gleaf) * sizeof(double)));
-  // per-bucket arrays, compacted to this rank's factors
-  {
-    std::vector<std::vector<int32_t>> epos(h->buckets.size());
-    for (size_t bi = 0; bi < h->buckets.size(); bi++) epos[bi].resize(h->buckets[bi].n_loc);
-    for (int i = 0; i < NFAC; i++)
-      if (h->fac_local[i] >= 0) epos[P.factors[i].bucket][h->buckets[P.factors[i].bucket].loc_of[P.factors[i].idx]] = h->fac_local[i];
-    for (size_t bi = 0; bi < h->buckets.size(); bi++) {
-      Bucket& b = h->buckets[bi];
-      const int ar = kFactorArity[b.type], ml = kFactorMeas[b.type];
-      const int nl = b.noise_kind == LMGPU_N_DIAG ? b.rows : (b.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
-      std::vector<int32_t> vidx((size_t)b.n_loc * ar);
-      std::vector<double> meas((size_t)b.n_loc * ml), noise((size_t)b.n_loc * nl);
-      for (int i = 0; i < b.n; i++) {
-        const int l = b.loc_of[i];
-        if (l < 0) continue;
-        for (int k = 0; k < ar; k++) vidx[(size_t)l * ar + k] = P.tidx[b.slots[(size_t)i * ar + k]];
-        std::memcpy(&meas[(size_t)l * ml], &b.meas[(size_t)i * ml], ml * sizeof(double));
-        if (nl) std::memcpy(&noise[(size_t)l * nl], &b.noise[(size_t)i * nl], nl * sizeof(double));
-      }
-      if ((rc = upload(h, &b.d_vidx, vidx))) return rc;
-      if ((rc = upload(h, &b.d_meas, meas))) return rc;
-      if (nl && (rc = upload(h, &b.d_noise, noise))) return rc;
-      if ((rc = upload(h, &b.d_epos, epos[bi]))) return rc;
-    }
-  }
-  // values, per type
-  for (int t = 0; t < kNumVarTypes; t++) {
-    const size_t bytes = std::max<size_t>(1, (size_t)P.type_count[t] * kVarStore[t]) * sizeof(double);
-    HIPCHECK(hipMalloc((void**)&h->vals[0][t], bytes));
-    HIPCHECK(hipMalloc((void**)&h->vals[1][t], bytes));
-    std::vector<int32_t> xo(P.type_count[t]);
-    for (int s = 0; s < P.n_vars; s++)
-      if (P.types[s] == t) xo[P.tidx[s]] = P.xoff[s];
-    if ((rc = upload(h, &h->type_xoff[t], xo))) return rc;
-  }
-  // hessian-diagonal CSR over the factors COUNTED on this rank (summed over ranks by all-reduce)
-  {
-    std::vector<int32_t> scalar_var(h->ntot), scalar_col(h->ntot), vi_ptr(P.n_vars + 1, 0), vi_fac;
-    std::vector<int8_t> vi_pos;
-    for (int s = 0; s < P.n_vars; s++)
-      for (int d = 0; d < P.dims[s]; d++) {
-        scalar_var[P.xoff[s] + d] = s;
-        scalar_col[P.xoff[s] + d] = d;
-      }
-    std::vector<std::vector<std::pair<int32_t, int8_t>>> vi(P.n_vars);
-    for (int i = 0; i < NFAC; i++) {
-      const int l = h->fac_local[i];
-      if (l < 0 || l >= h->n_counted) continue;
-      for (int k = 0; k < kMaxArity; k++)
-        if (P.factors[i].slots[k] >= 0) vi[P.factors[i].slots[k]].push_back({l, (int8_t)k});
-    }
-    for (int s = 0; s < P.n_vars; s++) {
-      vi_ptr[s] = (int32_t)vi_fac.size();
-      for (auto& pr : vi[s]) {
-        vi_fac.push_back(pr.first);
-        vi_pos.push_back(pr.second);
-      }
-    }
-    vi_ptr[P.n_vars] = (int32_t)vi_fac.size();
-    if ((rc = upload(h, &h->d_scalar_var, scalar_var))) return rc;
-    if ((rc = upload(h, &h->d_scalar_col, scalar_col))) return rc;
-    if ((rc = upload(h, &h->d_vi_ptr, vi_ptr))) return rc;
-    if ((rc = upload(h, &h->d_vi_fac, vi_fac))) return rc;
-    if ((rc = upload(h, &h->d_vi_pos, vi_pos))) return rc;
-  }
-  HIPCHECK(hipMalloc((void**)&h->delta, h->ntot * sizeof(double)));
-  HIPCHECK(hipMemset(h->delta, 0, h->ntot * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->dampw, h->ntot * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->hdiag, h->ntot * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->ebuf0, std::max(1, h->nfac) * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->ebuf1, std::max(1, h->nfac) * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->partial, 256 * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->dscal, 8 * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->ywork, std::max(1, P.max_front_n) * sizeof(double)));
-  HIPCHECK(hipMalloc((void**)&h->d_status, 2 * sizeof(int)));
+  if ((rc = finalize_vectors(h))) return rc;
   {
     int max_nf = 1;
     for (int fi = 0; fi < NF; fi++)
@@ -2810,6 +3042,10 @@ int lmgpu_joint_marginal_covariance(lmgpu_handle* h, int32_t nslots, const int32
   }
   if (h->cfg.world_size > 1) {
     h->err = "marginal covariances are computed on one GPU";
+    return LMGPU_INVALID;
+  }
+  if (h->pcg_structure) {
+    h->err = "marginal covariances need the fronts of the direct solver; this handle was finalized under PCG";
     return LMGPU_INVALID;
   }
   int rc = need_device(h);
@@ -2984,6 +3220,10 @@ int lmgpu_dl_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state*
   }
   int rc = need_device(h);
   if (rc) return rc;
+  if (h->solver == LMGPU_SOLVER_PCG) {
+    h->err = "Dogleg is not compatible with the conjugate gradient solver (it needs the Bayes tree of the direct solver)";
+    return LMGPU_INVALID;
+  }
   if (inout) h->lm = *inout;
   double currentError = h->lm.error;
   if (!(currentError <= p->errorTol || h->lm.iterations >= p->maxIterations)) {
@@ -3033,6 +3273,40 @@ int lmgpu_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* in
 int lmgpu_get_timings(const lmgpu_handle* h, lmgpu_timings* out) {
   if (!h || !out) return LMGPU_INVALID;
   *out = h->tim;
+  return LMGPU_OK;
+}
+
+int lmgpu_set_linear_solver(lmgpu_handle* h, int32_t solver, const lmgpu_pcg_params* pcg) {
+  if (!h) return LMGPU_INVALID;
+  if (solver == LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY) {
+    if (h->pcg_structure) {
+      h->err = "lmgpu_set_linear_solver: this handle was finalized under PCG and has no fronts to eliminate";
+      return LMGPU_INVALID;
+    }
+    h->solver = solver;
+    return LMGPU_OK;
+  }
+  if (solver != LMGPU_SOLVER_PCG || !pcg) {
+    h->err = "lmgpu_set_linear_solver: unknown solver, or PCG without parameters (NonlinearOptimizer.cpp:156-158)";
+    return LMGPU_INVALID;
+  }
+  if (h->cfg.world_size > 1 || (h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT)) {
+    h->err = "lmgpu_set_linear_solver: PCG is single-rank";
+    return LMGPU_INVALID;
+  }
+  if ((pcg->preconditioner != LMGPU_PRECOND_DUMMY && pcg->preconditioner != LMGPU_PRECOND_BLOCK_JACOBI) || pcg->minIterations < 0 ||
+      pcg->maxIterations < 0 || pcg->maxIterations > (1 << 28) || pcg->reset < 1 || !(pcg->epsilon_rel >= 0.0) || !(pcg->epsilon_abs >= 0.0)) {
+    h->err = "lmgpu_set_linear_solver: invalid PCG parameters (preconditioner 0 / 1, iterations >= 0, reset >= 1, epsilons >= 0)";
+    return LMGPU_INVALID;
+  }
+  h->solver = solver;
+  h->pcgp = *pcg;
+  return LMGPU_OK;
+}
+
+int lmgpu_get_pcg_stats(const lmgpu_handle* h, lmgpu_pcg_stats* out) {
+  if (!h || !out || !h->pcg_have_stats) return LMGPU_INVALID;
+  *out = h->pcg_stats;
   return LMGPU_OK;
 }
 

@@ -177,7 +177,7 @@ std::string symbolic_multifrontal(int32_t n, const std::vector<int32_t>& keyrank
   return "";
 }
 
-std::string Plan::build(int32_t lds_limit_n) {
+std::string Plan::build(int32_t lds_limit_n, bool symbolic) {
   const int32_t n = n_vars;
   if (n <= 0) return "no variables";
   dims.resize(n);
@@ -215,6 +215,15 @@ std::string Plan::build(int32_t lds_limit_n) {
         if (f.slots[q] == f.slots[k]) return "factor with repeated variable";
       fvars[i].push_back(f.slots[k]);
     }
+  }
+  fronts.clear();
+  if (!symbolic) {
+    roots.clear();
+    etree_parent.assign(n, -1);
+    front_of_var.assign(n, -1);
+    n_levels = 0;
+    max_front_n = 0;
+    return "";
   }
   SymbolicFronts sf;
   const std::string e = symbolic_multifrontal(n, keyrank, fvars, &sf);

@@ -80,9 +80,10 @@ struct Plan {
   int32_t n_levels = 0;
   int32_t max_front_n = 0;
 
-  // Build everything.  lds_limit_n: fronts with n <= lds_limit_n are class 0.
+  // Build everything.  lds_limit_n: fronts with n <= lds_limit_n are class 0.  symbolic = false: the variable layout and the
+  // sorted, checked factor list only (no elimination tree, no fronts: the iterative solver needs none).
   // Returns empty string on success, else an error message.
-  std::string build(int32_t lds_limit_n);
+  std::string build(int32_t lds_limit_n, bool symbolic = true);
 };
 
 }  // namespace lmgpu

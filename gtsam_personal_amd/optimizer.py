@@ -4,6 +4,7 @@ Same names / argument meaning / error behaviour as the reference interface it st
   LevenbergMarquardtParams       gtsam/nonlinear/LevenbergMarquardtParams.h:35-157
   LevenbergMarquardtOptimizer    gtsam/nonlinear/LevenbergMarquardtOptimizer.h  (iterate :103, linearize :113, lambda, getInnerIterations)
   NonlinearOptimizer             gtsam/nonlinear/NonlinearOptimizer.h (optimize :98, error, iterations, values, solve :129)
+  PCGSolverParameters            gtsam/linear/PCGSolver.h:36-50, ConjugateGradientSolver.h:34-50 (linearSolverType = "ITERATIVE")
 All numerics run in liblmgpu.so on the GPU; this file only marshals arrays.
 """
 from __future__ import annotations
@@ -17,9 +18,63 @@ from .graph import (CAM_BUNDLER, F_PRIOR_CAM, F_SFM, FACTOR_ARITY, N_UNIT, VAR_D
                     Values)
 
 
+class DummyPreconditionerParameters:
+    """gtsam/linear/Preconditioner.h: the identity preconditioner"""
+    kind = _lib.LMGPU_PRECOND_DUMMY
+
+
+class BlockJacobiPreconditionerParameters:
+    """gtsam/linear/Preconditioner.h: L = chol(H_jj) per variable of the damped graph's hessianBlockDiagonal"""
+    kind = _lib.LMGPU_PRECOND_BLOCK_JACOBI
+
+
+class PCGSolverParameters:
+    """PCGSolverParameters (gtsam/linear/PCGSolver.h:36-50) = ConjugateGradientParameters (ConjugateGradientSolver.h:34-50, defaults
+    minIterations 1, maxIterations 500, reset 501, epsilon_rel 1e-3, epsilon_abs 1e-3) + the preconditioner's parameters (default none:
+    the reference's createPreconditioner throws for it, Preconditioner.cpp:189-205, and so does the optimizer here)."""
+
+    def __init__(self, preconditioner=None):
+        self.minIterations = 1
+        self.maxIterations = 500
+        self.reset = 501
+        self.epsilon_rel = 1e-3
+        self.epsilon_abs = 1e-3
+        self.preconditioner = preconditioner
+
+    def _c(self):
+        pre = self.preconditioner
+        if not isinstance(pre, (DummyPreconditionerParameters, BlockJacobiPreconditionerParameters)):
+            raise ValueError("createPreconditioner: unexpected preconditioner parameter type (Dummy or BlockJacobi are bound)")
+        if int(self.reset) < 1:
+            raise ValueError("PCGSolverParameters.reset must be >= 1")
+        return _lib.lmgpu_pcg_params(pre.kind, int(self.minIterations), int(self.maxIterations), int(self.reset), float(self.epsilon_rel),
+                                     float(self.epsilon_abs))
+
+
+LINEAR_SOLVER_TYPES = ("MULTIFRONTAL_CHOLESKY", "ITERATIVE")
+
+
+def _check_linear_solver(params):
+    """NonlinearOptimizer::solve (NonlinearOptimizer.cpp:154-173): ITERATIVE needs iterativeParams of a bound type.  Returns the
+    lmgpu_pcg_params to select, or None for the direct solver.  Runs before any device handle exists."""
+    t = getattr(params, "linearSolverType", "MULTIFRONTAL_CHOLESKY")
+    if t not in LINEAR_SOLVER_TYPES:
+        raise ValueError(f"linearSolverType {t!r} is not bound (one of {LINEAR_SOLVER_TYPES})")
+    if t != "ITERATIVE":
+        return None
+    ip = getattr(params, "iterativeParams", None)
+    if ip is None:
+        raise RuntimeError("NonlinearOptimizer::solve: cg parameter has to be assigned ...")
+    if not isinstance(ip, PCGSolverParameters):
+        raise RuntimeError("NonlinearOptimizer::solve: special cg parameter type is not handled in LM solver ...")
+    return ip._c()
+
+
 class LevenbergMarquardtParams:
     def __init__(self):
         self.ordering = None
+        self.linearSolverType = "MULTIFRONTAL_CHOLESKY"
+        self.iterativeParams = None
         LevenbergMarquardtParams.SetLegacyDefaults(self)
         self.errorTol = 0.0
         self.minDiagonal = 1e-6
@@ -50,6 +105,9 @@ class LevenbergMarquardtParams:
         p.minModelFidelity = 1e-3
         p.diagonalDamping = True
         p.useFixedLambdaFactor = False
+
+    def isIterative(self):
+        return self.linearSolverType == "ITERATIVE"
 
     @staticmethod
     def LegacyDefaults():
@@ -86,7 +144,10 @@ class LevenbergMarquardtOptimizer:
                  device: int = 0, rank: int = 0, world_size: int = 1, comm_id: bytes | None = None,
                  local_group=None, split_root: bool = False):
         self.params = params or LevenbergMarquardtParams()
+        pcg = _check_linear_solver(self.params)
         ordering = ordering if ordering is not None else self.params.ordering
+        if ordering is None and pcg is not None:
+            ordering = Ordering.Natural(graph)  # PCGSolver's KeyInfo(gfg) orders by key (IterativeSolver.cpp:111-114)
         if ordering is None:
             raise ValueError("an elimination Ordering is required (Ordering.Schur / Ordering.Natural, or COLAMD/METIS from the caller)")
         self.graph, self.ordering = graph, Ordering(ordering)
@@ -125,6 +186,8 @@ class LevenbergMarquardtOptimizer:
             nptr = _dp(np.ascontiguousarray(noise)) if kind != N_UNIT else None
             self._check(self.lib.lmgpu_add_factor_bucket_robust(self._h, ftype, len(gi32), _ip(gi32), _ip(slots), _dp(meas), kind, nptr,
                                                                 models[0].robust_kind, models[0].robust_k))
+        if pcg is not None:  # before finalize: no symbolic analysis, no fronts
+            self._check(self.lib.lmgpu_set_linear_solver(self._h, _lib.LMGPU_SOLVER_PCG, ct.byref(pcg)))
         self._check(self.lib.lmgpu_finalize_structure(self._h))
         self._ntot = self.lib.lmgpu_total_dim(self._h)
         self._nstore = self.lib.lmgpu_total_store(self._h)
@@ -219,6 +282,20 @@ class LevenbergMarquardtOptimizer:
         self._check(self.lib.lmgpu_optimize(self._h, ct.byref(cp), ct.byref(self.state)))
         self._lin_generation = getattr(self, "_lin_generation", 0) + 1
         return self.values()
+
+    def set_linear_solver(self, params):
+        """switch the linear solver of this handle: `params` = a LevenbergMarquardtParams-like object (linearSolverType, iterativeParams)"""
+        pcg = _check_linear_solver(params)
+        if pcg is None:
+            self._check(self.lib.lmgpu_set_linear_solver(self._h, _lib.LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY, None))
+        else:
+            self._check(self.lib.lmgpu_set_linear_solver(self._h, _lib.LMGPU_SOLVER_PCG, ct.byref(pcg)))
+
+    def pcg_stats(self):
+        """statistics of the last PCG solve (lmgpu_get_pcg_stats)"""
+        st = _lib.lmgpu_pcg_stats()
+        self._check(self.lib.lmgpu_get_pcg_stats(self._h, ct.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
 
     def timings(self):
         t = _lib.lmgpu_timings()
@@ -449,6 +526,8 @@ class DoglegOptimizer(LevenbergMarquardtOptimizer):
 
     def __init__(self, graph, initialValues, ordering=None, params=None, **kw):
         params = params or DoglegParams()
+        if getattr(params, "linearSolverType", "MULTIFRONTAL_CHOLESKY") == "ITERATIVE":  # DoglegOptimizer.cpp:108-113
+            raise RuntimeError("Dogleg is not currently compatible with the linear conjugate gradient solver")
         super().__init__(graph, initialValues, ordering, params, **kw)
         self.state.lambda_ = float(getattr(params, "deltaInitial", 1.0))
 

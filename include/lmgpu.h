@@ -207,6 +207,39 @@ int lmgpu_dl_iterate(lmgpu_handle* h, lmgpu_lm_state* inout);
 int lmgpu_dl_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* inout);
 int lmgpu_get_timings(const lmgpu_handle* h, lmgpu_timings* out);
 
+/* ---- linear solver: NonlinearOptimizerParams::linearSolverType (gtsam/nonlinear/NonlinearOptimizerParams.h; dispatch
+ *      NonlinearOptimizer.cpp:154-173).  LMGPU_SOLVER_PCG = Iterative with PCGSolverParameters (gtsam/linear/PCGSolver.h:36-50):
+ *      preconditionedConjugateGradient (gtsam/linear/ConjugateGradientSolver.h:109-171) on A = sum J^T J + lambda D, b = -gradientAtZero
+ *      (GaussianFactorGraphSystem, PCGSolver.cpp:69-145), from x = 0 (IterativeSolver.cpp:92-102).  Preconditioners
+ *      (Preconditioner.cpp:80-177): DUMMY = identity; BLOCK_JACOBI = per variable L = chol(H_jj) of the DAMPED graph's
+ *      hessianBlockDiagonal, left L^-1 x, right L^-T x.  Deviation: a diagonal block that is not positive definite returns
+ *      LMGPU_INDETERMINATE with lmgpu_last_failed_slot = that variable (the reference carries Eigen's failed LLT on silently).
+ *      Reaching maxIterations is not an error (the estimate so far is the step).  lmgpu_solve, lmgpu_iterate, lmgpu_optimize,
+ *      lmgpu_gn_iterate and lmgpu_gn_optimize honour the selection; lmgpu_dl_* return LMGPU_INVALID under PCG (the reference throws,
+ *      DoglegOptimizer.cpp:108-113); so does world_size > 1.  ISAM2 is not affected.
+ *      Selected BEFORE lmgpu_finalize_structure, PCG skips the symbolic analysis and all front memory: the handle has no fronts
+ *      (lmgpu_num_fronts 0; lmgpu_get_front, the marginal covariances and switching back to Cholesky return LMGPU_INVALID).
+ *      A handle finalized for Cholesky may switch to PCG and back.  Time of a PCG solve is booked as eliminate_ms (backsub_ms 0); its
+ *      launches carry no lmgpu_set_kernel_timing events (no category of lmgpu_kernel_category fits them, and LMGPU_KT_NUM stays as it
+ *      is): their device time is in lmgpu_get_pcg_stats (precond_ms, iterate_ms), per kernel with rocprofv3. */
+enum lmgpu_linear_solver { LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY = 0, LMGPU_SOLVER_PCG = 1 };
+enum lmgpu_preconditioner { LMGPU_PRECOND_DUMMY = 0, LMGPU_PRECOND_BLOCK_JACOBI = 1 };
+/* ConjugateGradientParameters (ConjugateGradientSolver.h:34-50; defaults min 1, max 500, reset 501, eps_rel 1e-3, eps_abs 1e-3) */
+typedef struct lmgpu_pcg_params {
+  int32_t preconditioner, minIterations, maxIterations, reset; /* reset >= 1: every reset-th iteration recomputes r = b - A x */
+  double epsilon_rel, epsilon_abs;
+} lmgpu_pcg_params;
+/* pcg may be NULL for LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY */
+int lmgpu_set_linear_solver(lmgpu_handle* h, int32_t solver, const lmgpu_pcg_params* pcg);
+/* of the last PCG solve: iterations = loop bodies executed; host_waits = host synchronisations of the solve (one per 16 iterations
+ * queued + one at the end); gamma0 = |L^-1 b|^2, gamma = |r|^2 at exit, threshold = max(eps_abs, eps_rel^2 gamma0);
+ * precond_ms = block diagonal + its Cholesky, iterate_ms = the loop (device time, HIP events).  LMGPU_INVALID before the first. */
+typedef struct lmgpu_pcg_stats {
+  int32_t iterations, host_waits;
+  double gamma0, gamma, threshold, precond_ms, iterate_ms;
+} lmgpu_pcg_stats;
+int lmgpu_get_pcg_stats(const lmgpu_handle* h, lmgpu_pcg_stats* out);
+
 /* Per-kernel device time (HIP events on the handle's stream around each launch), accumulated since
  * lmgpu_set_kernel_timing(h, 1).  work[] is the ALGORITHMIC work of the launches in the category:
  * bytes for LINEARIZE (232 B per SFM factor + every camera / point row once) and ALLREDUCE,
@@ -241,7 +274,7 @@ int lmgpu_get_jacobian(lmgpu_handle* h, int32_t graph_index, double* out, int32_
  * NonlinearFactorGraph::linearize), column-major rows[i] x cols[i] at out + offsets[i]; offsets has *n_out + 1 entries.
  * Any output may be NULL (out == NULL: shapes only, no device needed).  One device copy per factor bucket. */
 int lmgpu_get_jacobians(lmgpu_handle* h, int32_t* n_out, int32_t* graph_index, int32_t* rows, int32_t* cols, int64_t* offsets, double* out);
-int lmgpu_num_fronts(const lmgpu_handle* h);
+int lmgpu_num_fronts(const lmgpu_handle* h); /* 0 on a handle finalized under LMGPU_SOLVER_PCG */
 /* info8: n_keys, n_frontal_keys, nf (rows of [R S d]), n (cols), parent front (-1 root), class (0 = LDS front, 1 = HBM front),
  *        owner rank (-1 = replicated on every rank), level (0 = leaf) */
 int lmgpu_front_info(const lmgpu_handle* h, int32_t front, int32_t* info8);

@@ -135,6 +135,10 @@ class Problem {
     check(lmgpu_finalize_structure(h_));
   }
 
+  /// NonlinearOptimizerParams::linearSolverType (gtsam/nonlinear/NonlinearOptimizer.cpp:154-173): LMGPU_SOLVER_PCG with its
+  /// PCGSolverParameters (before finalize(): the handle is built without fronts), or LMGPU_SOLVER_MULTIFRONTAL_CHOLESKY (pcg unused)
+  void set_linear_solver(int32_t solver, const lmgpu_pcg_params* pcg = nullptr) { check(lmgpu_set_linear_solver(h_, solver, pcg)); }
+
   int totalDim() const { return lmgpu_total_dim(h_); }
   int totalStore() const { return lmgpu_total_store(h_); }
   int numFronts() const { return lmgpu_num_fronts(h_); }

@@ -35,6 +35,8 @@
 #include <gtsam/linear/GaussianFactorGraph.h>
 #include <gtsam/linear/JacobianFactor.h>
 #include <gtsam/linear/NoiseModel.h>
+#include <gtsam/linear/PCGSolver.h>
+#include <gtsam/linear/Preconditioner.h>
 #include <gtsam/linear/VectorValues.h>
 #include <gtsam/linear/linearExceptions.h>
 #include <gtsam/nonlinear/DoglegOptimizer.h>
@@ -202,7 +204,10 @@ inline bool extractFactor(const NonlinearFactor::shared_ptr& f, const Values& in
 /// shared by the three optimizers: the device-resident problem + Values / VectorValues marshalling
 class Device {
  public:
-  Device(const NonlinearFactorGraph& graph, const Values& initial, const Ordering& ordering, int device) : p_(device) {
+  /// pcg != nullptr: the linear solver is PCG, selected before finalize (no fronts are built)
+  Device(const NonlinearFactorGraph& graph, const Values& initial, const Ordering& ordering, int device,
+         const lmgpu_pcg_params* pcg = nullptr)
+      : p_(device) {
     std::vector<uint64_t> keys(ordering.begin(), ordering.end());
     std::vector<int32_t> types;
     types.reserve(keys.size());
@@ -219,6 +224,7 @@ class Device {
       std::vector<uint64_t> fk(nm->keys().begin(), nm->keys().end());
       p_.addFactor(type, (int32_t)i, fk.data(), meas.data(), nz.kind, nz.data.empty() ? nullptr : nz.data.data(), nz.robust, nz.robustK);
     }
+    if (pcg) p_.set_linear_solver(LMGPU_SOLVER_PCG, pcg);
     p_.finalize();
     upload(initial);
   }
@@ -323,11 +329,38 @@ inline lmgpu_lm_params toC(const LevenbergMarquardtParams& p) {  // gtsam/nonlin
                          p.minDiagonal, p.maxDiagonal};
 }
 
+/// NonlinearOptimizer::solve's dispatch (gtsam/nonlinear/NonlinearOptimizer.cpp:154-173) as far as it is bound: isIterative() with
+/// PCGSolverParameters and a Dummy or BlockJacobi preconditioner -> lmgpu_pcg_params (returns true); every other iterative parameter type
+/// (SubgraphSolverParameters, another preconditioner, none) throws std::invalid_argument -- no silent fallback to Cholesky.
+inline bool toPcg(const NonlinearOptimizerParams& p, lmgpu_pcg_params* out) {
+  if (!p.isIterative()) return false;
+  auto pcg = std::dynamic_pointer_cast<PCGSolverParameters>(p.iterativeParams);
+  if (!pcg) throw std::invalid_argument("lmgpu adapter: the iterative linear solver is bound for PCGSolverParameters only");
+  int32_t pre;
+  if (std::dynamic_pointer_cast<DummyPreconditionerParameters>(pcg->preconditioner))
+    pre = LMGPU_PRECOND_DUMMY;
+  else if (std::dynamic_pointer_cast<BlockJacobiPreconditionerParameters>(pcg->preconditioner))
+    pre = LMGPU_PRECOND_BLOCK_JACOBI;
+  else
+    throw std::invalid_argument("lmgpu adapter: PCG is bound with the Dummy or BlockJacobi preconditioner only");
+  const size_t lim = (size_t)1 << 28;
+  if (pcg->minIterations > lim || pcg->maxIterations > lim || pcg->reset > lim || pcg->reset == 0)
+    throw std::invalid_argument("lmgpu adapter: PCG iteration counts out of range (reset >= 1, counts <= 2^28)");
+  *out = lmgpu_pcg_params{pre, (int32_t)pcg->minIterations, (int32_t)pcg->maxIterations, (int32_t)pcg->reset, pcg->epsilon_rel,
+                          pcg->epsilon_abs};
+  return true;
+}
+
+/// the lmgpu_pcg_params of `p` as a Device argument (nullptr: the direct solver); `buf` holds them
+inline const lmgpu_pcg_params* pcgOf(const NonlinearOptimizerParams& p, lmgpu_pcg_params* buf) { return toPcg(p, buf) ? buf : nullptr; }
+
 }  // namespace lmgpu_detail
 
 /// drop-in for LevenbergMarquardtOptimizer: same constructor arguments, same optimize() / iterate() / lambda() / values().
 /// Unsupported factors, constrained noise, Scalar-scheme or custom m-estimators make the constructor throw
 /// std::invalid_argument, so that a caller keeps the stock optimizer explicitly — there is no silent fallback.
+/// linearSolverType = Iterative with PCGSolverParameters (Dummy / BlockJacobi preconditioner) runs the device PCG solver; any other
+/// iterative parameter type throws std::invalid_argument here as well.
 class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
  public:
   enum Mode { WholeIterate, Piecewise };
@@ -335,7 +368,7 @@ class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
   GpuLevenbergMarquardtOptimizer(const NonlinearFactorGraph& graph, const Values& initial,
                                  const LevenbergMarquardtParams& params = LevenbergMarquardtParams(), int device = 0, Mode mode = WholeIterate)
       : LevenbergMarquardtOptimizer(graph, initial, params),  // fixes params_.ordering (LevenbergMarquardtParams.h:112-117), initial error
-        dev_(graph, initial, *params_.ordering, device), cp_(lmgpu_detail::toC(params_)), mode_(mode) {}
+        dev_(graph, initial, *params_.ordering, device, lmgpu_detail::pcgOf(params_, &pcg_)), cp_(lmgpu_detail::toC(params_)), mode_(mode) {}
 
   /// LevenbergMarquardtOptimizer::iterate() (LevenbergMarquardtOptimizer.cpp:273-308)
   GaussianFactorGraph::shared_ptr iterate() override {
@@ -387,6 +420,7 @@ class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
   GaussianFactorGraph::shared_ptr lastLinearGraph() const { return dev_.downloadLinearGraph(graph_); }
 
  private:
+  lmgpu_pcg_params pcg_{};  // (declared before dev_: the constructor fills it while building dev_)
   mutable lmgpu_detail::Device dev_;
   lmgpu_lm_params cp_;
   Mode mode_;
@@ -398,7 +432,7 @@ class GpuGaussNewtonOptimizer : public GaussNewtonOptimizer {
  public:
   GpuGaussNewtonOptimizer(const NonlinearFactorGraph& graph, const Values& initial, const GaussNewtonParams& params = GaussNewtonParams(),
                           int device = 0)
-      : GaussNewtonOptimizer(graph, initial, params), dev_(graph, initial, *params_.ordering, device) {}
+      : GaussNewtonOptimizer(graph, initial, params), dev_(graph, initial, *params_.ordering, device, lmgpu_detail::pcgOf(params_, &pcg_)) {}
 
   GaussianFactorGraph::shared_ptr iterate() override {
     lmgpu_lm_state st{state_->error, 0.0, 0.0, (int32_t)state_->iterations, 0};
@@ -428,6 +462,7 @@ class GpuGaussNewtonOptimizer : public GaussNewtonOptimizer {
   }
 
  private:
+  lmgpu_pcg_params pcg_{};  // (declared before dev_: the constructor fills it while building dev_)
   mutable lmgpu_detail::Device dev_;
   bool discardLinear_ = false;
 };
@@ -444,6 +479,8 @@ class GpuDoglegOptimizer : public NonlinearOptimizer {
   GpuDoglegOptimizer(const NonlinearFactorGraph& graph, const Values& initial, const DoglegParams& params = DoglegParams(), int device = 0)
       : NonlinearOptimizer(graph, std::unique_ptr<internal::NonlinearOptimizerState>(new State(initial, graph.error(initial), params.deltaInitial))),
         params_(params) {
+    if (params_.isIterative())  // DoglegOptimizer.cpp:108-110 throws in iterate(); refused before anything is built here
+      throw std::invalid_argument("Dogleg is not currently compatible with the linear conjugate gradient solver");
     if (!params_.ordering) params_.ordering = Ordering::Create(params_.orderingType, graph);  // DoglegOptimizer.cpp:127-131
     dev_.reset(new lmgpu_detail::Device(graph, initial, *params_.ordering, device));
   }
