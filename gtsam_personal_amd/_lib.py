@@ -75,6 +75,21 @@ class lmgpu_pcg_stats(ct.Structure):
                 ("threshold", ct.c_double), ("precond_ms", ct.c_double), ("iterate_ms", ct.c_double)]
 
 
+LMGPU_GNC_GM, LMGPU_GNC_TLS = 0, 1
+LMGPU_GNC_BASE_LM, LMGPU_GNC_BASE_GN = 0, 1
+GNC_STOP_REASONS = ("maxIterations", "cost", "weights", "mu", "mu <= 0 at initialisation", "nothing unknown")
+
+
+class lmgpu_gnc_params(ct.Structure):
+    _fields_ = [("lossType", ct.c_int32), ("maxIterations", ct.c_int32), ("baseOptimizer", ct.c_int32), ("muStep", ct.c_double),
+                ("relativeCostTol", ct.c_double), ("weightsTol", ct.c_double)]
+
+
+class lmgpu_gnc_result(ct.Structure):
+    _fields_ = [("iterations", ct.c_int32), ("stop", ct.c_int32), ("mu", ct.c_double), ("cost", ct.c_double), ("prev_cost", ct.c_double),
+                ("base_iterations_total", ct.c_int32)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -109,6 +124,18 @@ SYMBOLS = {
     "lmgpu_get_timings": (ct.c_int, [_H, ct.POINTER(lmgpu_timings)]),
     "lmgpu_set_linear_solver": (ct.c_int, [_H, ct.c_int32, ct.POINTER(lmgpu_pcg_params)]),
     "lmgpu_get_pcg_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_pcg_stats)]),
+    "lmgpu_chi2inv": (ct.c_double, [ct.c_double, ct.c_int32]),
+    "lmgpu_gnc_enable": (ct.c_int, [_H, ct.c_int32, ct.c_int32]),
+    "lmgpu_gnc_set_inlier_cost_thresholds": (ct.c_int, [_H, ct.c_int32, _D, ct.c_double]),
+    "lmgpu_gnc_set_known": (ct.c_int, [_H, ct.c_int32, ct.POINTER(ct.c_uint64), ct.c_int32, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_gnc_set_weights": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_gnc_get_weights": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_gnc_get_inlier_cost_thresholds": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_gnc_initialize_mu": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_gnc_calculate_weights": (ct.c_int, [_H, ct.c_int32, ct.c_double]),
+    "lmgpu_gnc_optimize": (ct.c_int, [_H, ct.POINTER(lmgpu_gnc_params), ct.POINTER(lmgpu_lm_params), ct.POINTER(lmgpu_lm_state),
+                                      ct.POINTER(lmgpu_gnc_result)]),
+    "lmgpu_gnc_get_trace": (ct.c_int, [_H, ct.c_int32, _D]),
     "lmgpu_set_kernel_timing": (ct.c_int, [_H, ct.c_int32]),
     "lmgpu_get_kernel_times": (ct.c_int, [_H, _D, _D, ct.POINTER(ct.c_int64)]),
     "lmgpu_get_jacobian": (ct.c_int, [_H, ct.c_int32, _D, _I, _I]),

@@ -30,6 +30,9 @@ struct BucketDev {
   double rk;              // its tuning constant
   const int32_t* sel;     // null: all n factors of the bucket; else n indices into the bucket (ISAM2 relinearizes a subset,
                           // gtsam/nonlinear/ISAM2.cpp:66-114)
+  const double* gw = nullptr;  // GNC weight of each factor, addressed like the error buffer (gw[epos[f]]); null: no weighting.
+                               // GncOptimizer::makeWeightedGraph (gtsam/nonlinear/GncOptimizer.h:396-416): Information(w * information),
+                               // i.e. [A b] *= sqrt(w) after the whitening and error = w * 0.5 ||whitened e||^2
 };
 
 struct ValuesDev {
@@ -115,6 +118,14 @@ __device__ __forceinline__ void robust_reweight(double* Jl, int kind, double k) 
   const double w = sqrt(robust_weight(kind, k, sqrt(s)));
 #pragma unroll
   for (int i = 0; i < M * COLS; i++) Jl[i] *= w;
+}
+
+// GNC: [A b] *= sqrt(w) after the Gaussian whitening (the square-root side of Gaussian::Information(w * information))
+template <int N>
+__device__ __forceinline__ void gnc_reweight(double* Jl, double w) {
+  const double sw = sqrt(w);
+#pragma unroll
+  for (int i = 0; i < N; i++) Jl[i] *= sw;
 }
 
 // NoiseModelFactor::error: loss(squaredMahalanobisDistance) = 0.5 d^2 (Gaussian) or rho(d) (Robust, NoiseModel.h:717-725)
@@ -209,6 +220,7 @@ __global__ __launch_bounds__(256) void sfm_linearize_kernel(BucketDev b, ValuesD
     }
     if (b.noise_kind != 0) whiten_block<2, 13>(Jl, b.noise_kind, b.noise + (size_t)f * (b.noise_kind == 2 ? 2 : 4));
     if (b.robust) robust_reweight<2, 13>(Jl, b.robust, b.rk);
+    if (b.gw) gnc_reweight<26>(Jl, b.gw[b.epos[f]]);
   } else {
 #pragma unroll
     for (int i = 0; i < 26; i++) Jl[i] = 0.0;
@@ -260,6 +272,7 @@ __global__ __launch_bounds__(256) void sfm_linearize_sel_kernel(BucketDev b, Val
   }
   if (b.noise_kind != 0) whiten_block<2, 13>(Jl, b.noise_kind, b.noise + (size_t)f * (b.noise_kind == 2 ? 2 : 4));
   if (b.robust) robust_reweight<2, 13>(Jl, b.robust, b.rk);
+  if (b.gw) gnc_reweight<26>(Jl, b.gw[b.epos[f]]);
   double* out = b.J + (size_t)f * 26;
 #pragma unroll
   for (int i = 0; i < 26; i++) out[i] = Jl[i];
@@ -283,7 +296,9 @@ __global__ __launch_bounds__(256) void sfm_error_kernel(BucketDev b, ValuesDev v
   } else {
     e[0] = e[1] = 0.0;
   }
-  ebuf[b.epos[f]] = whitened_half_sq<2>(e, b.noise_kind, b.noise ? b.noise + (size_t)f * (b.noise_kind == 2 ? 2 : 4) : nullptr, b.robust, b.rk);
+  const double err = whitened_half_sq<2>(e, b.noise_kind, b.noise ? b.noise + (size_t)f * (b.noise_kind == 2 ? 2 : 4) : nullptr, b.robust, b.rk);
+  const int ep = b.epos[f];
+  ebuf[ep] = b.gw ? b.gw[ep] * err : err;
 }
 
 // ---------------------------------------------------------------- generic per-type evaluation
@@ -521,11 +536,14 @@ __global__ __launch_bounds__(128) void sfm2_factor_kernel(BucketDev b, ValuesDev
     }
     whiten_block<M, COLS>(Jl, b.noise_kind, nz);
     if (b.robust) robust_reweight<M, COLS>(Jl, b.robust, b.rk);
+    if (b.gw) gnc_reweight<M * COLS>(Jl, b.gw[b.epos[f]]);
     double* out = b.J + (size_t)f * (M * COLS);
 #pragma unroll
     for (int i = 0; i < M * COLS; i++) out[i] = Jl[i];
   } else {
-    ebuf[b.epos[f]] = whitened_half_sq<M>(e, b.noise_kind, nz, b.robust, b.rk);
+    const double err = whitened_half_sq<M>(e, b.noise_kind, nz, b.robust, b.rk);
+    const int ep = b.epos[f];
+    ebuf[ep] = b.gw ? b.gw[ep] * err : err;
   }
 }
 
@@ -605,11 +623,14 @@ __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const Va
     }
     whiten_block<M, COLS>(Jl, b.noise_kind, nz);
     if (b.robust) robust_reweight<M, COLS>(Jl, b.robust, b.rk);
+    if (b.gw) gnc_reweight<M * COLS>(Jl, b.gw[b.epos[f]]);
     double* out = b.J + (size_t)f * (M * COLS);
 #pragma unroll
     for (int i = 0; i < M * COLS; i++) out[i] = Jl[i];
   } else {
-    ebuf[b.epos[f]] = whitened_half_sq<M>(e, b.noise_kind, nz, b.robust, b.rk);
+    const double err = whitened_half_sq<M>(e, b.noise_kind, nz, b.robust, b.rk);
+    const int ep = b.epos[f];
+    ebuf[ep] = b.gw ? b.gw[ep] * err : err;
   }
 }
 

@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +37,7 @@
 #include "kernels_bayes.hpp"
 #include "kernels_schur.hpp"
 #include "kernels_pcg.hpp"
+#include "kernels_gnc.hpp"
 #include "plan.hpp"
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
@@ -387,6 +389,19 @@ struct lmgpu_handle {
   int32_t* h_pcg_done = nullptr; // pinned
   hipEvent_t pcg_ev[3] = {nullptr, nullptr, nullptr};
   lmgpu_pcg_stats pcg_stats{};
+
+  // ---- GNC (kernels_gnc.hpp; lmgpu_gnc_*).  Device vectors in local factor order (= the error buffer's), nfac entries each.
+  bool gnc_on = false;
+  bool gnc_raw = false;          // the next error launches evaluate the UNWEIGHTED graph (r_k for the weight update)
+  int gnc_n = 0;                 // nfg_.size(): length of every vector that crosses the boundary
+  int gnc_n_in = 0, gnc_n_out = 0;
+  double *gnc_w = nullptr, *gnc_b = nullptr, *gnc_part = nullptr, *gnc_scal = nullptr;
+  unsigned char* gnc_fixed = nullptr;
+  double* h_gnc_scal = nullptr;  // pinned: [0] max |w - round(w)|, [1] mu
+  std::vector<int32_t> gnc_pos;  // graph index -> local factor (-1: the slot holds no factor)
+  std::vector<unsigned char> gnc_fixed_h;
+  std::vector<double> gnc_trace; // per outer iteration: mu, cost, max |w - round(w)|, weight-update ms, base optimizer ms, base iterations
+  hipEvent_t gnc_ev[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -430,8 +445,9 @@ BucketDev bucket_dev(lmgpu_handle* h, const Bucket& b) {
   d.type = b.type;
   d.n = b.n_loc;
   d.noise_kind = b.noise_kind;
-  d.robust = b.robust;
+  d.robust = h->gnc_on ? 0 : b.robust;  // GncOptimizer's constructor strips noiseModel::Robust (GncOptimizer.h:63-73)
   d.rk = b.robust_k;
+  d.gw = (h->gnc_on && !h->gnc_raw) ? h->gnc_w : nullptr;
   d.vidx = b.d_vidx;
   d.meas = b.d_meas;
   d.noise = b.d_noise;
@@ -2014,6 +2030,10 @@ int lmgpu_destroy(lmgpu_handle* h) {
     if (h->h_pcg_done) (void)hipHostFree(h->h_pcg_done);
     for (int i = 0; i < 3; i++)
       if (h->pcg_ev[i]) (void)hipEventDestroy(h->pcg_ev[i]);
+    fr(h->gnc_w); fr(h->gnc_b); fr(h->gnc_part); fr(h->gnc_scal); fr(h->gnc_fixed);
+    if (h->h_gnc_scal) (void)hipHostFree(h->h_gnc_scal);
+    for (int i = 0; i < 2; i++)
+      if (h->gnc_ev[i]) (void)hipEventDestroy(h->gnc_ev[i]);
     for (Bucket& b : h->buckets) {
       fr(b.d_vidx); fr(b.d_meas); fr(b.d_noise); fr(b.d_epos);
     }
@@ -3308,6 +3328,434 @@ int lmgpu_get_pcg_stats(const lmgpu_handle* h, lmgpu_pcg_stats* out) {
   if (!h || !out || !h->pcg_have_stats) return LMGPU_INVALID;
   *out = h->pcg_stats;
   return LMGPU_OK;
+}
+
+// ---------------------------------------------------------------- GNC (gtsam/nonlinear/GncOptimizer.h, GncParams.h)
+namespace {
+
+// regularised lower incomplete gamma P(a, x): series for x < a + 1, Lentz continued fraction of Q otherwise
+double gamma_p(double a, double x) {
+  if (x <= 0.0) return 0.0;
+  const double lg = std::lgamma(a);
+  if (x < a + 1.0) {
+    double ap = a, sum = 1.0 / a, del = sum;
+    for (int n = 0; n < 10000; n++) {
+      ap += 1.0;
+      del *= x / ap;
+      sum += del;
+      if (std::fabs(del) < std::fabs(sum) * 1e-17) break;
+    }
+    return sum * std::exp(-x + a * std::log(x) - lg);
+  }
+  const double tiny = 1e-300;
+  double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, hh = d;
+  for (int i = 1; i < 10000; i++) {
+    const double an = -i * (i - a);
+    b += 2.0;
+    d = an * d + b;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = b + an / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    hh *= del;
+    if (std::fabs(del - 1.0) < 1e-16) break;
+  }
+  return 1.0 - std::exp(-x + a * std::log(x) - lg) * hh;
+}
+
+int gnc_need(lmgpu_handle* h, const char* who) {
+  if (!h->gnc_on) {
+    h->err = std::string(who) + ": GNC is not enabled on this handle (lmgpu_gnc_enable)";
+    return LMGPU_INVALID;
+  }
+  return need_device(h);
+}
+
+// a boundary vector (graph-index order, gnc_n entries) -> local factor order; slots without a factor are dropped
+void gnc_to_local(const lmgpu_handle* h, const double* v, std::vector<double>& loc) {
+  loc.assign((size_t)std::max(1, h->nfac), 1.0);
+  for (int g = 0; g < h->gnc_n; g++)
+    if (h->gnc_pos[g] >= 0) loc[h->gnc_pos[g]] = v[g];
+}
+
+int gnc_upload(lmgpu_handle* h, double* dst, const std::vector<double>& loc) {
+  HIPCHECK(hipMemcpyAsync(dst, loc.data(), (size_t)h->nfac * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return LMGPU_OK;
+}
+
+int gnc_download(lmgpu_handle* h, const double* src, double* out) {
+  std::vector<double> loc((size_t)std::max(1, h->nfac));
+  HIPCHECK(hipMemcpyAsync(loc.data(), src, (size_t)h->nfac * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  for (int g = 0; g < h->gnc_n; g++) out[g] = h->gnc_pos[g] >= 0 ? loc[h->gnc_pos[g]] : 1.0;
+  return LMGPU_OK;
+}
+
+// initializeWeightsFromKnownInliersAndOutliers (GncOptimizer.h:174-180): ones, known outliers 0
+int gnc_reset_weights(lmgpu_handle* h) {
+  std::vector<double> w((size_t)std::max(1, h->nfac), 1.0);
+  for (int i = 0; i < h->nfac; i++)
+    if (h->gnc_fixed_h[i] == 2) w[i] = 0.0;
+  return gnc_upload(h, h->gnc_w, w);
+}
+
+int gnc_default_thresholds(lmgpu_handle* h, double alpha) {
+  std::vector<double> b((size_t)std::max(1, h->nfac), 1.0);
+  std::map<int, double> by_rows;  // rows of a factor -> its threshold (one quantile evaluation per distinct row count)
+  for (size_t i = 0; i < h->plan.factors.size(); i++) {
+    const int l = h->fac_local[i];
+    if (l < 0) continue;
+    const int rows = h->buckets[h->plan.factors[i].bucket].rows;
+    auto it = by_rows.find(rows);
+    if (it == by_rows.end()) it = by_rows.emplace(rows, 0.5 * lmgpu_chi2inv(alpha, rows)).first;  // :134
+    b[l] = it->second;
+  }
+  return gnc_upload(h, h->gnc_b, b);
+}
+
+// r_k of every factor at values[which] into ebuf0: the error kernels on the unweighted graph (gw = nullptr, robust ignored)
+void gnc_raw_errors(lmgpu_handle* h, int which) {
+  h->gnc_raw = true;
+  launch_factors<false>(h, which);
+  h->gnc_raw = false;
+}
+
+// calculateWeights at values[cur] (queued): weights into gnc_w, max |w - round(w)| into h_gnc_scal[0]
+int gnc_enqueue_weights(lmgpu_handle* h, int loss, double mu) {
+  gnc_raw_errors(h, h->cur);
+  const int g = std::min(GNC_MAX_BLOCKS, std::max(1, (h->nfac + 255) / 256));
+  hipLaunchKernelGGL(gnc_weights_kernel, dim3(g), dim3(256), 0, h->stream, h->nfac, (const double*)h->ebuf0, (const double*)h->gnc_b,
+                     (const unsigned char*)h->gnc_fixed, mu, loss, h->gnc_w, h->gnc_part);
+  hipLaunchKernelGGL(gnc_finish_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)h->gnc_part, g, 0, h->gnc_scal);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(h->h_gnc_scal, h->gnc_scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  h->linearized = h->have_jacobians = false;  // the stored [A b] carry the previous weights: no solve and no parity tap reads them
+  return LMGPU_OK;
+}
+
+// initializeMu at values[cur] (waits for the scalar)
+int gnc_init_mu(lmgpu_handle* h, int loss, double* mu) {
+  gnc_raw_errors(h, h->cur);
+  const int g = std::min(GNC_MAX_BLOCKS, std::max(1, (h->nfac + 255) / 256));
+  hipLaunchKernelGGL(gnc_mu_init_kernel, dim3(g), dim3(256), 0, h->stream, h->nfac, (const double*)h->ebuf0, (const double*)h->gnc_b, loss,
+                     h->gnc_part);
+  hipLaunchKernelGGL(gnc_finish_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)h->gnc_part, g, loss == LMGPU_GNC_GM ? 0 : 1,
+                     h->gnc_scal + 1);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(h->h_gnc_scal + 1, h->gnc_scal + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  *mu = h->h_gnc_scal[1];
+  return LMGPU_OK;
+}
+
+// BaseOptimizer(graph, values, params).optimize() on the weighted graph at values[cur]: a fresh state, then the optimizer's own loop
+int gnc_base_optimize(lmgpu_handle* h, int base, const lmgpu_lm_params* bp) {
+  int rc = lmgpu_lm_init(h, bp, nullptr);
+  if (rc) return rc;
+  return base == LMGPU_GNC_BASE_GN ? lmgpu_gn_optimize(h, bp, nullptr) : lmgpu_optimize(h, bp, nullptr);
+}
+
+}  // namespace
+
+double lmgpu_chi2inv(double alpha, int32_t dofs) {
+  if (!(alpha >= 0.0) || !(alpha < 1.0) || dofs < 1) return std::numeric_limits<double>::quiet_NaN();
+  if (alpha == 0.0) return 0.0;
+  const double a = 0.5 * dofs;
+  // bracket, then Newton on P(a, x / 2) = alpha inside it (bisection whenever a step leaves the bracket)
+  double lo = 0.0, hi = std::max(1.0, (double)dofs);
+  while (gamma_p(a, 0.5 * hi) < alpha) hi *= 2.0;
+  double x = 0.5 * (lo + hi);
+  for (int it = 0; it < 200; it++) {
+    const double f = gamma_p(a, 0.5 * x) - alpha;
+    if (f > 0) hi = x; else lo = x;
+    const double pdf = 0.5 * std::exp(-0.5 * x + (a - 1.0) * std::log(0.5 * x) - std::lgamma(a));
+    double xn = pdf > 0 ? x - f / pdf : 0.5 * (lo + hi);
+    if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+    if (std::fabs(xn - x) <= 1e-15 * std::fabs(x)) {
+      x = xn;
+      break;
+    }
+    x = xn;
+  }
+  return x;
+}
+
+int lmgpu_gnc_enable(lmgpu_handle* h, int32_t on, int32_t graph_size) {
+  if (!h) return LMGPU_INVALID;
+  if (!h->finalized) {
+    h->err = "lmgpu_gnc_enable: refused (!h->finalized)";
+    return LMGPU_INVALID;
+  }
+  if (on && (h->cfg.world_size > 1 || (h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT))) {
+    h->err = "lmgpu_gnc_enable: GNC is single-rank (world_size > 1)";
+    return LMGPU_INVALID;
+  }
+  int rc = need_device(h);
+  if (rc) return rc;
+  auto drop = [&]() {
+    if (h->gnc_w) (void)hipFree(h->gnc_w);
+    if (h->gnc_b) (void)hipFree(h->gnc_b);
+    if (h->gnc_part) (void)hipFree(h->gnc_part);
+    if (h->gnc_scal) (void)hipFree(h->gnc_scal);
+    if (h->gnc_fixed) (void)hipFree(h->gnc_fixed);
+    h->gnc_w = h->gnc_b = h->gnc_part = h->gnc_scal = nullptr;
+    h->gnc_fixed = nullptr;
+  };
+  if (!on) {
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    drop();
+    if (h->gnc_on) h->linearized = h->have_jacobians = false;
+    h->gnc_on = false;
+    return LMGPU_OK;
+  }
+  const int max_gi = h->graph_index_sorted.empty() ? -1 : h->graph_index_sorted.back();
+  if (h->plan.factors.size() && h->graph_index_sorted.front() < 0) {
+    h->err = "lmgpu_gnc_enable: negative graph_index";
+    return LMGPU_INVALID;
+  }
+  if (graph_size <= 0) graph_size = max_gi + 1;
+  if (graph_size <= max_gi) {
+    h->err = "lmgpu_gnc_enable: graph_size is smaller than the largest graph_index + 1";
+    return LMGPU_INVALID;
+  }
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  drop();
+  h->gnc_n = graph_size;
+  h->gnc_n_in = h->gnc_n_out = 0;
+  h->gnc_pos.assign((size_t)graph_size, -1);
+  for (size_t i = 0; i < h->plan.factors.size(); i++) h->gnc_pos[h->graph_index_sorted[i]] = h->fac_local[i];
+  h->gnc_fixed_h.assign((size_t)std::max(1, h->nfac), 0);
+  const size_t n1 = (size_t)std::max(1, h->nfac);
+  HIPCHECK(hipMalloc((void**)&h->gnc_w, n1 * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->gnc_b, n1 * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->gnc_part, GNC_MAX_BLOCKS * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->gnc_scal, 2 * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->gnc_fixed, n1));
+  HIPCHECK(hipMemset(h->gnc_fixed, 0, n1));
+  if (!h->h_gnc_scal) HIPCHECK(hipHostMalloc((void**)&h->h_gnc_scal, 2 * sizeof(double)));
+  for (int i = 0; i < 2; i++)
+    if (!h->gnc_ev[i]) HIPCHECK(hipEventCreate(&h->gnc_ev[i]));
+  if ((rc = gnc_reset_weights(h))) return rc;
+  if ((rc = gnc_default_thresholds(h, 0.99))) return rc;  // GncOptimizer.h:104-106
+  h->gnc_on = true;
+  h->linearized = h->have_jacobians = false;
+  return LMGPU_OK;
+}
+
+int lmgpu_gnc_set_inlier_cost_thresholds(lmgpu_handle* h, int32_t n, const double* barcSq, double alpha) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_set_inlier_cost_thresholds");
+  if (rc) return rc;
+  if (!barcSq) {
+    if (!(alpha > 0.0 && alpha < 1.0)) {
+      h->err = "lmgpu_gnc_set_inlier_cost_thresholds: alpha must lie in (0, 1)";
+      return LMGPU_INVALID;
+    }
+    return gnc_default_thresholds(h, alpha);
+  }
+  if (n != h->gnc_n) {
+    h->err = "lmgpu_gnc_set_inlier_cost_thresholds: the number of thresholds does not match the size of the factor graph";
+    return LMGPU_INVALID;
+  }
+  std::vector<double> loc;
+  gnc_to_local(h, barcSq, loc);
+  return gnc_upload(h, h->gnc_b, loc);
+}
+
+int lmgpu_gnc_set_known(lmgpu_handle* h, int32_t n_in, const uint64_t* inliers, int32_t n_out, const uint64_t* outliers) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_set_known");
+  if (rc) return rc;
+  if (n_in < 0 || n_out < 0 || (n_in && !inliers) || (n_out && !outliers)) {
+    h->err = "lmgpu_gnc_set_known: refused (negative count or NULL list)";
+    return LMGPU_INVALID;
+  }
+  std::vector<unsigned char> slot((size_t)h->gnc_n, 0);
+  for (int i = 0; i < n_in; i++) {
+    if (inliers[i] >= (uint64_t)h->gnc_n) {
+      h->err = "lmgpu_gnc_set_known: one or more measurements that are not in the factor graph selected to be known inliers";
+      return LMGPU_INVALID;
+    }
+    slot[inliers[i]] = 1;
+  }
+  for (int i = 0; i < n_out; i++) {
+    if (outliers[i] >= (uint64_t)h->gnc_n) {
+      h->err = "lmgpu_gnc_set_known: one or more measurements that are not in the factor graph selected to be known outliers";
+      return LMGPU_INVALID;
+    }
+    if (slot[outliers[i]] == 1) {
+      h->err = "lmgpu_gnc_set_known: one or more measurements selected to be BOTH a known inlier and a known outlier";
+      return LMGPU_INVALID;
+    }
+    slot[outliers[i]] = 2;
+  }
+  std::fill(h->gnc_fixed_h.begin(), h->gnc_fixed_h.end(), 0);
+  for (int g = 0; g < h->gnc_n; g++)
+    if (h->gnc_pos[g] >= 0) h->gnc_fixed_h[h->gnc_pos[g]] = slot[g];
+  h->gnc_n_in = n_in;
+  h->gnc_n_out = n_out;
+  HIPCHECK(hipMemcpyAsync(h->gnc_fixed, h->gnc_fixed_h.data(), (size_t)std::max(1, h->nfac), hipMemcpyHostToDevice, h->stream));
+  h->linearized = h->have_jacobians = false;
+  return gnc_reset_weights(h);
+}
+
+int lmgpu_gnc_set_weights(lmgpu_handle* h, int32_t n, const double* w) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_set_weights");
+  if (rc) return rc;
+  if (!w || n != h->gnc_n) {
+    h->err = "lmgpu_gnc_set_weights: the number of specified weights does not match the size of the factor graph";
+    return LMGPU_INVALID;
+  }
+  h->linearized = h->have_jacobians = false;
+  std::vector<double> loc;
+  gnc_to_local(h, w, loc);
+  return gnc_upload(h, h->gnc_w, loc);
+}
+
+int lmgpu_gnc_get_weights(lmgpu_handle* h, int32_t n, double* w) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_get_weights");
+  if (rc) return rc;
+  if (!w || n != h->gnc_n) {
+    h->err = "lmgpu_gnc_get_weights: the length does not match the size of the factor graph";
+    return LMGPU_INVALID;
+  }
+  return gnc_download(h, h->gnc_w, w);
+}
+
+int lmgpu_gnc_get_inlier_cost_thresholds(lmgpu_handle* h, int32_t n, double* barcSq) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_get_inlier_cost_thresholds");
+  if (rc) return rc;
+  if (!barcSq || n != h->gnc_n) {
+    h->err = "lmgpu_gnc_get_inlier_cost_thresholds: the length does not match the size of the factor graph";
+    return LMGPU_INVALID;
+  }
+  return gnc_download(h, h->gnc_b, barcSq);
+}
+
+static int gnc_check_loss(lmgpu_handle* h, int32_t lossType, const char* who) {
+  if (lossType != LMGPU_GNC_GM && lossType != LMGPU_GNC_TLS) {
+    h->err = std::string(who) + ": called with unknown loss type";
+    return LMGPU_INVALID;
+  }
+  if (!h->have_values) {
+    h->err = std::string(who) + ": refused (!h->have_values)";
+    return LMGPU_INVALID;
+  }
+  return LMGPU_OK;
+}
+
+int lmgpu_gnc_initialize_mu(lmgpu_handle* h, int32_t lossType, double* mu) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_initialize_mu");
+  if (rc) return rc;
+  if (!mu) {
+    h->err = "lmgpu_gnc_initialize_mu: refused (!mu)";
+    return LMGPU_INVALID;
+  }
+  if ((rc = gnc_check_loss(h, lossType, "lmgpu_gnc_initialize_mu"))) return rc;
+  return gnc_init_mu(h, lossType, mu);
+}
+
+int lmgpu_gnc_calculate_weights(lmgpu_handle* h, int32_t lossType, double mu) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_calculate_weights");
+  if (rc) return rc;
+  if ((rc = gnc_check_loss(h, lossType, "lmgpu_gnc_calculate_weights"))) return rc;
+  if ((rc = gnc_enqueue_weights(h, lossType, mu))) return rc;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return LMGPU_OK;
+}
+
+int lmgpu_gnc_optimize(lmgpu_handle* h, const lmgpu_gnc_params* gp, const lmgpu_lm_params* bp, lmgpu_lm_state* base_state_out,
+                       lmgpu_gnc_result* out) {
+  if (!h) return LMGPU_INVALID;
+  int rc = gnc_need(h, "lmgpu_gnc_optimize");
+  if (rc) return rc;
+  if (!gp || !bp || !out) {
+    h->err = "lmgpu_gnc_optimize: refused (!params || !base || !out)";
+    return LMGPU_INVALID;
+  }
+  if (gp->baseOptimizer != LMGPU_GNC_BASE_LM && gp->baseOptimizer != LMGPU_GNC_BASE_GN) {
+    h->err = "lmgpu_gnc_optimize: the base optimizer must be Levenberg-Marquardt or Gauss-Newton (Dogleg is not bound)";
+    return LMGPU_INVALID;
+  }
+  if (gp->maxIterations < 0 || !(gp->muStep > 0.0)) {
+    h->err = "lmgpu_gnc_optimize: refused (maxIterations < 0 || !(muStep > 0))";
+    return LMGPU_INVALID;
+  }
+  if ((rc = gnc_check_loss(h, gp->lossType, "lmgpu_gnc_optimize"))) return rc;
+  const int loss = gp->lossType;
+  std::memset(out, 0, sizeof(*out));
+  h->gnc_trace.clear();
+  // state_ = the values at the call: every base optimizer starts from them (GncOptimizer.h:184-187, 236-238)
+  if ((rc = lmgpu_save_values(h))) return rc;
+  double mu = 0.0;
+  if ((rc = gnc_init_mu(h, loss, &mu))) return rc;  // :188 -- a function of state_ and barcSq only, so evaluated while the values are state_
+  rc = gnc_base_optimize(h, gp->baseOptimizer, bp);  // :184-187
+  if (base_state_out) *base_state_out = h->lm;
+  out->base_iterations_total = h->lm.iterations;
+  if (rc) return rc;
+  double prev_cost = h->lm.error, cost = 0.0;  // :189 graph_initial.error(result) = the base optimizer's own final error
+  out->mu = mu;
+  out->prev_cost = prev_cost;
+  const int nrUnknownInOrOut = h->gnc_n - (h->gnc_n_in + h->gnc_n_out);  // :196
+  if (mu <= 0 || nrUnknownInOrOut == 0) {                                 // :198-215
+    out->stop = mu <= 0 ? 4 : 5;
+    return LMGPU_OK;
+  }
+  int iter = 0, stop = 0;
+  for (iter = 0; iter < gp->maxIterations; iter++) {
+    (void)hipEventRecord(h->gnc_ev[0], h->stream);
+    if ((rc = gnc_enqueue_weights(h, loss, mu))) return rc;  // :232
+    (void)hipEventRecord(h->gnc_ev[1], h->stream);
+    if ((rc = lmgpu_restore_values(h))) return rc;  // :236-238
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = gnc_base_optimize(h, gp->baseOptimizer, bp);
+    const double base_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (base_state_out) *base_state_out = h->lm;
+    out->base_iterations_total += h->lm.iterations;
+    if (rc) return rc;
+    cost = h->lm.error;  // :241
+    const double wdev = h->h_gnc_scal[0];  // its copy was queued before the base optimizer's first wait
+    float wms = 0.0f;
+    (void)hipEventElapsedTime(&wms, h->gnc_ev[0], h->gnc_ev[1]);
+    const double tr[6] = {mu, cost, wdev, (double)wms, base_ms, (double)h->lm.iterations};
+    h->gnc_trace.insert(h->gnc_trace.end(), tr, tr + 6);
+    // checkConvergence :389-393 = cost :351-359 || weights :362-386 || mu :332-348
+    if (std::fabs(cost - prev_cost) / std::max(prev_cost, 1e-7) < gp->relativeCostTol) {
+      stop = 1;
+      break;
+    }
+    if (loss == LMGPU_GNC_TLS && !(wdev > gp->weightsTol)) {
+      stop = 2;
+      break;
+    }
+    if (loss == LMGPU_GNC_GM && std::fabs(mu - 1.0) < 1e-9) {
+      stop = 3;
+      break;
+    }
+    mu = loss == LMGPU_GNC_GM ? std::max(1.0, mu / gp->muStep) : mu * gp->muStep;  // updateMu :317-329
+    prev_cost = cost;
+  }
+  out->iterations = iter;
+  out->stop = stop;
+  out->mu = mu;
+  out->cost = cost;
+  out->prev_cost = prev_cost;
+  return LMGPU_OK;
+}
+
+int lmgpu_gnc_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows6) {
+  if (!h) return -1;
+  const int n = (int)(h->gnc_trace.size() / 6);
+  if (rows6)
+    for (int i = 0; i < std::min(n, (int)max_rows) * 6; i++) rows6[i] = h->gnc_trace[i];
+  return n;
 }
 
 int lmgpu_set_kernel_timing(lmgpu_handle* h, int32_t on) {

@@ -327,10 +327,14 @@ class NonlinearFactorGraph:
             self._add(ftype, [keys], [meas], model)
 
     def resize(self, n):
-        """FactorGraph::resize(0) as the incremental examples use it to start the next batch of new factors"""
-        if n != 0:
-            raise NotImplementedError("only resize(0)")
-        self.__init__()
+        """FactorGraph::resize: 0 as the incremental examples use it to start the next batch of new factors; n >= size() appends
+        empty slots (null factors: they keep their graph index and hold nothing)"""
+        if n == 0:
+            self.__init__()
+        elif n >= self._n:
+            self._n = int(n)
+        else:
+            raise NotImplementedError("only resize(0) or growing")
 
     # -- reference-named adders (single factor or a batch with one shared model)
     def add_GeneralSFMFactor(self, measured, model, cameraKey, landmarkKey):

@@ -601,3 +601,231 @@ class JointMarginal:
 
     def fullMatrix(self) -> np.ndarray:
         return self._full.copy()
+
+
+# ---------------------------------------------------------------- GNC (gtsam/nonlinear/GncParams.h, GncOptimizer.h)
+class GncLossType:
+    """GncParams.h:36-39"""
+    GM = _lib.LMGPU_GNC_GM    # Geman McClure
+    TLS = _lib.LMGPU_GNC_TLS  # Truncated least squares
+
+
+class _GncParams:
+    """GncParams<BaseOptimizerParameters> (GncParams.h:42-160): defaults lossType TLS, maxIterations 100, muStep 1.4, relativeCostTol 1e-5,
+    weightsTol 1e-4 (:69-73), no known inliers / outliers; setters as there (:84-138)."""
+    _base_params = LevenbergMarquardtParams
+    _base_kind = _lib.LMGPU_GNC_BASE_LM
+
+    def __init__(self, baseOptimizerParams=None):
+        self.baseOptimizerParams = baseOptimizerParams if baseOptimizerParams is not None else self._base_params()
+        self.lossType = GncLossType.TLS
+        self.maxIterations = 100
+        self.muStep = 1.4
+        self.relativeCostTol = 1e-5
+        self.weightsTol = 1e-4
+        self.knownInliers = []
+        self.knownOutliers = []
+
+    def setLossType(self, type_):
+        self.lossType = type_
+
+    def setMaxIterations(self, maxIter):
+        self.maxIterations = int(maxIter)
+
+    def setMuStep(self, step):
+        self.muStep = float(step)
+
+    def setRelativeCostTol(self, value):
+        self.relativeCostTol = float(value)
+
+    def setWeightsTol(self, value):
+        self.weightsTol = float(value)
+
+    def setKnownInliers(self, knownIn):
+        """GncParams.h:122-127: appended to the list, which is kept sorted"""
+        self.knownInliers = sorted(list(self.knownInliers) + [int(i) for i in knownIn])
+
+    def setKnownOutliers(self, knownOut):
+        """GncParams.h:133-138: appended to the list, which is kept sorted"""
+        self.knownOutliers = sorted(list(self.knownOutliers) + [int(i) for i in knownOut])
+
+    def _c(self):
+        return _lib.lmgpu_gnc_params(int(self.lossType), int(self.maxIterations), self._base_kind, float(self.muStep),
+                                     float(self.relativeCostTol), float(self.weightsTol))
+
+
+class GncLMParams(_GncParams):
+    """GncParams<LevenbergMarquardtParams>"""
+
+
+class GncGaussNewtonParams(_GncParams):
+    """GncParams<GaussNewtonParams>"""
+    _base_params = GaussNewtonParams
+    _base_kind = _lib.LMGPU_GNC_BASE_GN
+
+
+class GncOptimizer:
+    """GncOptimizer<GncParams<...>>(graph, initialValues, params) (gtsam/nonlinear/GncOptimizer.h:44-470) on ONE device handle, created
+    once: the outer loop runs in liblmgpu.so (lmgpu_gnc_optimize), the weights / thresholds / known mask stay on the device and only
+    cross the bus in getWeights / setWeights / getInlierCostThresholds / setInlierCostThresholds.  `ordering` as for the base optimizers
+    (default: baseOptimizerParams.ordering).  The constructor's checks (:75-99) raise before any device work.  Single GPU.
+    Unlike the reference's, this object works on the handle's state: initializeMu() and calculateWeights(values, mu) set the handle's
+    current values (to the initial values / to `values`), so the values of an earlier optimize() are gone from the device afterwards
+    (the Values object optimize() returned is the caller's); optimize() uses the handle's one value snapshot (save_values of the base
+    optimizer object) for the initial values; every change of the weights invalidates linear graphs handed out before."""
+
+    def __init__(self, graph: NonlinearFactorGraph, initialValues: Values, params=None, ordering=None, device: int = 0):
+        self.params = params if params is not None else GncLMParams()
+        if not isinstance(self.params, _GncParams):
+            raise ValueError("GncOptimizer: params must be GncLMParams or GncGaussNewtonParams")
+        if self.params.lossType not in (GncLossType.GM, GncLossType.TLS):
+            raise RuntimeError("GncOptimizer: unknown loss type")
+        n = graph.size()
+        kin, kout = list(self.params.knownInliers), list(self.params.knownOutliers)
+        if set(kin) & set(kout):
+            raise RuntimeError("GncOptimizer::constructor: the user has selected one or more measurements to be BOTH a known inlier and a "
+                               "known outlier.")
+        if any(i < 0 or i > n - 1 for i in kin):
+            raise RuntimeError("GncOptimizer::constructor: the user has selected one or more measurements that are not in the factor graph "
+                               "to be known inliers.")
+        if any(i < 0 or i > n - 1 for i in kout):
+            raise RuntimeError("GncOptimizer::constructor: the user has selected one or more measurements that are not in the factor graph "
+                               "to be known outliers.")
+        base_cls = GaussNewtonOptimizer if self.params._base_kind == _lib.LMGPU_GNC_BASE_GN else LevenbergMarquardtOptimizer
+        self._n = n
+        self._state = initialValues.copy()
+        self._opt = base_cls(graph, initialValues, ordering, self.params.baseOptimizerParams, device=device)
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_enable(o._h, 1, n))
+        self._set_known(kin, kout)
+        self.result = _lib.lmgpu_gnc_result()
+
+    # ------------------------------------------------------------ plumbing
+    def _set_known(self, kin, kout):
+        o = self._opt
+        a, b = np.asarray(kin, dtype=np.uint64), np.asarray(kout, dtype=np.uint64)
+        up = ct.POINTER(ct.c_uint64)
+        o._check(o.lib.lmgpu_gnc_set_known(o._h, len(a), a.ctypes.data_as(up), len(b), b.ctypes.data_as(up)))
+        self._weights_changed()
+
+    def _weights_changed(self):
+        """the [A b] on the device carry other weights now: linear graphs handed out earlier refuse to be read"""
+        o = self._opt
+        o._lin_generation = getattr(o, "_lin_generation", 0) + 1
+
+    def close(self):
+        self._opt.close()
+
+    def base(self):
+        """the base optimizer object whose handle carries the weighted graph (error(), iterate(), solve(), jacobian(), ... act on it)"""
+        return self._opt
+
+    # ------------------------------------------------------------ reference interface
+    @staticmethod
+    def Chi2inv(alpha, dofs):
+        """GncOptimizer.h:38-40"""
+        return float(_lib.load().lmgpu_chi2inv(float(alpha), int(dofs)))
+
+    def getFactors(self):
+        return self._opt.graph
+
+    def getState(self):
+        return self._state
+
+    def getParams(self):
+        return self.params
+
+    def setInlierCostThresholds(self, inth):
+        """:115-125: one threshold for all factors, or one per factor"""
+        v = np.full(self._n, float(inth)) if np.isscalar(inth) else np.ascontiguousarray(inth, dtype=np.float64).reshape(-1)
+        if v.size != self._n:
+            raise RuntimeError("GncOptimizer::setInlierCostThresholds: the number of thresholds does not match the size of the factor graph.")
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_set_inlier_cost_thresholds(o._h, self._n, _dp(v), 0.0))
+
+    def setInlierCostThresholdsAtProbability(self, alpha):
+        """:130-137"""
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_set_inlier_cost_thresholds(o._h, self._n, None, float(alpha)))
+
+    def getInlierCostThresholds(self):
+        out = np.empty(max(1, self._n))
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_get_inlier_cost_thresholds(o._h, self._n, _dp(out)))
+        return out[:self._n]
+
+    def setWeights(self, w):
+        """:142-149"""
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != self._n:
+            raise RuntimeError("GncOptimizer::setWeights: the number of specified weights does not match the size of the factor graph.")
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_set_weights(o._h, self._n, _dp(w)))
+        self._weights_changed()
+
+    def getWeights(self):
+        out = np.empty(max(1, self._n))
+        o = self._opt
+        o._check(o.lib.lmgpu_gnc_get_weights(o._h, self._n, _dp(out)))
+        return out[:self._n]
+
+    def initializeMu(self):
+        """:272-314, at the initial values (state_), which become the handle's current values"""
+        o = self._opt
+        o.set_values(self._state)
+        mu = ct.c_double()
+        o._check(o.lib.lmgpu_gnc_initialize_mu(o._h, int(self.params.lossType), ct.byref(mu)))
+        return mu.value
+
+    def updateMu(self, mu):
+        """:317-329"""
+        if self.params.lossType == GncLossType.GM:
+            return max(1.0, mu / self.params.muStep)
+        return mu * self.params.muStep
+
+    def checkMuConvergence(self, mu):
+        """:332-348"""
+        return self.params.lossType == GncLossType.GM and abs(mu - 1.0) < 1e-9
+
+    def checkCostConvergence(self, cost, prev_cost):
+        """:351-359"""
+        return abs(cost - prev_cost) / max(prev_cost, 1e-7) < self.params.relativeCostTol
+
+    def checkWeightsConvergence(self, weights):
+        """:362-386"""
+        if self.params.lossType != GncLossType.TLS:
+            return False
+        w = np.asarray(weights, dtype=np.float64)
+        rounded = np.sign(w) * np.floor(np.abs(w) + 0.5)  # std::round: half away from zero
+        return not bool((np.abs(w - rounded) > self.params.weightsTol).any())
+
+    def checkConvergence(self, mu, weights, cost, prev_cost):
+        """:389-393"""
+        return self.checkCostConvergence(cost, prev_cost) or self.checkWeightsConvergence(weights) or self.checkMuConvergence(mu)
+
+    def calculateWeights(self, currentEstimate: Values, mu):
+        """:419-469: the weights at `currentEstimate`.  Side effects: they become the handle's current weights (as weights_ does in
+        optimize()) and `currentEstimate` the handle's current values"""
+        o = self._opt
+        o.set_values(currentEstimate)
+        o._check(o.lib.lmgpu_gnc_calculate_weights(o._h, int(self.params.lossType), float(mu)))
+        self._weights_changed()
+        return self.getWeights()
+
+    def optimize(self) -> Values:
+        """:183-269; the summary of the run is in .result (iterations, stop, mu, cost, prev_cost, base_iterations_total)"""
+        o = self._opt
+        o.set_values(self._state)
+        gp, bp = self.params._c(), self.params.baseOptimizerParams._c()
+        o._check(o.lib.lmgpu_gnc_optimize(o._h, ct.byref(gp), ct.byref(bp), ct.byref(o.state), ct.byref(self.result)))
+        o._lin_generation = getattr(o, "_lin_generation", 0) + 1
+        return o.values()
+
+    def trace(self):
+        """per outer iteration of the last optimize(): (mu, cost, max |w - round(w)|, weight-update device ms, base optimizer host ms,
+        base optimizer iterations)"""
+        o = self._opt
+        n = o.lib.lmgpu_gnc_get_trace(o._h, 0, None)
+        out = np.zeros((max(n, 1), 6))
+        o.lib.lmgpu_gnc_get_trace(o._h, n, _dp(out))
+        return out[:n]

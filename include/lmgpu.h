@@ -240,6 +240,75 @@ typedef struct lmgpu_pcg_stats {
 } lmgpu_pcg_stats;
 int lmgpu_get_pcg_stats(const lmgpu_handle* h, lmgpu_pcg_stats* out);
 
+/* ---- GNC: GncOptimizer<GncParams<LevenbergMarquardtParams | GaussNewtonParams>> (gtsam/nonlinear/GncOptimizer.h, GncParams.h) on the
+ *      device-resident graph.  Graduated non-convexity is an outer loop around the base optimizer: per outer iteration every factor gets a
+ *      weight w_k in [0, 1] from its unweighted error r_k at the last result, and the base optimizer runs again FROM THE INITIAL VALUES on
+ *      the graph whose factor k has the information w_k * information_k (makeWeightedGraph :396-416).  Here the weight lives in the factor
+ *      kernels: linearize multiplies the whitened [A b] of factor k by sqrt(w_k), the factor's error is w_k * 0.5 ||whitened e||^2, and a
+ *      bucket's noiseModel::Robust is ignored while GNC is enabled (the constructor strips it, :63-73).  The graph structure does not
+ *      change under reweighting, so the symbolic analysis, the plan and all front memory are reused by every outer iteration; the weight,
+ *      error, threshold and known-inlier / known-outlier vectors stay in device memory except in the explicit get / set calls.
+ *      For GAUSS noise the reference re-factors w * information into a new R', which differs from sqrt(w) R by an orthogonal factor: a
+ *      factor's [A b] is not a parity quantity there; A^T A, A^T b, the error, the step and the values are.
+ *      A weight of 0 removes the factor; if that leaves a variable unconstrained the solve returns LMGPU_INDETERMINATE like any singular
+ *      system (the reference throws in the same place).
+ *      Boundary vectors (weights, thresholds) have graph_size = nfg_.size() entries indexed by the factor's graph index (`graph_index` of
+ *      lmgpu_add_factor_bucket); a slot of the graph that holds no factor reads as weight 1 / threshold 1 and takes part in no reduction.
+ *      Single rank (world_size > 1: LMGPU_INVALID); Cholesky and PCG alike (the weights act in linearize and error); ISAM2 is not affected.
+ *      While enabled, lmgpu_error, lmgpu_linearize, lmgpu_lm_init, lmgpu_iterate, lmgpu_gn_iterate, ... act on the weighted graph with the
+ *      current weights; a change of the weights (set_weights, set_known, calculate_weights, enable) invalidates the stored linearization
+ *      (lmgpu_solve and lmgpu_get_jacobian(s) refuse until the next lmgpu_linearize); lmgpu_gnc_enable(h, 0, 0) returns the handle to exactly its behaviour without GNC.  Every other lmgpu_gnc_* call
+ *      on a handle without GNC enabled returns LMGPU_INVALID. */
+enum lmgpu_gnc_loss { LMGPU_GNC_GM = 0, LMGPU_GNC_TLS = 1 };    /* GncLossType, GncParams.h:36-39 */
+enum lmgpu_gnc_base { LMGPU_GNC_BASE_LM = 0, LMGPU_GNC_BASE_GN = 1 };
+typedef struct lmgpu_gnc_params { /* GncParams.h:66-81; defaults TLS, 100, 1.4, 1e-5, 1e-4 */
+  int32_t lossType, maxIterations, baseOptimizer;
+  double muStep, relativeCostTol, weightsTol;
+} lmgpu_gnc_params;
+typedef struct lmgpu_gnc_result {
+  int32_t iterations;            /* `iter` at the exit of the loop GncOptimizer.h:218-257 */
+  int32_t stop;                  /* 0 maxIterations, 1 cost, 2 weights, 3 mu, 4 mu <= 0 at initialisation, 5 nothing unknown */
+  double mu, cost, prev_cost;
+  int32_t base_iterations_total; /* sum of the base optimizer's iterations over all its runs */
+} lmgpu_gnc_result;
+/* Chi2inv (GncOptimizer.h:38-40): the alpha quantile of the chi-square distribution with `dofs` degrees of freedom, MATLAB's chi2inv.
+ * Host code, no device: regularised incomplete gamma function + Newton inside a bisection bracket.  NaN for alpha outside [0, 1). */
+double lmgpu_chi2inv(double alpha, int32_t dofs);
+/* on != 0: the constructor's state (GncOptimizer.h:100-106): allocate the weight, threshold and mask vectors; weights 1; thresholds
+ * 0.5 * chi2inv(0.99, rows of the factor); no known inliers / outliers.  graph_size = nfg_.size() (> every graph_index; 0: the largest
+ * graph_index + 1).  on == 0: drop them.  After lmgpu_finalize_structure. */
+int lmgpu_gnc_enable(lmgpu_handle* h, int32_t on, int32_t graph_size);
+/* setInlierCostThresholds(Vector) (:123-125; n must equal graph_size, :142-149 style check) or, with barcSq == NULL,
+ * setInlierCostThresholdsAtProbability(alpha) (:130-137) */
+int lmgpu_gnc_set_inlier_cost_thresholds(lmgpu_handle* h, int32_t n, const double* barcSq, double alpha);
+/* GncParams::knownInliers / knownOutliers (GncParams.h:78-81) with the constructor's checks (GncOptimizer.h:75-99): an index in both
+ * lists or outside the graph is LMGPU_INVALID.  Resets the weights to initializeWeightsFromKnownInliersAndOutliers (:174-180). */
+int lmgpu_gnc_set_known(lmgpu_handle* h, int32_t n_in, const uint64_t* inliers, int32_t n_out, const uint64_t* outliers);
+int lmgpu_gnc_set_weights(lmgpu_handle* h, int32_t n, const double* w); /* setWeights :142-149: n != graph_size is LMGPU_INVALID */
+int lmgpu_gnc_get_weights(lmgpu_handle* h, int32_t n, double* w);       /* getWeights :161 */
+int lmgpu_gnc_get_inlier_cost_thresholds(lmgpu_handle* h, int32_t n, double* barcSq); /* getInlierCostThresholds :164 */
+/* initializeMu (:272-314) with the factor errors at the handle's CURRENT values (the reference evaluates at state_) */
+int lmgpu_gnc_initialize_mu(lmgpu_handle* h, int32_t lossType, double* mu);
+/* weights_ = calculateWeights(current values, mu) (:419-469) */
+int lmgpu_gnc_calculate_weights(lmgpu_handle* h, int32_t lossType, double mu);
+/* GncOptimizer::optimize() (:183-269).  state_ = the handle's values at the call (kept with lmgpu_save_values, which this call
+ * overwrites).  initializeMu at state_; base optimizer from state_ on the graph with the current weights; prev_cost = its final error;
+ * the two early exits (mu <= 0, nothing unknown); then per outer iteration: calculateWeights at the result, values back to state_, base
+ * optimizer with a FRESH state (lmgpu_lm_init: lambda back to lambdaInitial), cost = its final error, checkConvergence (cost, then
+ * weights, then mu; :389-393), updateMu.  On return the handle's values are the result, lmgpu_gnc_get_weights the last weights,
+ * *base_state_out (may be NULL) the state of the last base optimizer run.  A failing base optimizer's status is returned as it is.
+ * `base` = its parameters; for LMGPU_GNC_BASE_GN only maxIterations and the three tolerances are read.
+ * Host synchronisations per outer iteration beyond the base optimizer's own (its constructor's error evaluation and its loop): NONE --
+ * the weight update is queued in front of the base optimizer and the one scalar checkWeightsConvergence needs (max |w - round(w)|)
+ * arrives under the base optimizer's first wait.  Before the loop: one (initializeMu's scalar) + the copy of lmgpu_save_values. */
+int lmgpu_gnc_optimize(lmgpu_handle* h, const lmgpu_gnc_params* params, const lmgpu_lm_params* base, lmgpu_lm_state* base_state_out,
+                       lmgpu_gnc_result* out);
+/* per outer iteration of the last lmgpu_gnc_optimize, 6 doubles: mu used, cost, max |w - round(w)|, device ms of the weight update (error
+ * kernels + weights + reduction, HIP events), host wall-clock ms of the base optimizer run (it starts the moment the weight update is
+ * queued, without a wait, so it CONTAINS the weight update's device time of the column before), its iterations.  Returns the number of outer iterations
+ * recorded (rows6 may be NULL; at most max_rows rows are written). */
+int lmgpu_gnc_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows6);
+
 /* Per-kernel device time (HIP events on the handle's stream around each launch), accumulated since
  * lmgpu_set_kernel_timing(h, 1).  work[] is the ALGORITHMIC work of the launches in the category:
  * bytes for LINEARIZE (232 B per SFM factor + every camera / point row once) and ALLREDUCE,
