@@ -10,4 +10,5 @@ from .optimizer import (BlockJacobiPreconditionerParameters, DoglegOptimizer, Do
                         GaussNewtonOptimizer, GaussNewtonParams, GncGaussNewtonParams, GncLMParams, GncLossType, GncOptimizer,
                         LevenbergMarquardtOptimizer, LevenbergMarquardtParams, JointMarginal, Marginals,
                         PCGSolverParameters)
+from .init_pose3 import InitializePose3  # noqa: F401
 from .isam2 import ISAM2, ISAM2DoglegParams, ISAM2GaussNewtonParams, ISAM2Params, ISAM2Result  # noqa: F401

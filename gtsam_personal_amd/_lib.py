@@ -75,6 +75,8 @@ class lmgpu_pcg_stats(ct.Structure):
                 ("threshold", ct.c_double), ("precond_ms", ct.c_double), ("iterate_ms", ct.c_double)]
 
 
+LMGPU_INIT_POSE3_ANCHOR_KEY = 99999999
+
 LMGPU_GNC_GM, LMGPU_GNC_TLS = 0, 1
 LMGPU_GNC_BASE_LM, LMGPU_GNC_BASE_GN = 0, 1
 GNC_STOP_REASONS = ("maxIterations", "cost", "weights", "mu", "mu <= 0 at initialisation", "nothing unknown")
@@ -136,6 +138,20 @@ SYMBOLS = {
     "lmgpu_gnc_optimize": (ct.c_int, [_H, ct.POINTER(lmgpu_gnc_params), ct.POINTER(lmgpu_lm_params), ct.POINTER(lmgpu_lm_state),
                                       ct.POINTER(lmgpu_gnc_result)]),
     "lmgpu_gnc_get_trace": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_init_pose3_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.POINTER(_H)]),
+    "lmgpu_init_pose3_destroy": (ct.c_int, [_H]),
+    "lmgpu_init_pose3_last_error": (ct.c_char_p, [_H]),
+    "lmgpu_init_pose3_add_factors": (ct.c_int, [_H, ct.c_int32, ct.c_int32, _I, ct.POINTER(ct.c_uint64), _D, ct.c_int32, _D]),
+    "lmgpu_init_pose3_finalize": (ct.c_int, [_H, ct.c_int32, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_init_pose3_num_poses": (ct.c_int, [_H]),
+    "lmgpu_init_pose3_num_factors": (ct.c_int, [_H]),
+    "lmgpu_init_pose3_get_slots": (ct.c_int, [_H, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_init_pose3_handle": (ct.c_void_p, [_H, ct.c_int32]),
+    "lmgpu_init_pose3_orientations_chordal": (ct.c_int, [_H, _D]),
+    "lmgpu_init_pose3_closest_rotations": (ct.c_int, [ct.c_int32, ct.c_int32, _D, _D]),
+    "lmgpu_init_pose3_orientations_gradient": (ct.c_int, [_H, _D, ct.c_int32, ct.c_int32, _D, _I, _D]),
+    "lmgpu_init_pose3_compute_poses": (ct.c_int, [_H, _D, ct.c_int32, _D, ct.POINTER(lmgpu_lm_state)]),
+    "lmgpu_init_pose3_initialize": (ct.c_int, [_H, _D, ct.c_int32, _D]),
     "lmgpu_set_kernel_timing": (ct.c_int, [_H, ct.c_int32]),
     "lmgpu_get_kernel_times": (ct.c_int, [_H, _D, _D, ct.POINTER(ct.c_int64)]),
     "lmgpu_get_jacobian": (ct.c_int, [_H, ct.c_int32, _D, _I, _I]),

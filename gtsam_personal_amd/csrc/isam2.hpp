@@ -574,6 +574,8 @@ void is_linearize_sel(lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, const int32_t* 
     case LMGPU_F_BEARING_RANGE_2D: hipLaunchKernelGGL((generic_factor_kernel<9, 2, 3, 2, 2, 0, 3, 4, 2, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
     case LMGPU_F_SFM2: hipLaunchKernelGGL(sfm2_factor_kernel<true>, dim3(g128), dim3(128), 0, s, d, vals, nob); break;
     case LMGPU_F_PRIOR_CAL3_S2: hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
+    case LMGPU_F_CHORDAL_BETWEEN: hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
+    case LMGPU_F_PRIOR_VEC9: hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
   }
 }
 
@@ -1723,6 +1725,8 @@ int is_graph_error(lmgpu_isam2* S, bool at_estimate, double* out) {
       case LMGPU_F_BEARING_RANGE_2D: hipLaunchKernelGGL((generic_factor_kernel<9, 2, 3, 2, 2, 0, 3, 4, 2, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
       case LMGPU_F_SFM2: hipLaunchKernelGGL(sfm2_factor_kernel<false>, dim3(g128), dim3(128), 0, s, d, vals, eb); break;
       case LMGPU_F_PRIOR_CAL3_S2: hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
+      case LMGPU_F_CHORDAL_BETWEEN: hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
+      case LMGPU_F_PRIOR_VEC9: hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
     }
   }
   const int g = std::min(256, std::max(1, ((int)nfac + 255) / 256));

@@ -36,7 +36,7 @@ struct BucketDev {
 };
 
 struct ValuesDev {
-  const double* v[6];  // POSE2 [n][3], POSE3 [n][12], POINT3 [n][3], CAM [n][15], POINT2 [n][2], CAL3_S2 [n][5]
+  const double* v[7];  // POSE2 [n][3], POSE3 [n][12], POINT3 [n][3], CAM [n][15], POINT2 [n][2], CAL3_S2 [n][5], VEC9 [n][9]
 };
 
 // whiten Jl (col-major M x COLS) in place
@@ -479,6 +479,38 @@ __device__ __forceinline__ void eval_prior_cal3_s2(const double* m, const double
   if (JAC) set_identity<5>(H1);
 }
 
+// Chordal relaxation of InitializePose3 (gtsam/slam/InitializePose3.cpp:37-71).  The unknown of a pose is the 9-vector of its relaxed
+// rotation, a linear variable; the two factor types are LINEAR in it, so linearized at zero values they are the reference's
+// JacobianFactors: between [-I9 | M9 | b = 0] with M9 = blockdiag(Rij, Rij, Rij) (m = Rij row-major), prior [I9 | b = m].
+template <bool JAC>
+__device__ __forceinline__ void eval_chordal_between(const double* m, const double* v0, const double* v1, double* e, double* H1, double* H2) {
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+      e[3 * k + i] = m[3 * i] * v1[3 * k] + m[3 * i + 1] * v1[3 * k + 1] + m[3 * i + 2] * v1[3 * k + 2] - v0[3 * k + i];
+  if (JAC) {
+#pragma unroll
+    for (int i = 0; i < 81; i++) H1[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 81; i++) H2[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) H1[10 * i] = -1.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) H2[9 * (3 * k + i) + 3 * k + j] = m[3 * i + j];
+  }
+}
+template <bool JAC>
+__device__ __forceinline__ void eval_prior_vec9(const double* m, const double* v0, double* e, double* H1) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) e[i] = v0[i] - m[i];
+  if (JAC) set_identity<9>(H1);
+}
+
 // GeneralSFMFactor2<Cal3_S2> (gtsam/slam/GeneralSFMFactor.h:208-262): one lane per factor, three variables (Pose3, Point3, Cal3_S2).
 // error = PinholeCamera<Cal3_S2>(pose, K).project(point) - z with H1 (2x6), H2 (2x3) as GenericProjectionFactor's (PinholePose chain) and
 // H3 = Cal3_S2::uncalibrate's Dcal = [u 0 v 1 0; 0 v 0 0 1] at the intrinsic point (u, v) (gtsam/geometry/Cal3_S2.cpp:44-50).  A point
@@ -576,6 +608,8 @@ __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const Va
   if (TYPE == 7) eval_projection<JAC>(m, v0, v1, e, H1, H2);
   if (TYPE == 9) eval_bearing_range_2d<JAC>(m, v0, v1, e, H1, H2);
   if (TYPE == 11) eval_prior_cal3_s2<JAC>(m, v0, e, H1);
+  if (TYPE == 12) eval_chordal_between<JAC>(m, v0, v1, e, H1, H2);
+  if (TYPE == 13) eval_prior_vec9<JAC>(m, v0, e, H1);
   if (TYPE == 8) {
     // GenericProjectionFactor with body_P_sensor (ProjectionFactor.h:142-149): camera pose = pose o sensor; H1 = H1_cam Ad(sensor^-1)
     const P3 sensor = load_pose3(m + 7);
@@ -665,6 +699,8 @@ __global__ __launch_bounds__(128) void linearize_multi_kernel(MultiLin ml, Value
     case 8: generic_factor_body<8, 2, 6, 3, 19, 1, 12, 2, 3, true>(b, vals, nob, fi); break;
     case 9: generic_factor_body<9, 2, 3, 2, 2, 0, 3, 4, 2, true>(b, vals, nob, fi); break;
     case 11: generic_factor_body<11, 5, 5, 0, 5, 5, 5, -1, 0, true>(b, vals, nob, fi); break;
+    case 12: generic_factor_body<12, 9, 9, 9, 9, 6, 9, 6, 9, true>(b, vals, nob, fi); break;
+    case 13: generic_factor_body<13, 9, 9, 0, 9, 6, 9, -1, 0, true>(b, vals, nob, fi); break;
     default: break;
   }
 }
@@ -823,6 +859,11 @@ __device__ __forceinline__ void retract_body(int type, int n, const double* cur,
     double* o = out + (size_t)i * 5;
 #pragma unroll
     for (int k = 0; k < 5; k++) o[k] = v[k] + d[k];
+  } else if (type == 6) {  // VEC9: vector space
+    const double* v = cur + (size_t)i * 9;
+    double* o = out + (size_t)i * 9;
+#pragma unroll
+    for (int k = 0; k < 9; k++) o[k] = v[k] + d[k];
   } else {  // PinholeCamera::retract gtsam/geometry/PinholeCamera.h:197-203
     const double* v = cur + (size_t)i * 15;
     double* o = out + (size_t)i * 15;
@@ -837,11 +878,11 @@ __global__ __launch_bounds__(256) void retract_kernel(int type, int n, const dou
 }
 // the variable types of one masked retraction in one launch (ISAM2 relinearizes poses and points in the same update): blockIdx.y = entry
 struct RetractMulti {
-  int32_t type[6], n[6];
-  const double* cur[6];
-  double* out[6];
-  const int32_t* xoff[6];
-  const int32_t* sel[6];
+  int32_t type[7], n[7];
+  const double* cur[7];
+  double* out[7];
+  const int32_t* xoff[7];
+  const int32_t* sel[7];
 };
 __global__ __launch_bounds__(256) void retract_multi_kernel(RetractMulti rm, const double* __restrict__ delta) {
   const int k = blockIdx.y;

@@ -510,6 +510,12 @@ void launch_factors(lmgpu_handle* h, int which) {
       case LMGPU_F_PRIOR_CAL3_S2:
         hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
         break;
+      case LMGPU_F_CHORDAL_BETWEEN:
+        hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
+        break;
+      case LMGPU_F_PRIOR_VEC9:
+        hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
+        break;
     }
   }
 }
@@ -4227,6 +4233,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 }  // extern "C"
 
 #include "isam2.hpp"
+#include "init_pose3.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py
 extern "C" int lmgpu_debug_ldsf(unsigned long long* out16, int reset) {

@@ -9,17 +9,17 @@
 
 namespace lmgpu {
 
-static const int kNumVarTypes = 6;
-static const int kVarDim[6] = {3, 6, 3, 9, 2, 5};
-static const int kVarStore[6] = {3, 12, 3, 15, 2, 5};
+static const int kNumVarTypes = 7;
+static const int kVarDim[7] = {3, 6, 3, 9, 2, 5, 9};
+static const int kVarStore[7] = {3, 12, 3, 15, 2, 5, 9};
 static const int kMaxArity = 3;
-static const int kFactorArity[12] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1};
-static const int kFactorRows[12] = {2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5};
-static const int kFactorMeas[12] = {2, 3, 12, 3, 12, 3, 15, 7, 19, 2, 2, 5};
+static const int kFactorArity[14] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1, 2, 1};
+static const int kFactorRows[14] = {2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5, 9, 9};
+static const int kFactorMeas[14] = {2, 3, 12, 3, 12, 3, 15, 7, 19, 2, 2, 5, 9, 9};
 // variable types each factor type expects (for validation)
-static const int kFactorVar0[12] = {3, 0, 1, 0, 1, 2, 3, 1, 1, 0, 1, 5};
-static const int kFactorVar1[12] = {2, 0, 1, -1, -1, -1, -1, 2, 2, 4, 2, -1};
-static const int kFactorVar2[12] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 5, -1};
+static const int kFactorVar0[14] = {3, 0, 1, 0, 1, 2, 3, 1, 1, 0, 1, 5, 6, 6};
+static const int kFactorVar1[14] = {2, 0, 1, -1, -1, -1, -1, 2, 2, 4, 2, -1, 6, -1};
+static const int kFactorVar2[14] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 5, -1, -1, -1};
 inline int factor_var_type(int ftype, int k) { return k == 0 ? kFactorVar0[ftype] : (k == 1 ? kFactorVar1[ftype] : kFactorVar2[ftype]); }
 
 struct FactorRef {

@@ -15,18 +15,18 @@ from __future__ import annotations
 import numpy as np
 
 # ---- enums shared with include/lmgpu.h
-POSE2, POSE3, POINT3, CAM_BUNDLER, POINT2, CAL3_S2 = 0, 1, 2, 3, 4, 5
-VAR_DIM = (3, 6, 3, 9, 2, 5)
-VAR_STORE = (3, 12, 3, 17, 2, 5)      # host packed value (camera keeps u0, v0)
-VAR_STORE_DEV = (3, 12, 3, 15, 2, 5)  # C-ABI packed value
+POSE2, POSE3, POINT3, CAM_BUNDLER, POINT2, CAL3_S2, VEC9 = 0, 1, 2, 3, 4, 5, 6
+VAR_DIM = (3, 6, 3, 9, 2, 5, 9)
+VAR_STORE = (3, 12, 3, 17, 2, 5, 9)      # host packed value (camera keeps u0, v0)
+VAR_STORE_DEV = (3, 12, 3, 15, 2, 5, 9)  # C-ABI packed value
 
 (F_SFM, F_BETWEEN_POSE2, F_BETWEEN_POSE3, F_PRIOR_POSE2, F_PRIOR_POSE3, F_PRIOR_POINT3, F_PRIOR_CAM, F_PROJECTION, F_PROJECTION_BPS,
- F_BEARING_RANGE_2D, F_SFM2, F_PRIOR_CAL3_S2) = range(12)
-FACTOR_ARITY = (2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1)
-FACTOR_ROWS = (2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5)
-FACTOR_MEAS = (2, 3, 12, 3, 12, 3, 17, 7, 19, 2, 2, 5)  # host measurement doubles (PRIOR_CAM carries u0, v0)
+ F_BEARING_RANGE_2D, F_SFM2, F_PRIOR_CAL3_S2, F_CHORDAL_BETWEEN, F_PRIOR_VEC9) = range(14)
+FACTOR_ARITY = (2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1, 2, 1)
+FACTOR_ROWS = (2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5, 9, 9)
+FACTOR_MEAS = (2, 3, 12, 3, 12, 3, 17, 7, 19, 2, 2, 5, 9, 9)  # host measurement doubles (PRIOR_CAM carries u0, v0)
 FACTOR_VARS = ((CAM_BUNDLER, POINT3), (POSE2, POSE2), (POSE3, POSE3), (POSE2,), (POSE3,), (POINT3,), (CAM_BUNDLER,), (POSE3, POINT3), (POSE3, POINT3),
-               (POSE2, POINT2), (POSE3, POINT3, CAL3_S2), (CAL3_S2,))
+               (POSE2, POINT2), (POSE3, POINT3, CAL3_S2), (CAL3_S2,), (VEC9, VEC9), (VEC9,))
 
 N_UNIT, N_ISO, N_DIAG, N_GAUSS = 0, 1, 2, 3
 
@@ -222,6 +222,10 @@ class Values:
         """Cal3_S2 as a variable (self-calibration, examples/SelfCalibrationExample.cpp:55-56)"""
         self.insert(key, CAL3_S2, [fx, fy, s, u0, v0])
 
+    def insert_vec9(self, key, v):
+        """a 9-vector unknown (the relaxed rotation of InitializePose3's chordal relaxation, column-major 3x3)"""
+        self.insert(key, VEC9, v)
+
     def insert_camera(self, key, R, t, f, k1, k2, u0=0.0, v0=0.0):
         self.insert(key, CAM_BUNDLER, camera_pack(R, t, f, k1, k2, u0, v0))
 
@@ -368,6 +372,17 @@ class NonlinearFactorGraph:
     def add_PriorFactorCal3_S2(self, key, K, model):
         """PriorFactor<Cal3_S2>; K = (fx, fy, s, u0, v0)"""
         self._add(F_PRIOR_CAL3_S2, [[key]], K, model)
+
+    def add_ChordalBetweenFactor(self, key1, key2, Rij, precision):
+        """the JacobianFactor (key1, -I9, key2, blockdiag(Rij, Rij, Rij), 0, Isotropic::Precision(9, precision)) of
+        InitializePose3::buildLinearOrientationGraph (gtsam/slam/InitializePose3.cpp:56-62); precision 0 is allowed"""
+        p = float(precision)
+        model = NoiseModel(9, N_UNIT) if p == 1.0 else NoiseModel(9, N_DIAG, np.full(9, 1.0 / np.sqrt(p) if p > 0 else np.inf))
+        self._add(F_CHORDAL_BETWEEN, [[key1, key2]], np.asarray(Rij, dtype=np.float64).reshape(9), model)
+
+    def add_PriorFactorVec9(self, key, b, model=None):
+        """the JacobianFactor (key, I9, b, model) (the anchor's prior, InitializePose3.cpp:65-69)"""
+        self._add(F_PRIOR_VEC9, [[key]], b, model)
 
     def add_GeneralSFMFactor2(self, measured, model, poseKey, landmarkKey, calibKey):
         """GeneralSFMFactor2<Cal3_S2>(measured, model, poseKey, landmarkKey, calibKey)  (gtsam/slam/GeneralSFMFactor.h:236-237)"""

@@ -44,6 +44,8 @@ enum lmgpu_status {
  *               (z' = z - (u0, v0)); Cal3Bundler::retract keeps it constant (gtsam/geometry/Cal3Bundler.h:134-136).
  *   POINT2      dim 2  store 2                           planar landmark (gtsam/geometry/Point2.h), vector retract
  *   CAL3_S2     dim 5  store 5   (fx, fy, s, u0, v0)     Cal3_S2 as a VARIABLE (gtsam/geometry/Cal3_S2.h:106-119: vector retract / local)
+ *   VEC9        dim 9  store 9   nine scalars, vector retract: the relaxed rotation of the chordal initialisation, the 3x3 matrix
+ *               column-major as in VectorValues of InitializePose3::buildLinearOrientationGraph (gtsam/slam/InitializePose3.cpp:37-71, 84)
  */
 enum lmgpu_var_type {
   LMGPU_POSE2 = 0,
@@ -52,7 +54,8 @@ enum lmgpu_var_type {
   LMGPU_CAM_BUNDLER = 3,
   LMGPU_POINT2 = 4,
   LMGPU_CAL3_S2 = 5,
-  LMGPU_NUM_VAR_TYPES = 6
+  LMGPU_VEC9 = 6,
+  LMGPU_NUM_VAR_TYPES = 7
 };
 
 /* Factor types ("buckets" are keyed by (factor type, noise kind) = fixed block shape).
@@ -74,6 +77,11 @@ enum lmgpu_var_type {
  *                                                              PinholeCamera<Cal3_S2>(pose, K).project(point, H1, H2, H3) - z; a point behind
  *                                                              the camera gives zero error and zero Jacobians (:251-260)
  *   PRIOR_CAL3_S2    1     5     5   (fx, fy, s, u0, v0)       PriorFactor<Cal3_S2>
+ *   CHORDAL_BETWEEN  2     9     9   Rij row-major             the JacobianFactor [-I9 | M9 | b = 0], M9 = blockdiag(Rij, Rij, Rij), of
+ *                                                              InitializePose3::buildLinearOrientationGraph (gtsam/slam/InitializePose3.cpp:56-62)
+ *                                                              on two VEC9: error = M9 x2 - x1.  Its Isotropic::Precision(9, p) is DIAG
+ *                                                              noise with nine times sqrt(p); p = 0 is allowed (a factor of zero rows)
+ *   PRIOR_VEC9       1     9     9   b                         the JacobianFactor [I9 | b] (the anchor's prior, :65-69): error = x - b
  * Keys of a factor: `arity` per factor, in the reference's key order.
  */
 enum lmgpu_factor_type {
@@ -89,7 +97,9 @@ enum lmgpu_factor_type {
   LMGPU_F_BEARING_RANGE_2D = 9,
   LMGPU_F_SFM2 = 10,
   LMGPU_F_PRIOR_CAL3_S2 = 11,
-  LMGPU_NUM_FACTOR_TYPES = 12
+  LMGPU_F_CHORDAL_BETWEEN = 12,
+  LMGPU_F_PRIOR_VEC9 = 13,
+  LMGPU_NUM_FACTOR_TYPES = 14
 };
 
 /* Noise models (gtsam/linear/NoiseModel.cpp).  Per-factor noise data, `rows` = factor rows:
@@ -308,6 +318,62 @@ int lmgpu_gnc_optimize(lmgpu_handle* h, const lmgpu_gnc_params* params, const lm
  * queued, without a wait, so it CONTAINS the weight update's device time of the column before), its iterations.  Returns the number of outer iterations
  * recorded (rows6 may be NULL; at most max_rows rows are written). */
 int lmgpu_gnc_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows6);
+
+/* ---- InitializePose3 (gtsam/slam/InitializePose3.h, InitializePose3.cpp, InitializePose.h): initial estimate of a 3D pose graph on the
+ *      device -- chordal relaxation or the Tron-Vidal gradient iteration for the rotations, then one Gauss-Newton step for the poses.
+ *      An lmgpu_init_pose3 owns two lmgpu_handles over the same slots: the ORIENTATION handle (VEC9 variables, CHORDAL_BETWEEN factors,
+ *      the anchor's PRIOR_VEC9; zero values, so the step of its lambda = 0 solve IS the relaxed solution) and the POSE handle (POSE3
+ *      variables, the extracted pose graph + the anchor's Unit(6) prior).  Rotations cross the boundary as n x 9 doubles, row-major 3x3,
+ *      poses as n x 12 (lmgpu.h POSE3 packing), both in the order of the `ordering` given to lmgpu_init_pose3_finalize with the anchor
+ *      left out.  The rotations of the last orientation call stay in device memory: lmgpu_init_pose3_compute_poses(R = NULL) reads them
+ *      there, so lmgpu_init_pose3_initialize moves nothing but its result through the host.
+ *   lmgpu_init_pose3_add_factors   initialize::buildPoseGraph<Pose3> (InitializePose.h:36-52): LMGPU_F_BETWEEN_POSE3 factors are kept,
+ *        LMGPU_F_PRIOR_POSE3 factors become between factors from LMGPU_INIT_POSE3_ANCHOR_KEY (kAnchorKey, :30), every other factor type
+ *        is dropped silently.  keys: n x arity Keys; meas / noise as in lmgpu_add_factor_bucket; graph_index = the factor's index in the
+ *        caller's NonlinearFactorGraph: the extracted graph keeps that order (createSymbolicGraph's factorId, InitializePose3.cpp:221-253).
+ *        rotationPrecision p (:48-51) = first entry of noiseModel->whitenInPlace(e1): UNIT 1, DIAG invsigma[0] (so Isotropic 1 / sigma),
+ *        GAUSS R[0][0] of the square-root information.
+ *   lmgpu_init_pose3_finalize      ordering = the pose keys in elimination order (a boundary input like everywhere in this library); it
+ *        may contain the anchor key to place it, otherwise the anchor is eliminated last.  Refused with LMGPU_INVALID BEFORE anything is
+ *        built: no Pose3 between factor, a key of `ordering` without a factor in the extracted graph, a factor key missing from
+ *        `ordering`, duplicate keys.  The object stays usable for further lmgpu_init_pose3_add_factors / another finalize.
+ *   lmgpu_init_pose3_orientations_chordal   computeOrientationsChordal (:102-114): linear solve at lambda = 0 (the linear solver selected
+ *        with lmgpu_set_linear_solver on the orientation handle: Cholesky or PCG), then normalizeRelaxedRotations (:75-92) as one kernel,
+ *        one thread per pose, on the solve's step vector in device memory: SO3::ClosestTo (gtsam/geometry/SO3.cpp:202-208) of the
+ *        transposed relaxed matrix by a one-sided Jacobi SVD in FP64.  LMGPU_INDETERMINATE where GaussianFactorGraph::optimize throws.
+ *   lmgpu_init_pose3_closest_rotations      the same kernel on n caller-supplied relaxed 9-vectors (normalizeRelaxedRotations on its own)
+ *   lmgpu_init_pose3_orientations_gradient  computeOrientationsGradient (:117-218) with gradientTron (:256-275): guess_R = the rotations of
+ *        givenGuess (one per pose), maxIter (the reference's default: 10000), setRefFrame.  One thread per node, CSR adjacency in
+ *        factor-index order, two rotation buffers, max-norm by block partials (no floating-point atomics).  The stop rule
+ *        `it > 20 && maxGrad < 5e-3` is evaluated on the device at the head of the next iteration's kernel, which then does nothing:
+ *        the host looks at the loop state once per 128 queued iterations, and the result is that of the reference's stopping iteration.
+ *        *iterations = loop bodies executed, *max_grad = maxGrad of the last one.  Needs at least one prior (the reference's
+ *        adjEdgesMap.at(kAnchorKey) throws without): LMGPU_INVALID otherwise.
+ *   lmgpu_init_pose3_compute_poses          initialize::computePoses<Pose3> (InitializePose.h:57-97): poses (R, 0), anchor at the identity
+ *        with a Unit(6) prior, GaussNewtonOptimizer with maxIterations = 1 (single_iter != 0) or NonlinearOptimizerParams' defaults;
+ *        gn_state_out (may be NULL) = the optimizer's final state.  R = NULL: the rotations of the last orientation call.
+ *   lmgpu_init_pose3_initialize             InitializePose3::initialize(graph, givenGuess, useGradient) (:296-314); guess_R may be NULL
+ *        for use_gradient == 0.
+ *   lmgpu_init_pose3_handle                 which = 0 orientation, 1 pose handle (owned by the object; for the parity taps, lmgpu_error,
+ *        lmgpu_set_linear_solver, lmgpu_get_pcg_stats).  Slots = positions in lmgpu_init_pose3_get_slots' key list. */
+#define LMGPU_INIT_POSE3_ANCHOR_KEY 99999999ull
+typedef struct lmgpu_init_pose3 lmgpu_init_pose3;
+int lmgpu_init_pose3_create(const lmgpu_config* cfg, lmgpu_init_pose3** out);
+int lmgpu_init_pose3_destroy(lmgpu_init_pose3* ip);
+const char* lmgpu_init_pose3_last_error(const lmgpu_init_pose3* ip);
+int lmgpu_init_pose3_add_factors(lmgpu_init_pose3* ip, int32_t factor_type, int32_t n, const int32_t* graph_index, const uint64_t* keys,
+                                 const double* meas, int32_t noise_kind, const double* noise);
+int lmgpu_init_pose3_finalize(lmgpu_init_pose3* ip, int32_t n_order, const uint64_t* ordering);
+int lmgpu_init_pose3_num_poses(const lmgpu_init_pose3* ip);   /* keys of the extracted graph without the anchor; -1 before finalize */
+int lmgpu_init_pose3_num_factors(const lmgpu_init_pose3* ip); /* factors of the extracted pose graph (anchor priors not counted) */
+int lmgpu_init_pose3_get_slots(const lmgpu_init_pose3* ip, uint64_t* keys_out); /* the handles' variables by slot, anchor included; returns their number */
+lmgpu_handle* lmgpu_init_pose3_handle(lmgpu_init_pose3* ip, int32_t which);
+int lmgpu_init_pose3_orientations_chordal(lmgpu_init_pose3* ip, double* R_out);
+int lmgpu_init_pose3_closest_rotations(int32_t device, int32_t n, const double* relaxed9, double* R_out);
+int lmgpu_init_pose3_orientations_gradient(lmgpu_init_pose3* ip, const double* guess_R, int32_t max_iter, int32_t set_ref_frame, double* R_out,
+                                           int32_t* iterations, double* max_grad);
+int lmgpu_init_pose3_compute_poses(lmgpu_init_pose3* ip, const double* R, int32_t single_iter, double* poses_out, lmgpu_lm_state* gn_state_out);
+int lmgpu_init_pose3_initialize(lmgpu_init_pose3* ip, const double* guess_R, int32_t use_gradient, double* poses_out);
 
 /* Per-kernel device time (HIP events on the handle's stream around each launch), accumulated since
  * lmgpu_set_kernel_timing(h, 1).  work[] is the ALGORITHMIC work of the launches in the category:

@@ -750,4 +750,104 @@ class GpuISAM2 {
   Values all_;  // every variable ever added, at its initial value
 };
 
+/// InitializePose3::initialize(graph, givenGuess, useGradient) (gtsam/slam/InitializePose3.h:85-92, InitializePose3.cpp:296-319) on the
+/// device: call gtsam::GpuInitializePose3::initialize where the program called InitializePose3::initialize.  The pose graph is extracted
+/// by the library (BetweenFactor<Pose3> kept, PriorFactor<Pose3> tied to kAnchorKey, everything else dropped: InitializePose.h:36-52);
+/// the relaxation, the projection onto SO(3) / the gradient iteration and the Gauss-Newton step run behind lmgpu_init_pose3_*.
+/// `ordering`: elimination order of the pose keys (default: ascending keys, Ordering::Natural); the anchor is placed last unless listed.
+class GpuInitializePose3 {
+ public:
+  static Values initialize(const NonlinearFactorGraph& graph, const Values& givenGuess, bool useGradient = false, const Ordering* ordering = nullptr,
+                           int device = 0) {
+    Session s(graph, ordering, device);
+    std::vector<double> guess;
+    if (useGradient) guess = s.packGuess(givenGuess);
+    std::vector<double> poses(s.keys.size() * 12);
+    s.check(lmgpu_init_pose3_initialize(s.ip, useGradient ? guess.data() : nullptr, useGradient ? 1 : 0, poses.data()));
+    Values out;
+    for (size_t i = 0; i < s.keys.size(); i++) out.insert(s.keys[i], lmgpu_detail::unpackPose3(&poses[12 * i]));
+    return out;
+  }
+  static Values initialize(const NonlinearFactorGraph& graph) { return initialize(graph, Values(), false); }
+
+  /// initializeOrientations (InitializePose3.cpp:278-285): the chordal rotations as Rot3
+  static Values initializeOrientations(const NonlinearFactorGraph& graph, const Ordering* ordering = nullptr, int device = 0) {
+    Session s(graph, ordering, device);
+    std::vector<double> R(s.keys.size() * 9);
+    s.check(lmgpu_init_pose3_orientations_chordal(s.ip, R.data()));
+    return s.rotations(R);
+  }
+
+  /// computeOrientationsGradient (:117-218) on the graph's extracted pose graph
+  static Values computeOrientationsGradient(const NonlinearFactorGraph& graph, const Values& givenGuess, size_t maxIter = 10000,
+                                            bool setRefFrame = true, const Ordering* ordering = nullptr, int device = 0) {
+    Session s(graph, ordering, device);
+    const std::vector<double> guess = s.packGuess(givenGuess);
+    std::vector<double> R(s.keys.size() * 9);
+    s.check(lmgpu_init_pose3_orientations_gradient(s.ip, guess.data(), static_cast<int32_t>(maxIter), setRefFrame ? 1 : 0, R.data(), nullptr, nullptr));
+    return s.rotations(R);
+  }
+
+ private:
+  struct Session {
+    lmgpu_init_pose3* ip = nullptr;
+    KeyVector keys;  // result order: the ordering without the anchor
+    Session(const NonlinearFactorGraph& graph, const Ordering* ordering, int device) {
+      lmgpu_config cfg{device, 0, 1, 0};
+      if (lmgpu_init_pose3_create(&cfg, &ip) != LMGPU_OK) throw std::runtime_error("lmgpu_init_pose3_create failed");
+      KeySet seen;
+      for (size_t i = 0; i < graph.size(); i++) {
+        const auto& f = graph[i];
+        if (!f) continue;
+        const bool between = static_cast<bool>(std::dynamic_pointer_cast<BetweenFactor<Pose3>>(f));
+        const bool prior = static_cast<bool>(std::dynamic_pointer_cast<PriorFactor<Pose3>>(f));
+        if (!between && !prior) continue;  // buildPoseGraph drops everything else
+        int32_t type = 0;
+        std::vector<double> m;
+        lmgpu_detail::extractFactor(f, Values(), &type, &m);
+        const lmgpu_detail::Noise nz = lmgpu_detail::extractNoise(std::static_pointer_cast<NoiseModelFactor>(f)->noiseModel());
+        if (nz.robust != LMGPU_ROBUST_NONE) throw std::invalid_argument("GpuInitializePose3: robust noise models are not bound");
+        const int32_t gi = static_cast<int32_t>(i);
+        std::vector<uint64_t> k(f->keys().begin(), f->keys().end());
+        for (uint64_t key : k) seen.insert(key);
+        check(lmgpu_init_pose3_add_factors(ip, type, 1, &gi, k.data(), m.data(), nz.kind, nz.data.empty() ? nullptr : nz.data.data()));
+      }
+      std::vector<uint64_t> order;
+      if (ordering) order.assign(ordering->begin(), ordering->end());
+      else order.assign(seen.begin(), seen.end());
+      if (order.empty()) order.push_back(LMGPU_INIT_POSE3_ANCHOR_KEY);  // let the library refuse the empty graph
+      check(lmgpu_init_pose3_finalize(ip, static_cast<int32_t>(order.size()), order.data()));
+      for (uint64_t key : order)
+        if (key != LMGPU_INIT_POSE3_ANCHOR_KEY) keys.push_back(key);
+    }
+    ~Session() { lmgpu_init_pose3_destroy(ip); }
+    Session(const Session&) = delete;
+    Session& operator=(const Session&) = delete;
+    void check(int rc) const {
+      if (rc == LMGPU_OK) return;
+      if (rc == LMGPU_INDETERMINATE) throw IndeterminantLinearSystemException(keys.empty() ? Key(0) : keys.front());
+      throw std::invalid_argument(std::string("GpuInitializePose3: ") + lmgpu_init_pose3_last_error(ip));
+    }
+    std::vector<double> packGuess(const Values& givenGuess) const {
+      std::vector<double> g(keys.size() * 9);
+      for (size_t i = 0; i < keys.size(); i++) {
+        const Matrix3 R = givenGuess.at<Pose3>(keys[i]).rotation().matrix();
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) g[9 * i + 3 * r + c] = R(r, c);
+      }
+      return g;
+    }
+    Values rotations(const std::vector<double>& R) const {
+      Values out;
+      for (size_t i = 0; i < keys.size(); i++) {
+        Matrix3 M;
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) M(r, c) = R[9 * i + 3 * r + c];
+        out.insert(keys[i], Rot3(M));
+      }
+      return out;
+    }
+  };
+};
+
 }  // namespace gtsam
