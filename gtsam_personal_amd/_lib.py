@@ -92,6 +92,14 @@ class lmgpu_gnc_result(ct.Structure):
                 ("base_iterations_total", ct.c_int32)]
 
 
+LMGPU_NCG_FLETCHER_REEVES, LMGPU_NCG_POLAK_RIBIERE, LMGPU_NCG_HESTENES_STIEFEL, LMGPU_NCG_DAI_YUAN = 0, 1, 2, 3
+
+
+class lmgpu_ncg_params(ct.Structure):
+    _fields_ = [("direction_method", ct.c_int32), ("gradient_descent", ct.c_int32), ("max_iterations", ct.c_int32),
+                ("relative_error_tol", ct.c_double), ("absolute_error_tol", ct.c_double), ("error_tol", ct.c_double)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -138,6 +146,12 @@ SYMBOLS = {
     "lmgpu_gnc_optimize": (ct.c_int, [_H, ct.POINTER(lmgpu_gnc_params), ct.POINTER(lmgpu_lm_params), ct.POINTER(lmgpu_lm_state),
                                       ct.POINTER(lmgpu_gnc_result)]),
     "lmgpu_gnc_get_trace": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_gradient": (ct.c_int, [_H, _D]),
+    "lmgpu_ncg_line_search": (ct.c_int, [_H, _D, _D, _I]),
+    "lmgpu_ncg_iterate": (ct.c_int, [_H, ct.POINTER(lmgpu_ncg_params), ct.POINTER(lmgpu_lm_state)]),
+    "lmgpu_ncg_optimize": (ct.c_int, [_H, ct.POINTER(lmgpu_ncg_params), ct.POINTER(lmgpu_lm_state)]),
+    "lmgpu_ncg_get_trace": (ct.c_int, [_H, ct.c_int32, _D]),
+    "lmgpu_ncg_host_waits": (ct.c_int, [_H]),
     "lmgpu_init_pose3_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.POINTER(_H)]),
     "lmgpu_init_pose3_destroy": (ct.c_int, [_H]),
     "lmgpu_init_pose3_last_error": (ct.c_char_p, [_H]),

@@ -33,6 +33,8 @@ struct BucketDev {
   const double* gw = nullptr;  // GNC weight of each factor, addressed like the error buffer (gw[epos[f]]); null: no weighting.
                                // GncOptimizer::makeWeightedGraph (gtsam/nonlinear/GncOptimizer.h:396-416): Information(w * information),
                                // i.e. [A b] *= sqrt(w) after the whitening and error = w * 0.5 ||whitened e||^2
+  const int32_t* skip = nullptr;  // error launches only: when set and *skip != 0 the launch does nothing (the trials of a nonlinear
+                                  // conjugate gradient line search queued behind its exit test, kernels_ncg.hpp); null everywhere else
 };
 
 struct ValuesDev {
@@ -281,6 +283,7 @@ __global__ __launch_bounds__(256) void sfm_linearize_sel_kernel(BucketDev b, Val
 __global__ __launch_bounds__(256) void sfm_error_kernel(BucketDev b, ValuesDev vals, double* __restrict__ ebuf) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= b.n) return;
+  if (b.skip && *b.skip) return;
   const int ci = b.vidx[2 * f], pi_ = b.vidx[2 * f + 1];
   double cam[15], pt[3];
   const double* cp = vals.v[3] + (size_t)ci * 15;
@@ -520,6 +523,7 @@ template <bool JAC>
 __global__ __launch_bounds__(128) void sfm2_factor_kernel(BucketDev b, ValuesDev vals, double* __restrict__ ebuf) {
   const int fi = blockIdx.x * blockDim.x + threadIdx.x;
   if (fi >= b.n) return;
+  if (!JAC && b.skip && *b.skip) return;
   const int f = b.sel ? b.sel[fi] : fi;
   constexpr int M = 2, COLS = 15;
   double m[7], v0[12], v1[3];
@@ -583,6 +587,7 @@ __global__ __launch_bounds__(128) void sfm2_factor_kernel(BucketDev b, ValuesDev
 template <int TYPE, int M, int D0, int D1, int ML, int T0, int S0, int T1, int S1, bool JAC>
 __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const ValuesDev& vals, double* __restrict__ ebuf, const int fi) {
   if (fi >= b.n) return;
+  if (!JAC && b.skip && *b.skip) return;
   const int f = b.sel ? b.sel[fi] : fi;
   constexpr int AR = (D1 > 0) ? 2 : 1;
   constexpr int COLS = D0 + D1 + 1;
@@ -833,11 +838,26 @@ __global__ __launch_bounds__(256) void reduce_stage2(const double* __restrict__ 
 // Values::retract gtsam/nonlinear/Values.cpp:53-64; one thread per variable of a type.
 // sel (may be null): the n variables to retract as indices into the type array (ISAM2's retractMasked, gtsam/nonlinear/ISAM2.cpp:465);
 // cur == out is allowed (every lane reads its variable before it writes it).
+// tangent dimension of a variable type: the device's copy of kVarDim (plan.hpp); lmgpu.hip static_asserts that the two agree
+__host__ __device__ constexpr int var_tangent_dim(int type) {
+  return (type == 0 || type == 2) ? 3 : (type == 1 ? 6 : (type == 4 ? 2 : (type == 5 ? 5 : 9)));
+}
+// scaled (the nonlinear conjugate gradient's advance, kernels_ncg.hpp): the tangent vector is scale * delta, each product rounded
+// once like the reference's `step *= alpha` (NonlinearConjugateGradientOptimizer.cpp:66-68); every other caller leaves the default,
+// for which this function is what it was.
 __device__ __forceinline__ void retract_body(int type, int n, const double* cur, double* out, const int32_t* __restrict__ xoff,
-                                             const double* __restrict__ delta, const int32_t* __restrict__ sel, const int li) {
+                                             const double* __restrict__ delta, const int32_t* __restrict__ sel, const int li,
+                                             const double scale = 1.0, const bool scaled = false) {
   if (li >= n) return;
   const int i = sel ? sel[li] : li;
   const double* d = delta + xoff[i];
+  double sd[9];
+  if (scaled) {
+    const int dim = var_tangent_dim(type);
+#pragma unroll
+    for (int k = 0; k < 9; k++) sd[k] = k < dim ? __dmul_rn(scale, d[k]) : 0.0;
+    d = sd;
+  }
   if (type == 0) {  // Pose2: compose(Pose2(d0,d1,d2))  gtsam/geometry/Pose2.cpp:100-110
     const double* v = cur + (size_t)i * 3;
     const P2 c = compose2(pose2_from(v[0], v[1], v[2]), pose2_from(d[0], d[1], d[2]));

@@ -38,6 +38,7 @@
 #include "kernels_schur.hpp"
 #include "kernels_pcg.hpp"
 #include "kernels_gnc.hpp"
+#include "kernels_ncg.hpp"
 #include "plan.hpp"
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
@@ -210,6 +211,9 @@ __global__ void clamp_diag_kernel(int n, const double* __restrict__ diag, double
   const double s = sqrt(fmin(fmax(diag[i], lo), hi));
   w[i] = s * s;
 }
+
+struct NcgState;  // ncg.hpp
+static void ncg_release(lmgpu_handle* h);
 
 struct lmgpu_handle {
   lmgpu_config cfg;
@@ -402,6 +406,10 @@ struct lmgpu_handle {
   std::vector<unsigned char> gnc_fixed_h;
   std::vector<double> gnc_trace; // per outer iteration: mu, cost, max |w - round(w)|, weight-update ms, base optimizer ms, base iterations
   hipEvent_t gnc_ev[2] = {nullptr, nullptr};
+
+  // ---- nonlinear conjugate gradient (kernels_ncg.hpp, ncg.hpp; lmgpu_ncg_*): allocated at first use
+  NcgState* ncg = nullptr;
+  const int32_t* err_skip = nullptr;  // set around the trial launches of a line search: BucketDev::skip of the error launches
 };
 
 namespace {
@@ -454,6 +462,7 @@ BucketDev bucket_dev(lmgpu_handle* h, const Bucket& b) {
   d.J = h->pool + b.joff;
   d.epos = b.d_epos;
   d.sel = nullptr;
+  d.skip = h->err_skip;
   return d;
 }
 
@@ -2036,6 +2045,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
     if (h->h_pcg_done) (void)hipHostFree(h->h_pcg_done);
     for (int i = 0; i < 3; i++)
       if (h->pcg_ev[i]) (void)hipEventDestroy(h->pcg_ev[i]);
+    ncg_release(h);
     fr(h->gnc_w); fr(h->gnc_b); fr(h->gnc_part); fr(h->gnc_scal); fr(h->gnc_fixed);
     if (h->h_gnc_scal) (void)hipHostFree(h->h_gnc_scal);
     for (int i = 0; i < 2; i++)
@@ -4234,6 +4244,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 
 #include "isam2.hpp"
 #include "init_pose3.hpp"
+#include "ncg.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py
 extern "C" int lmgpu_debug_ldsf(unsigned long long* out16, int reset) {

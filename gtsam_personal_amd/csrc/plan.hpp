@@ -10,7 +10,7 @@
 namespace lmgpu {
 
 static const int kNumVarTypes = 7;
-static const int kVarDim[7] = {3, 6, 3, 9, 2, 5, 9};
+static constexpr int kVarDim[7] = {3, 6, 3, 9, 2, 5, 9};
 static const int kVarStore[7] = {3, 12, 3, 15, 2, 5, 9};
 static const int kMaxArity = 3;
 static const int kFactorArity[14] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1, 2, 1};

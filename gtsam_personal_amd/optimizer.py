@@ -545,6 +545,79 @@ class DoglegOptimizer(LevenbergMarquardtOptimizer):
         return self.values()
 
 
+class DirectionMethod:
+    """gtsam/nonlinear/NonlinearConjugateGradientOptimizer.h:72-77"""
+    FletcherReeves = _lib.LMGPU_NCG_FLETCHER_REEVES
+    PolakRibiere = _lib.LMGPU_NCG_POLAK_RIBIERE
+    HestenesStiefel = _lib.LMGPU_NCG_HESTENES_STIEFEL
+    DaiYuan = _lib.LMGPU_NCG_DAI_YUAN
+
+
+class NonlinearConjugateGradientOptimizer(LevenbergMarquardtOptimizer):
+    """NonlinearConjugateGradientOptimizer(graph, initialValues, params, directionMethod)
+    (gtsam/nonlinear/NonlinearConjugateGradientOptimizer.h:80-132, .cpp:44-90): gradient, direction update, the golden-section line
+    search and the advance all run in liblmgpu.so (lmgpu_ncg_*), one host wait per iteration.  `params`: NonlinearOptimizerParams
+    (GaussNewtonParams here; maxIterations, the three tolerances, ordering, linearSolverType).  The optimizer eliminates nothing, so
+    the ordering only fixes the slot order (default: by key); with linearSolverType = "ITERATIVE" the handle is built without fronts,
+    which is the form for graphs whose fronts do not fit.  gradientDescent: the template's last switch (.h:200), which the reference's
+    class leaves at false."""
+
+    def __init__(self, graph, initialValues, params=None, directionMethod=DirectionMethod.PolakRibiere, ordering=None,
+                 gradientDescent=False, **kw):
+        params = params or GaussNewtonParams()
+        if directionMethod not in (DirectionMethod.FletcherReeves, DirectionMethod.PolakRibiere, DirectionMethod.HestenesStiefel,
+                                   DirectionMethod.DaiYuan):
+            raise RuntimeError("NonlinearConjugateGradientOptimizer: Invalid directionMethod")
+        if ordering is None and getattr(params, "ordering", None) is None:
+            ordering = Ordering.Natural(graph)
+        self.directionMethod, self.gradientDescent = int(directionMethod), bool(gradientDescent)
+        super().__init__(graph, initialValues, ordering, params, **kw)
+
+    def _ncg_c(self):
+        p = self.params
+        return _lib.lmgpu_ncg_params(self.directionMethod, int(self.gradientDescent), int(p.maxIterations), float(p.relativeErrorTol),
+                                     float(p.absoluteErrorTol), float(p.errorTol))
+
+    def iterate(self):
+        """.cpp:71-80: a gradient-descent step and one conjugate step from the current values; returns None like the reference
+        (it returns nullptr: the system is not linearized for the caller)"""
+        cp = self._ncg_c()
+        self._check(self.lib.lmgpu_ncg_iterate(self._h, ct.byref(cp), ct.byref(self.state)))
+        self._lin_generation = getattr(self, "_lin_generation", 0) + 1
+        return None
+
+    def optimize(self) -> Values:
+        cp = self._ncg_c()
+        self._check(self.lib.lmgpu_ncg_optimize(self._h, ct.byref(cp), ct.byref(self.state)))
+        self._lin_generation = getattr(self, "_lin_generation", 0) + 1
+        return self.values()
+
+    def gradient(self):
+        """System::gradient at the current values (.cpp:56-60): packed by slot; delta_by_key() splits it"""
+        g = np.empty(self._ntot)
+        self._check(self.lib.lmgpu_gradient(self._h, _dp(g)))
+        return g
+
+    def line_search(self, direction=None):
+        """lineSearch (.h:135-181) from the current values along `direction` (packed by slot; None: the gradient); the values stay.
+        Returns (alpha, trials)."""
+        a, n = ct.c_double(), ct.c_int32()
+        d = None if direction is None else _dp(np.ascontiguousarray(direction, dtype=np.float64))
+        self._check(self.lib.lmgpu_ncg_line_search(self._h, d, ct.byref(a), ct.byref(n)))
+        return a.value, n.value
+
+    def trace(self):
+        """per line search of the last iterate() / optimize() / line_search(): (alpha, beta, error, trials); row 0 of an iterate /
+        optimize is the uncounted gradient-descent step"""
+        n = self.lib.lmgpu_ncg_get_trace(self._h, 0, None)
+        out = np.zeros((max(n, 1), 4))
+        self.lib.lmgpu_ncg_get_trace(self._h, n, _dp(out))
+        return out[:n]
+
+    def host_waits(self):
+        return int(self.lib.lmgpu_ncg_host_waits(self._h))
+
+
 class Marginals:
     """Marginals(graph, solution, ordering): marginal covariances of single variables at `solution`
     (gtsam/nonlinear/Marginals.h; constructor Marginals.cpp:28-43: linearize the graph at the solution and eliminate it;

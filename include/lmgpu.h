@@ -319,6 +319,51 @@ int lmgpu_gnc_optimize(lmgpu_handle* h, const lmgpu_gnc_params* params, const lm
  * recorded (rows6 may be NULL; at most max_rows rows are written). */
 int lmgpu_gnc_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows6);
 
+/* ---- NonlinearConjugateGradientOptimizer (gtsam/nonlinear/NonlinearConjugateGradientOptimizer.h, .cpp) on the device-resident graph:
+ *      the one optimizer that needs no factorisation.  It works on a handle finalized for Cholesky or under LMGPU_SOLVER_PCG alike (the
+ *      selection is not read) and on every factor type, robust noise included: it uses the linearize and error launches that exist.
+ *        System::error    = graph.error                                        (.cpp:51-54)        lmgpu_error
+ *        System::gradient = graph.linearize(values)->gradientAtZero()          (.cpp:37-42, 56-60) lmgpu_gradient: -sum_f A_f^T b_f of the
+ *                           whitened, robust-reweighted [A b] of lmgpu_linearize, per scalar in a fixed order (bitwise reproducible)
+ *        System::advance  = values.retract(alpha * g)                          (.cpp:62-69)
+ *        lineSearch       golden section on [-1 / |direction|, 0], tau = 1e-5  (.h:135-181)
+ *        nonlinearConjugateGradient                                            (.h:195-289): early exit error <= errorTol; one gradient-
+ *                           descent step before the loop that is not counted; beta by enum lmgpu_ncg_direction: FletcherReeves .h:28-36,
+ *                           PolakRibiere :38-47, HestenesStiefel :49-59, DaiYuan :61-70; or direction = gradient with gradient_descent;
+ *                           direction = gradient + beta * direction; loop while ++iteration < maxIterations && !checkConvergence
+ *      The bracket of the line search lives in device memory and each trial (scaled retract, error, one-thread update rule) reads its
+ *      step there: per NCG iteration the host queues linearize, gradient, direction update, 40 trials (every kernel of a trial behind the exit
+ *      test returns at once), the final advance and its error, and waits ONCE; a search that needs more trials costs one wait per further 44,
+ *      and one that has not met the exit test after 128 trials returns LMGPU_HIP_ERROR with a message (the reference would still loop).
+ *      Refused with LMGPU_INVALID and a message: a handle with GNC enabled, a handle with a communicator (multi-rank), a call before
+ *      lmgpu_set_values.  ISAM2 is not affected.
+ *   lmgpu_gradient          gradientAtZero at the current values, lmgpu_total_dim doubles, tangent-packed by slot
+ *   lmgpu_ncg_line_search   lineSearch from the current values along dir_packed (NULL: the gradient at the current values); the handle's
+ *                           values are left unchanged.  *trials = error evaluations of the search.
+ *   lmgpu_ncg_iterate       NonlinearConjugateGradientOptimizer::iterate (.cpp:71-80): nonlinearConjugateGradient with singleIteration, i.e.
+ *                           a gradient-descent step and ONE conjugate step, started over at every call; state: error, iterations + 1
+ *   lmgpu_ncg_optimize      optimize (.cpp:82-90): the full loop; state: error, iterations = the loop's count
+ *   lmgpu_ncg_get_trace     per line search of the last of the three calls above, 4 doubles: alpha, beta (0 where the direction is the
+ *                           gradient), error after the advance (lmgpu_ncg_line_search: the best error the search saw), trials.  Row 0 of
+ *                           an iterate / optimize is the uncounted gradient-descent step.  Returns the number of rows recorded.
+ *   lmgpu_ncg_host_waits    host synchronisations of the last of those calls (the constructor-style error evaluation included) */
+enum lmgpu_ncg_direction {
+  LMGPU_NCG_FLETCHER_REEVES = 0,
+  LMGPU_NCG_POLAK_RIBIERE = 1, /* the reference's default */
+  LMGPU_NCG_HESTENES_STIEFEL = 2,
+  LMGPU_NCG_DAI_YUAN = 3
+};
+typedef struct lmgpu_ncg_params { /* NonlinearOptimizerParams defaults: 100, 1e-5, 1e-5, 0 */
+  int32_t direction_method, gradient_descent, max_iterations;
+  double relative_error_tol, absolute_error_tol, error_tol;
+} lmgpu_ncg_params;
+int lmgpu_gradient(lmgpu_handle* h, double* g_packed);
+int lmgpu_ncg_line_search(lmgpu_handle* h, const double* dir_packed, double* alpha, int32_t* trials);
+int lmgpu_ncg_iterate(lmgpu_handle* h, const lmgpu_ncg_params* p, lmgpu_lm_state* inout);
+int lmgpu_ncg_optimize(lmgpu_handle* h, const lmgpu_ncg_params* p, lmgpu_lm_state* inout);
+int lmgpu_ncg_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows4);
+int lmgpu_ncg_host_waits(const lmgpu_handle* h);
+
 /* ---- InitializePose3 (gtsam/slam/InitializePose3.h, InitializePose3.cpp, InitializePose.h): initial estimate of a 3D pose graph on the
  *      device -- chordal relaxation or the Tron-Vidal gradient iteration for the rotations, then one Gauss-Newton step for the poses.
  *      An lmgpu_init_pose3 owns two lmgpu_handles over the same slots: the ORIENTATION handle (VEC9 variables, CHORDAL_BETWEEN factors,

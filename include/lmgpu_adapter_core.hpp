@@ -211,6 +211,9 @@ class Problem {
   void optimize(const lmgpu_lm_params& p, lmgpu_lm_state* inout) { check(lmgpu_optimize(h_, &p, inout)); }
   void gnIterate(lmgpu_lm_state* inout) { check(lmgpu_gn_iterate(h_, inout)); }
   void dlIterate(lmgpu_lm_state* inout) { check(lmgpu_dl_iterate(h_, inout)); }
+  /// NonlinearConjugateGradientOptimizer::iterate / optimize (gtsam/nonlinear/NonlinearConjugateGradientOptimizer.cpp:71-90)
+  void ncgIterate(const lmgpu_ncg_params& p, lmgpu_lm_state* inout) { check(lmgpu_ncg_iterate(h_, &p, inout)); }
+  void ncgOptimize(const lmgpu_ncg_params& p, lmgpu_lm_state* inout) { check(lmgpu_ncg_optimize(h_, &p, inout)); }
 
   /// status -> exception, the mapping the reference-side adapter relies on
   void check(int rc) const {

@@ -44,6 +44,7 @@
 #include <gtsam/nonlinear/ISAM2.h>
 #include <gtsam/3rdparty/CCOLAMD/Include/ccolamd.h>
 #include <gtsam/nonlinear/LevenbergMarquardtOptimizer.h>
+#include <gtsam/nonlinear/NonlinearConjugateGradientOptimizer.h>
 #include <gtsam/nonlinear/NonlinearFactorGraph.h>
 #include <gtsam/nonlinear/PriorFactor.h>
 #include <gtsam/nonlinear/Values.h>
@@ -465,6 +466,52 @@ class GpuGaussNewtonOptimizer : public GaussNewtonOptimizer {
   lmgpu_pcg_params pcg_{};  // (declared before dev_: the constructor fills it while building dev_)
   mutable lmgpu_detail::Device dev_;
   bool discardLinear_ = false;
+};
+
+/// drop-in for NonlinearConjugateGradientOptimizer (gtsam/nonlinear/NonlinearConjugateGradientOptimizer.h:80-132, .cpp:44-90): the
+/// gradient, the direction update, the golden-section line search and the advance run on the device (lmgpu_ncg_iterate /
+/// lmgpu_ncg_optimize), one host wait per iteration.  The optimizer eliminates nothing: the ordering only fixes the slot order
+/// (params.ordering, else the keys of the Values in their order); linearSolverType = Iterative builds the handle without fronts.
+/// The direction method is honoured (the reference's constructor takes it but leaves directionMethod_ at PolakRibiere, .cpp:44-49).
+class GpuNonlinearConjugateGradientOptimizer : public NonlinearConjugateGradientOptimizer {
+ public:
+  GpuNonlinearConjugateGradientOptimizer(const NonlinearFactorGraph& graph, const Values& initial, const Parameters& params = Parameters(),
+                                         const DirectionMethod& directionMethod = DirectionMethod::PolakRibiere, int device = 0)
+      : NonlinearConjugateGradientOptimizer(graph, initial, params, directionMethod),
+        dev_(graph, initial, params.ordering ? *params.ordering : Ordering(initial.keys()), device, lmgpu_detail::pcgOf(params_, &pcg_)),
+        method_(directionMethod) {}
+
+  /// NonlinearConjugateGradientOptimizer::iterate() (.cpp:71-80): returns nullptr like the reference's
+  GaussianFactorGraph::shared_ptr iterate() override {
+    lmgpu_lm_state st{state_->error, 0.0, 0.0, (int32_t)state_->iterations, 0};
+    dev_.problem().ncgIterate(toC(), &st);
+    state_.reset(new internal::NonlinearOptimizerState(dev_.download(state_->values), st.error, (unsigned)st.iterations));
+    return nullptr;
+  }
+
+  /// NonlinearConjugateGradientOptimizer::optimize() (.cpp:82-90)
+  const Values& optimize() override {
+    lmgpu_lm_state st{state_->error, 0.0, 0.0, (int32_t)state_->iterations, 0};
+    dev_.problem().ncgOptimize(toC(), &st);
+    state_.reset(new internal::NonlinearOptimizerState(dev_.download(state_->values), st.error, (unsigned)st.iterations));
+    return state_->values;
+  }
+
+ private:
+  lmgpu_ncg_params toC() const {
+    int32_t m = LMGPU_NCG_POLAK_RIBIERE;
+    switch (method_) {
+      case DirectionMethod::FletcherReeves: m = LMGPU_NCG_FLETCHER_REEVES; break;
+      case DirectionMethod::PolakRibiere: m = LMGPU_NCG_POLAK_RIBIERE; break;
+      case DirectionMethod::HestenesStiefel: m = LMGPU_NCG_HESTENES_STIEFEL; break;
+      case DirectionMethod::DaiYuan: m = LMGPU_NCG_DAI_YUAN; break;
+    }
+    return lmgpu_ncg_params{m, 0, (int32_t)params_.maxIterations, params_.relativeErrorTol, params_.absoluteErrorTol, params_.errorTol};
+  }
+
+  lmgpu_pcg_params pcg_{};  // (declared before dev_: the constructor fills it while building dev_)
+  mutable lmgpu_detail::Device dev_;
+  DirectionMethod method_;
 };
 
 /// DoglegOptimizer's state type (internal::DoglegState) is private to DoglegOptimizer.cpp:54-62, so a subclass cannot replace
