@@ -50,9 +50,9 @@ struct Mat {
   double operator()(int i, int j) const { return a[(size_t)j * r + i]; }
 };
 
-enum VarType { POSE2 = 0, POSE3 = 1, POINT3 = 2, CAM_BUNDLER = 3, POINT2 = 4, CAL3_S2 = 5 };
-static const int kVarDim[6] = {3, 6, 3, 9, 2, 5};
-static const int kVarStore[6] = {3, 12, 3, 17, 2, 5};  // packed value doubles (oracle keeps u0,v0 with the camera); CAL3_S2 = (fx, fy, s, u0, v0)
+enum VarType { POSE2 = 0, POSE3 = 1, POINT3 = 2, CAM_BUNDLER = 3, POINT2 = 4, CAL3_S2 = 5, VEC9 = 6 };
+static const int kVarDim[7] = {3, 6, 3, 9, 2, 5, 9};
+static const int kVarStore[7] = {3, 12, 3, 17, 2, 5, 9};  // packed value doubles (oracle keeps u0,v0 with the camera); CAL3_S2 = (fx, fy, s, u0, v0)
 
 enum FactorType {
   F_SFM = 0,            // GeneralSFMFactor<PinholeCamera<Cal3Bundler>,Point3>  (cam, point), meas 2
@@ -66,12 +66,14 @@ enum FactorType {
   F_PROJECTION_BPS = 8, // the same with body_P_sensor: meas 2 + K 5 + sensor pose (R row-major 9, t 3)
   F_BEARING_RANGE_2D = 9,  // BearingRangeFactor<Pose2,Point2>  (pose, landmark), meas 2 (bearing angle, range)
   F_SFM2 = 10,             // GeneralSFMFactor2<Cal3_S2>  (pose, point, calibration), meas 2   gtsam/slam/GeneralSFMFactor.h:208-262
-  F_PRIOR_CAL3_S2 = 11     // PriorFactor<Cal3_S2>  meas 5 (fx, fy, s, u0, v0)
+  F_PRIOR_CAL3_S2 = 11,    // PriorFactor<Cal3_S2>  meas 5 (fx, fy, s, u0, v0)
+  F_CHORDAL_BETWEEN = 12,  // the JacobianFactor [-I9 | blockdiag(Rij, Rij, Rij)] of InitializePose3's relaxation, meas 9 (Rij row-major)
+  F_PRIOR_VEC9 = 13        // [I9 | b], meas 9 (b)
 };
-static const int kNumFactorTypes = 12;
-static const int kFactorArity[12] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1};
-static const int kFactorRows[12] = {2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5};
-static const int kFactorMeas[12] = {2, 3, 12, 3, 12, 3, 17, 7, 19, 2, 2, 5};
+static const int kNumFactorTypes = 14;
+static const int kFactorArity[14] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1, 2, 1};
+static const int kFactorRows[14] = {2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5, 9, 9};
+static const int kFactorMeas[14] = {2, 3, 12, 3, 12, 3, 17, 7, 19, 2, 2, 5, 9, 9};
 
 enum NoiseKind { N_UNIT = 0, N_ISO = 1, N_DIAG = 2, N_GAUSS = 3 };
 
@@ -166,6 +168,9 @@ static Value retract(const Value& x, const double* d) {
     case CAL3_S2:  // Cal3_S2::retract gtsam/geometry/Cal3_S2.h:113-115: Cal3_S2(vector() + d)
       for (int i = 0; i < 5; i++) r.v[i] = x.v[i] + d[i];
       break;
+    case VEC9:  // a vector space
+      for (int i = 0; i < 9; i++) r.v[i] = x.v[i] + d[i];
+      break;
     case CAM_BUNDLER: {
       // PinholeCamera::retract gtsam/geometry/PinholeCamera.h:197-203; Cal3Bundler.h:134-136
       store_pose3(pose3_retract(as_pose3(x.v), d), r.v);
@@ -218,6 +223,34 @@ static void evaluate_error(const Factor& f, const Values& vals, double* e, doubl
       }
       e[0] = fx * pn[0] + s * pn[1] + u0 - f.meas[0];
       e[1] = fy * pn[1] + v0 - f.meas[1];
+      return;
+    }
+    case F_CHORDAL_BETWEEN: {
+      // gtsam/slam/InitializePose3.cpp:56-62 as a factor on 9-vectors: e = blockdiag(Rij, Rij, Rij) x2 - x1 (linear, b = 0)
+      const Value& a = vals.at(f.keys[0]);
+      const Value& b = vals.at(f.keys[1]);
+      for (int k = 0; k < 3; k++)
+        for (int i = 0; i < 3; i++)
+          e[3 * k + i] = f.meas[3 * i] * b.v[3 * k] + f.meas[3 * i + 1] * b.v[3 * k + 1] + f.meas[3 * i + 2] * b.v[3 * k + 2] - a.v[3 * k + i];
+      if (H1) {
+        std::memset(H1, 0, 81 * sizeof(double));
+        for (int i = 0; i < 9; i++) H1[10 * i] = -1.0;
+      }
+      if (H2) {
+        std::memset(H2, 0, 81 * sizeof(double));
+        for (int k = 0; k < 3; k++)
+          for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) H2[9 * (3 * k + i) + 3 * k + j] = f.meas[3 * i + j];
+      }
+      return;
+    }
+    case F_PRIOR_VEC9: {
+      const Value& a = vals.at(f.keys[0]);
+      for (int i = 0; i < 9; i++) e[i] = a.v[i] - f.meas[i];
+      if (H1) {
+        std::memset(H1, 0, 81 * sizeof(double));
+        for (int i = 0; i < 9; i++) H1[10 * i] = 1.0;
+      }
       return;
     }
     case F_PRIOR_CAL3_S2: {
@@ -528,7 +561,7 @@ static GFactor linearize_factor(const Factor& f, const Values& vals) {
     g.dims.push_back(kVarDim[vals.at(f.keys[j]).type]);
     tot += g.dims.back();
   }
-  double e[9], H1[81], H2[54], H3[10];
+  double e[9], H1[81], H2[81], H3[10];
   evaluate_error(f, vals, e, H1, ar > 1 ? H2 : nullptr, ar > 2 ? H3 : nullptr);
   g.Ab = Mat(m, tot + 1);
   for (int i = 0; i < m; i++) {
@@ -1377,7 +1410,7 @@ void orc_destroy(void* h) { delete (Problem*)h; }
 
 int orc_add_variable(void* h, uint64_t key, int type, const double* value) {
   auto* p = (Problem*)h;
-  if (type < 0 || type > 5) return 2;
+  if (type < 0 || type > 6) return 2;
   Value v;
   v.type = type;
   std::memset(v.v, 0, sizeof(v.v));
@@ -1971,7 +2004,7 @@ void orc_isam2_set_partial_check(void* h, int enable) { ((ISAM2Handle*)h)->S.ena
 
 int orc_isam2_add_variable(void* h, uint64_t key, int type, const double* value) {
   auto& S = ((ISAM2Handle*)h)->S;
-  if (type < 0 || type > 5) return 2;
+  if (type < 0 || type > 6) return 2;
   Value v;
   v.type = type;
   std::memset(v.v, 0, sizeof(v.v));
