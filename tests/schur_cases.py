@@ -356,11 +356,12 @@ def var_dims(c):
     return {k: VAR_DIM[c["initial"].type(k)] for k in c["ordering"]}
 
 
-def reference(c, jacobians, fronts, lam, diagonal):
-    """the dense extended-precision reference of case c from whitened Jacobians [Ab of factor g] and [(front keys, n frontal keys)]"""
+def reference(c, jacobians, fronts, lam, diagonal, block=0):
+    """the dense extended-precision reference of case c from whitened Jacobians [Ab of factor g] and [(front keys, n frontal keys)];
+    block: dense_reference's row-at-a-time form (0) or its blocked one (panel rows)"""
     from dense_reference import DenseReference
     fk = c["graph"].factor_keys_in_graph_order()
-    return DenseReference(list(zip(fk, jacobians)), var_dims(c), lam, diagonal, fronts)
+    return DenseReference(list(zip(fk, jacobians)), var_dims(c), lam, diagonal, fronts, block=block)
 
 
 def deviations(ref, rsd_of_front, delta_by_key):
@@ -377,22 +378,29 @@ def deviations(ref, rsd_of_front, delta_by_key):
     return per_front, float(np.sqrt(((a - b) ** 2).sum() / (b ** 2).sum()))
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_floor(name):
-    """the float64 oracle against the reference built from the oracle's own Jacobians, over DAMPINGS: dict(rsd = largest per-front
-    deviation, delta = largest delta deviation, residual = largest reference residual, detail = [(lam, diagonal, rsd, delta)])"""
+def floor_of(c, dampings, block=0, keep=None):
+    """the float64 oracle against the reference built from the oracle's own Jacobians, over `dampings`: dict(rsd = largest per-front
+    deviation, delta = largest delta deviation, residual = largest reference residual, detail = [(lam, diagonal, rsd, delta)]).
+    keep: a list that receives (reference, oracle cliques, oracle delta) of every damping"""
     import oracle_harness as oh
-    c = case(name)
     orc = oh.OracleProblem(c["graph"], c["initial"], c["ordering"])
     orc.linearize()
     jac = [orc.jacobian(g) for g in range(c["graph"].size())]
     out = dict(rsd=0.0, delta=0.0, residual=0.0, detail=[])
-    for lam, diagonal in DAMPINGS:
+    for lam, diagonal in dampings:
         rc, delta, _, _ = orc.solve(lam, diagonal)
-        assert rc == 0, (name, lam)
+        assert rc == 0, lam
         cl = orc.cliques()
-        ref = reference(c, jac, [(keys, nfk) for keys, nfk, _, _ in cl], lam, diagonal)
+        ref = reference(c, jac, [(keys, nfk) for keys, nfk, _, _ in cl], lam, diagonal, block)
         per_front, dd = deviations(ref, lambda i: cl[i][2], delta)
         out["detail"].append((lam, diagonal, max(per_front), dd))
         out["rsd"], out["delta"], out["residual"] = max(out["rsd"], max(per_front)), max(out["delta"], dd), max(out["residual"], ref.residual)
+        if keep is not None:
+            keep.append((ref, cl, delta))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_floor(name):
+    """floor_of the case `name` over DAMPINGS, with the row-at-a-time reference"""
+    return floor_of(case(name), DAMPINGS)
