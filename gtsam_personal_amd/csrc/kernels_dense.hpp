@@ -12,6 +12,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "kernels_front.hpp"
 
 namespace lmgpu {
@@ -131,11 +133,25 @@ __device__ __forceinline__ void glds_row(const double* g, double* lds_row) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_row, 16, 0, 0);
 }
 
+// One element of C, in the flavour the tile's hand-off needs.  WT = false: a plain store (the tile ends at a kernel boundary, or its
+// workgroup publishes it behind a release fence).  WT = true: write-through -- an agent-scope relaxed atomic store, emitted as
+// global_store_dwordx2 ... sc1 -- for a tile that another workgroup of the SAME launch reads next and that is published without a
+// release fence (pdf_publish_wt, kernels_potrf.hpp).  The value stored is the same either way.
+template <bool WT>
+__device__ __forceinline__ void store_c(double* p, double v) {
+  if constexpr (WT)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    *p = v;
+}
+
 // Sadd != nullptr (multi-rank, rows of the next panel): the tile also receives its so far separate assembled contributions,
 // C += Sadd - P^T P (same layout as A)
-template <bool HAS_S = false>
+// WT_OPT: the caller may ask for write-through C stores with `wt` (wave-uniform; see store_c); without WT_OPT only the plain epilogue exists
+template <bool HAS_S = false, bool WT_OPT = false>
 __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int ld, int n, int p0, int kp, int r0, int r1, int ti, int tj,
-                                          double* sm /* [2 stages][2 operands][SYRK_KC][SYRK_LDW] */, const double* __restrict__ Sadd = nullptr) {
+                                          double* sm /* [2 stages][2 operands][SYRK_KC][SYRK_LDW] */, const double* __restrict__ Sadd = nullptr,
+                                          bool wt = false) {
   if (tj < ti) return;
   const int it0 = r0 + ti * 128, jt0 = r0 + tj * 128;  // tile origins
   if (it0 >= r1 || jt0 >= n) return;
@@ -197,49 +213,60 @@ __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int ld, int n,
   // chain per element would put 64 memory round trips behind every tile).
   const int i0 = it0 + wr * 64, j0 = jt0 + wc * 64;
   const bool full = (i0 + 64 <= r1) && (j0 + 64 <= n) && (j0 >= i0 + 63);  // wave-uniform: every element valid
-  if (full) {
+  auto epilogue = [&](auto flavour) {
+    constexpr bool WT = decltype(flavour)::value;
+    if (full) {
 #pragma unroll
-    for (int a = 0; a < 4; a++) {
-      double c[4][4];
+      for (int a = 0; a < 4; a++) {
+        double c[4][4];
 #pragma unroll
-      for (int b = 0; b < 4; b++)
+        for (int b = 0; b < 4; b++)
 #pragma unroll
-        for (int r = 0; r < 4; r++) c[b][r] = A[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc];
-      if constexpr (HAS_S) {
-        if (Sadd) {
+          for (int r = 0; r < 4; r++) c[b][r] = A[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc];
+        if constexpr (HAS_S) {
+          if (Sadd) {
 #pragma unroll
-          for (int b = 0; b < 4; b++)
+            for (int b = 0; b < 4; b++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) c[b][r] += Sadd[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc];
-        }
-      }
-#pragma unroll
-      for (int b = 0; b < 4; b++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) A[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc] = c[b][r] - acc[a][b][r];
-    }
-  } else {
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-      double c[4][4];
-#pragma unroll
-      for (int b = 0; b < 4; b++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {  // clamped (always mapped) address; the value is only used where valid
-          const int row = min(i0 + a * 16 + kk + 4 * r, r1 - 1), col = min(j0 + b * 16 + cc, n - 1);
-          c[b][r] = A[(size_t)row * ld + col];
-          if constexpr (HAS_S) {
-            if (Sadd) c[b][r] += Sadd[(size_t)row * ld + col];
+              for (int r = 0; r < 4; r++) c[b][r] += Sadd[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc];
           }
         }
 #pragma unroll
-      for (int b = 0; b < 4; b++)
+        for (int b = 0; b < 4; b++)
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int row = i0 + a * 16 + kk + 4 * r, col = j0 + b * 16 + cc;
-          if (row < r1 && col < n && col >= row) A[(size_t)row * ld + col] = c[b][r] - acc[a][b][r];
-        }
+          for (int r = 0; r < 4; r++) store_c<WT>(&A[(size_t)(i0 + a * 16 + kk + 4 * r) * ld + j0 + b * 16 + cc], c[b][r] - acc[a][b][r]);
+      }
+    } else {
+#pragma unroll
+      for (int a = 0; a < 4; a++) {
+        double c[4][4];
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {  // clamped (always mapped) address; the value is only used where valid
+            const int row = min(i0 + a * 16 + kk + 4 * r, r1 - 1), col = min(j0 + b * 16 + cc, n - 1);
+            c[b][r] = A[(size_t)row * ld + col];
+            if constexpr (HAS_S) {
+              if (Sadd) c[b][r] += Sadd[(size_t)row * ld + col];
+            }
+          }
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int row = i0 + a * 16 + kk + 4 * r, col = j0 + b * 16 + cc;
+            if (row < r1 && col < n && col >= row) store_c<WT>(&A[(size_t)row * ld + col], c[b][r] - acc[a][b][r]);
+          }
+      }
     }
+  };
+  if constexpr (WT_OPT) {
+    if (wt)
+      epilogue(std::true_type{});
+    else
+      epilogue(std::false_type{});
+  } else {
+    epilogue(std::false_type{});
   }
 }
 

@@ -491,6 +491,7 @@ __global__ __launch_bounds__(256) void front_tail_kernel(double* __restrict__ A,
 // barrier, ONE lane: agent-scope release fence, wait, relaxed agent-scope flag store / add; consumer: ONE lane polls
 // relaxed, ONE agent-scope acquire fence, wait, workgroup barrier, then plain vector loads.  Logical workgroup ids come
 // from a ticket counter, so a workgroup only ever waits for workgroups that started before it (no dispatch-order assumption).
+// (The tile roles of a fused / chained step publish differently -- write-through stores, no release fence: pdf_publish_wt below.)
 // flags (zeroed by the host before the launch): [0] ticket, [4 + j] diag_ready[j], [8 + 4 i + j] tile_ready[i][j],
 // [PDF_TA0 + sj] number of finished trailing-update workgroups of column strip sj in the next panel's rows (fused step only).
 // development aid (tools/microbench.hip defines it): wave 0 lane 0 of the diagonal workgroups stores s_memtime at the phase boundaries
@@ -565,13 +566,21 @@ __device__ __forceinline__ bool pdf_wait3(const unsigned int* f0, unsigned int n
   return *s_ok != 0;
 }
 
+// development aid (tools/microbench.hip defines them): the signaller's ticks inside the release fence, per workgroup
+#ifndef PDF_PROF_FENCE_BEGIN
+#define PDF_PROF_FENCE_BEGIN()
+#define PDF_PROF_FENCE_END()
+#endif
+
 // every wave calls this after its last store of the payload; `signaller` = the one thread that raises the flag
 __device__ __forceinline__ void pdf_publish(unsigned int* flag, bool signaller) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (signaller) {
+    PDF_PROF_FENCE_BEGIN();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    PDF_PROF_FENCE_END();
     __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -581,8 +590,32 @@ __device__ __forceinline__ void pdf_publish2(unsigned int* flag0, unsigned int* 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (signaller) {
+    PDF_PROF_FENCE_BEGIN();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    PDF_PROF_FENCE_END();
+    __hip_atomic_fetch_add(flag0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (flag1) __hip_atomic_fetch_add(flag1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Publish forms for a payload that was stored WRITE-THROUGH (every store of it an agent-scope relaxed atomic store, which the
+// compiler emits with the sc1 bit: the bytes go to memory past this XCD's L2 and the line leaves it).  Such a payload needs no
+// release fence -- on gfx950 the fence writes back EVERY dirty line of the XCD's L2, not only this workgroup's -- only: every
+// storing wave drains its stores, workgroup barrier, ONE lane adds to the flag (cdna_hip_programming.md Guideline 16, form R1).
+// The consumer side is unchanged (pdf_wait / pdf_wait3: relaxed poll, one agent-scope acquire, barrier, plain loads).
+// Used by the tile roles of a fused / chained step (kernels_step.hpp), whose 2-128 KB of C are read next by one other workgroup a
+// step or two later; the panel roles keep plain stores + release fence, their payload is re-read from the L2 by hundreds of tiles.
+__device__ __forceinline__ void pdf_publish_wt(unsigned int* flag, bool signaller) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (signaller) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void pdf_publish2_wt(unsigned int* flag0, unsigned int* flag1, bool signaller) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (signaller) {
     __hip_atomic_fetch_add(flag0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (flag1) __hip_atomic_fetch_add(flag1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

@@ -6,7 +6,8 @@
 // of the trailing update (look-ahead without a second stream); the row-panel workgroups finish the panel.
 // step_kernel = one step per launch.  chain_kernel = all fused steps of a front in one launch, ticket order from
 // chain_schedule (host, below) -- see the comment there for what the order buys.  front_tail_kernel (kernels_potrf.hpp) ends the
-// front when the remainder is small.  Every inter-workgroup hand-off is the release/acquire protocol of kernels_potrf.hpp.
+// front when the remainder is small.  Every inter-workgroup hand-off is the release/acquire protocol of kernels_potrf.hpp: the panel
+// roles publish plain stores behind a release fence, the tile roles publish write-through stores without one; every consumer acquires.
 #pragma once
 #include "kernels_dense.hpp"
 #include "kernels_potrf.hpp"
@@ -15,8 +16,15 @@
 #ifndef CHAIN_PROF_BEGIN
 #define CHAIN_PROF_BEGIN()
 #define CHAIN_PROF_WAITED()
+#define CHAIN_PROF_STORED()
 #define CHAIN_PROF_END(cls)
 #endif
+
+// How the tile roles of a step hand their C tile to the workgroup that reads it next (kernels_potrf.hpp, pdf_publish_wt): write-through
+// stores and a flag add with no release fence.  The test library also keeps the form this replaced -- plain stores behind a release
+// fence -- and a consumer that has the tile's lines in its L1 before it waits; the product library compiles neither.
+#define CHAIN_FORM_FENCED_TILES 1  // dev_forms bit, LMGPU_CHAIN_FENCED_TILES
+#define CHAIN_FORM_PREREAD 2       // dev_forms bit, LMGPU_CHAIN_PREREAD
 
 namespace lmgpu {
 
@@ -30,6 +38,9 @@ struct StepArgs {
   double* inv16;
   unsigned int* flags;
   const double* S;  // != nullptr: partial-assembly buffer (same layout as A) whose rows r0 .. r0+255 are folded in by this launch
+#ifdef LMGPU_TEST_HOOKS
+  int dev_forms = 0;  // CHAIN_FORM_* (wave-uniform)
+#endif
 };
 
 // 64x64 tile of the trailing update for the rows of the NEXT panel (the head of the dependency chain): four waves, 32x32 each,
@@ -107,8 +118,9 @@ __device__ __forceinline__ void syrk_subtile64(double* __restrict__ A, int ld, i
 // The sub-tiles of column strips 0..3 feed the diagonal workgroups (the head of the launch's dependency chain) and are cut once
 // more: one workgroup per 32x32 quadrant, one 16x16 MFMA tile per wave, i.e. 64 dependent MFMAs per wave at K = 256 instead of
 // 256 (in-kernel timestamps: the first potrf waited 22-40 us for its 64x64 sub-tile, MFMA-bound on SIMDs shared with update tiles).
+// wt (wave-uniform): write-through C stores (kernels_dense.hpp, store_c)
 __device__ __forceinline__ void syrk_quadrant32(double* __restrict__ A, int ld, int n, int p0, int kp, int r0, int si, int sj, int qd,
-                                                const double* __restrict__ Sadd) {
+                                                const double* __restrict__ Sadd, bool wt = false) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kk = lane >> 4, cc = lane & 15;
   const int wr = wave >> 1, wc = wave & 1, qr = qd >> 1, qc = qd & 1;
   if (si == sj && (qr > qc || (qr == qc && wr > wc))) return;
@@ -147,10 +159,18 @@ __device__ __forceinline__ void syrk_quadrant32(double* __restrict__ A, int ld, 
       }
     }
   }
+  if (wt) {
 #pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int row = i0 + kk + 4 * r, col = j0 + cc;
-    if (row < n && col < n && col >= row) A[(size_t)row * ld + col] = cur[r] + acc[r];
+    for (int r = 0; r < 4; r++) {
+      const int row = i0 + kk + 4 * r, col = j0 + cc;
+      if (row < n && col < n && col >= row) store_c<true>(&A[(size_t)row * ld + col], cur[r] + acc[r]);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = i0 + kk + 4 * r, col = j0 + cc;
+      if (row < n && col < n && col >= row) A[(size_t)row * ld + col] = cur[r] + acc[r];
+    }
   }
 }
 
@@ -196,8 +216,26 @@ __device__ __forceinline__ bool chain_wait_tile(const ChainLink& c, int T, int S
                    threadIdx.x);
 }
 
+#ifdef LMGPU_TEST_HOOKS
+// CHAIN_FORM_PREREAD: before it waits for its inputs, a tile role plain-loads the first row of every 16-row group of the rows x cols
+// block of C at (i0, j0) it is about to update, so that its CU's L1 holds the bytes of BEFORE the hand-off when the hand-off happens
+// (a consumer whose loads were not behind the acquire would then compute with them).  The values are discarded.
+__device__ __forceinline__ void chain_preread(const double* A, int ld, int n, int i0, int j0, int rows, int cols) {
+  for (int idx = threadIdx.x; idx < (rows >> 4) * cols; idx += 256) {
+    const int row = min(i0 + 16 * (idx / cols), n - 1), col = min(j0 + idx % cols, n - 1);
+    const double v = A[(size_t)row * ld + col];
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"(v) : "memory");
+  }
+}
+#endif
+
 // the work of logical workgroup t of one step
 __device__ __forceinline__ void step_body(const StepArgs& a, int t, const ChainLink& c, double* sm, int* s_ok) {
+#ifdef LMGPU_TEST_HOOKS
+  const bool wt_tiles = !(a.dev_forms & CHAIN_FORM_FENCED_TILES), preread = (a.dev_forms & CHAIN_FORM_PREREAD) != 0;
+#else
+  constexpr bool wt_tiles = true;
+#endif
   const int r0 = a.p0 + a.kp, m = a.n - r0;
   const int T = (m + 127) >> 7;  // tile rows = tile columns of the trailing matrix
   const bool next = a.kb_next > 0;
@@ -214,21 +252,36 @@ __device__ __forceinline__ void step_body(const StepArgs& a, int t, const ChainL
     const int sj = (u >= 6) ? 3 : ((u >= 3) ? 2 : (u >= 1 ? 1 : 0));
     const int si = u - sj * (sj + 1) / 2;
     __builtin_amdgcn_s_setprio(2);
+#ifdef LMGPU_TEST_HOOKS
+    if (preread) chain_preread(a.A, a.ld, a.n, r0 + 64 * si + 32 * ((t & 3) >> 1), r0 + 64 * sj + 32 * (t & 1), 32, 32);
+#endif
     const bool ok = chain_wait_tile(c, T, S, si >> 1, sj >> 1, s_ok);
     CHAIN_PROF_WAITED();
     if (!ok && threadIdx.x == 0) atomicExch(a.status + 1, 1 + a.front_id);  // hand-off timed out: a fault, reported apart from pivot failures
-    syrk_quadrant32(a.A, a.ld, a.n, a.p0, a.kp, r0, si, sj, t & 3, a.S);
-    pdf_publish(&a.flags[PDF_TA0 + sj], threadIdx.x == 0);
+    syrk_quadrant32(a.A, a.ld, a.n, a.p0, a.kp, r0, si, sj, t & 3, a.S, wt_tiles);
+    CHAIN_PROF_STORED();
+    if (wt_tiles)
+      pdf_publish_wt(&a.flags[PDF_TA0 + sj], threadIdx.x == 0);
+    else
+      pdf_publish(&a.flags[PDF_TA0 + sj], threadIdx.x == 0);
     CHAIN_PROF_END(0);
     return;
   }
   if (t < nTA) {  // the rest of the next panel's rows: tile rows 0 and 1, tile columns 2 ..
     const int u = t - nHead, ti = u & 1, tj = 2 + (u >> 1);
+#ifdef LMGPU_TEST_HOOKS
+    if (preread) chain_preread(a.A, a.ld, a.n, r0 + 128 * ti, r0 + 128 * tj, 128, 128);
+#endif
     const bool ok = chain_wait_tile(c, T, S, ti, tj, s_ok);
     CHAIN_PROF_WAITED();
     if (!ok && threadIdx.x == 0) atomicExch(a.status + 1, 1 + a.front_id);
-    syrk_tile<true>(a.A, a.ld, a.n, a.p0, a.kp, r0, a.n, ti, tj, sm, a.S);
-    pdf_publish2(&a.flags[PDF_TA0 + 2 * tj], 2 * tj + 1 < S ? &a.flags[PDF_TA0 + 2 * tj + 1] : nullptr, threadIdx.x == 0);
+    syrk_tile<true, true>(a.A, a.ld, a.n, a.p0, a.kp, r0, a.n, ti, tj, sm, a.S, wt_tiles);
+    CHAIN_PROF_STORED();
+    unsigned int* const strip1 = 2 * tj + 1 < S ? &a.flags[PDF_TA0 + 2 * tj + 1] : nullptr;
+    if (wt_tiles)
+      pdf_publish2_wt(&a.flags[PDF_TA0 + 2 * tj], strip1, threadIdx.x == 0);
+    else
+      pdf_publish2(&a.flags[PDF_TA0 + 2 * tj], strip1, threadIdx.x == 0);
     CHAIN_PROF_END(1);
     return;
   }
@@ -247,14 +300,27 @@ __device__ __forceinline__ void step_body(const StepArgs& a, int t, const ChainL
       ti++;
     }
     const int tj = ti + rem;
+#ifdef LMGPU_TEST_HOOKS
+    if (preread) chain_preread(a.A, a.ld, a.n, r0 + 128 * ti, r0 + 128 * tj, 128, 128);
+#endif
     const bool ok = chain_wait_tile(c, T, S, ti, tj, s_ok);
     CHAIN_PROF_WAITED();
     if (!ok && threadIdx.x == 0) atomicExch(a.status + 1, 1 + a.front_id);  // hand-off timed out: a fault, reported apart from pivot failures
+    // a tile that a later step of this launch continues is handed over write-through; one that ends at the kernel boundary (a step
+    // launched on its own, the last step of a chain) is stored plainly and stays in the L2 for the next launch
+    const bool wt = c.publish && wt_tiles;
     if (c.merged)
-      syrk_tile(a.A, a.ld, a.n, a.p0 - 256, a.kp + 256, r0, a.n, ti, tj, sm);  // panels i - 1 and i are consecutive rows: one operand slab of depth 512
+      syrk_tile<false, true>(a.A, a.ld, a.n, a.p0 - 256, a.kp + 256, r0, a.n, ti, tj, sm, nullptr, wt);  // panels i - 1 and i are consecutive rows: one operand slab of depth 512
     else
-      syrk_tile(a.A, a.ld, a.n, a.p0, a.kp, r0, a.n, ti, tj, sm);
-    if (c.publish) pdf_publish(&a.flags[PDF_TD0 + ti * T - ti * (ti - 1) / 2 + (tj - ti)], threadIdx.x == 0);
+      syrk_tile<false, true>(a.A, a.ld, a.n, a.p0, a.kp, r0, a.n, ti, tj, sm, nullptr, wt);
+    CHAIN_PROF_STORED();
+    if (c.publish) {
+      unsigned int* const done = &a.flags[PDF_TD0 + ti * T - ti * (ti - 1) / 2 + (tj - ti)];
+      if (wt_tiles)
+        pdf_publish_wt(done, threadIdx.x == 0);
+      else
+        pdf_publish(done, threadIdx.x == 0);
+    }
     CHAIN_PROF_END(3);
     return;
   }
@@ -302,6 +368,9 @@ struct ChainArgs {
   const int2* tasks;    // (step - i0, logical workgroup of that step) per ticket
   const double* S;      // multi-rank: the partial-assembly buffer (summed over the ranks for every row chunk this launch touches: the host
                         // waits for those chunks' events before the launch) whose rows the head tiles fold in; else nullptr
+#ifdef LMGPU_TEST_HOOKS
+  int dev_forms = 0;  // CHAIN_FORM_* (wave-uniform)
+#endif
 };
 
 __global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs ca) {
@@ -316,6 +385,9 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs ca) {
   const int kbn = min(ca.nf, (i + 2) * 256) - (i + 1) * 256;
   StepArgs a{ca.A, ca.ld, ca.n, ca.nf, 256 * i, 256, kbn, ca.front_id, ca.status, ca.inv16 + (size_t)(i + 1) * 4096,
              ca.flags + (size_t)(i + 1) * PDF_FLAG_WORDS, ca.S};
+#ifdef LMGPU_TEST_HOOKS
+  a.dev_forms = ca.dev_forms;
+#endif
   const ChainLink c{s > 0 ? ca.flags + (size_t)i * PDF_FLAG_WORDS : nullptr, s + 1 < ca.nsteps, merged,
                     (merged && s > 1) ? ca.flags + (size_t)(i - 1) * PDF_FLAG_WORDS : nullptr};
   step_body(a, task.y, c, sm, &s_ok);

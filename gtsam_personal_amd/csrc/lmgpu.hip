@@ -271,6 +271,7 @@ struct lmgpu_handle {
   bool bsd_ticket = false;                     // LMGPU_BSD_TICKET=1: the block back-substitution always draws tickets (tests: the path of levels with more blocks than CUs)
   bool no_tail = false;                        // LMGPU_NO_TAIL=1: the end of a front as separate update / panel launches (A/B)
   bool no_chain = false;                       // LMGPU_NO_CHAIN=1: one launch per fused step instead of one per run of steps (A/B)
+  int chain_forms = 0;                         // test library: CHAIN_FORM_* bits (LMGPU_CHAIN_FENCED_TILES, LMGPU_CHAIN_PREREAD; kernels_step.hpp)
   unsigned int* d_pflags = nullptr;            // hand-off flags of panel_dataflow_kernel, PDF_FLAG_WORDS per outer panel
   int pflags_panels = 0;
   unsigned int* bs_flags = nullptr;
@@ -1018,6 +1019,9 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
               if (rcw) return rcw;
             }
             ChainArgs ca{A, ld, F.n, F.nf, cp.i0, cp.nsteps, F.id, h->d_status, h->inv16, h->d_pflags, cp.d_tasks, split ? (const double*)Asm : nullptr};
+#ifdef LMGPU_TEST_HOOKS
+            ca.dev_forms = h->chain_forms;
+#endif
             const int ktc = h->kt.begin(LMGPU_KT_CHAIN, s);
             hipLaunchKernelGGL(chain_kernel, dim3(cp.ntasks), dim3(256), STEP_LDS_BYTES, s, ca);
             h->kt.end(ktc, s, cp.flop, 1);
@@ -1053,6 +1057,9 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
           const int kbn = rows_of(i + 1);
           StepArgs a{A, ld, F.n, F.nf, k0, kb, kbn, F.id, h->d_status, h->inv16 + (size_t)(i + 1) * 4096, h->d_pflags + (size_t)(i + 1) * PDF_FLAG_WORDS,
                      fold_in_step ? (const double*)Asm : nullptr};
+#ifdef LMGPU_TEST_HOOKS
+          a.dev_forms = h->chain_forms;
+#endif
           const int grid = step_grid(m, kbn);
           if (run_launches == 0) kt_run = h->kt.begin(LMGPU_KT_SYRK, s);
           hipLaunchKernelGGL(step_kernel, dim3(grid), dim3(256), STEP_LDS_BYTES, s, a);
@@ -1971,6 +1978,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   h->two_launch_panel = dev_switch("LMGPU_PANEL_2L") != nullptr;
   h->no_fuse = dev_switch("LMGPU_NO_FUSE") != nullptr;
   h->no_chain = dev_switch("LMGPU_NO_CHAIN") != nullptr;
+  h->chain_forms = (dev_switch("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (dev_switch("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
   h->no_tail = dev_switch("LMGPU_NO_TAIL") != nullptr;
   h->no_wide16 = dev_switch("LMGPU_NO_WIDE16") != nullptr;
   if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) h->wide16_max = atoi(e);

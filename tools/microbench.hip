@@ -1,6 +1,8 @@
 // Development microbenchmark (not part of the product): times the dense-front kernels on a synthetic SPD matrix and
 // (trailing-update tile at several sizes).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../gtsam_personal_amd/csrc tools/microbench.hip -o tools/microbench
+// With -DLMGPU_TEST_HOOKS the kernels carry the test library's hand-off forms as well and   microbench <n> <far_pct> <merge> <forms>
+// selects them for the chained launch (CHAIN_FORM_* bits of kernels_step.hpp: 1 = tiles published behind a release fence).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,7 +22,10 @@
   } while (0)
 // where the workgroups of a chained launch spend their time: per class (head quadrants, head 64-tiles, diagonal, update tiles, row-panel)
 // [count, ticks waiting for inputs, ticks working] + slot-time per 100 us bucket of the launch (100 MHz realtime counter)
+// + the publish segment per class: g_pub[3 cls] = workgroups with a stamp, [3 cls + 1] = ticks from thread 0's last C store to the end
+// of the publish; g_fence[3 cls] = release fences, [3 cls + 1] = the signaller's ticks inside them (fence + its wait)
 __device__ unsigned long long g_prof[16], g_hist[256], g_t0, g_begin[1 << 17], g_waited[1 << 17];
+__device__ unsigned long long g_pub[16], g_fence[16], g_stored[1 << 17], g_fence_n[1 << 17], g_fence_t[1 << 17], g_fence_b[1 << 17];
 __device__ __forceinline__ unsigned long long prof_now() {
   unsigned long long t_;
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");
@@ -31,12 +36,26 @@ __device__ __forceinline__ unsigned long long prof_now() {
     if (threadIdx.x == 0) {                                 \
       g_begin[blockIdx.x] = prof_now();                     \
       g_waited[blockIdx.x] = 0;                             \
+      g_stored[blockIdx.x] = 0;                             \
+      g_fence_n[blockIdx.x] = 0;                            \
+      g_fence_t[blockIdx.x] = 0;                            \
       atomicMin(&g_t0, g_begin[blockIdx.x]);                \
     }                                                       \
   } while (0)
 #define CHAIN_PROF_WAITED()                                 \
   do {                                                      \
     if (threadIdx.x == 0) g_waited[blockIdx.x] = prof_now(); \
+  } while (0)
+#define CHAIN_PROF_STORED()                                 \
+  do {                                                      \
+    if (threadIdx.x == 0) g_stored[blockIdx.x] = prof_now(); \
+  } while (0)
+/* inside `if (signaller)`: one thread of the workgroup */
+#define PDF_PROF_FENCE_BEGIN() g_fence_b[blockIdx.x] = prof_now()
+#define PDF_PROF_FENCE_END()                                   \
+  do {                                                         \
+    g_fence_t[blockIdx.x] += prof_now() - g_fence_b[blockIdx.x]; \
+    g_fence_n[blockIdx.x] += 1;                                \
   } while (0)
 #define CHAIN_PROF_END(cls)                                                              \
   do {                                                                                   \
@@ -48,6 +67,12 @@ __device__ __forceinline__ unsigned long long prof_now() {
       atomicAdd(&g_prof[3 * (cls)], 1ull);                                               \
       atomicAdd(&g_prof[3 * (cls) + 1], w_ - b_);                                        \
       atomicAdd(&g_prof[3 * (cls) + 2], e_ - w_);                                        \
+      if (g_stored[blockIdx.x]) {                                                        \
+        atomicAdd(&g_pub[3 * (cls)], 1ull);                                              \
+        atomicAdd(&g_pub[3 * (cls) + 1], e_ - g_stored[blockIdx.x]);                     \
+      }                                                                                  \
+      atomicAdd(&g_fence[3 * (cls)], g_fence_n[blockIdx.x]);                             \
+      atomicAdd(&g_fence[3 * (cls) + 1], g_fence_t[blockIdx.x]);                         \
       const unsigned long long t0_ = g_t0;                                               \
       int it_ = 0;                                                                       \
       for (unsigned long long x_ = w_ - t0_; x_ < e_ - t0_ && it_ < 300; it_++) {        \
@@ -221,6 +246,10 @@ int main(int argc, char** argv) {
       CK(hipMalloc((void**)&d_tasks, tasks.size() * sizeof(int2)));
       CK(hipMemcpy(d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice));
       ChainArgs ca{A, ld, n, n - 1, first, nsteps, 0, status, inv16, flags, d_tasks};
+#ifdef LMGPU_TEST_HOOKS
+      ca.dev_forms = argc > 4 ? atoi(argv[4]) : 0;
+      printf("hand-off forms %d\n", ca.dev_forms);
+#endif
       reset();
       CK(hipMemset(flags, 0, (size_t)(np + 2) * PDF_FLAG_WORDS * 4));
       // panel `first` must be factored for the first step (its trailing data are whatever the matrix holds: timing only)
@@ -232,6 +261,8 @@ int main(int argc, char** argv) {
         const unsigned long long big = ~0ull;
         CK(hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z.data(), 16 * 8));
         CK(hipMemcpyToSymbol(HIP_SYMBOL(g_hist), z.data(), 256 * 8));
+        CK(hipMemcpyToSymbol(HIP_SYMBOL(g_pub), z.data(), 16 * 8));
+        CK(hipMemcpyToSymbol(HIP_SYMBOL(g_fence), z.data(), 16 * 8));
         CK(hipMemcpyToSymbol(HIP_SYMBOL(g_t0), &big, 8));
       }
       CK(hipEventRecord(e0, 0));
@@ -246,8 +277,10 @@ int main(int argc, char** argv) {
       auto st = [&](int region, int b, int slot) { return *(unsigned long long*)&hf[(size_t)region * PDF_FLAG_WORDS + 512 + 64 * b + 2 * slot]; };
       const unsigned long long t0 = st(first + 1, 0, 19);
       {
-        unsigned long long pr[16], hi[256];
+        unsigned long long pr[16], hi[256], pb[16], fe[16];
         CK(hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_prof), 16 * 8));
+        CK(hipMemcpyFromSymbol(pb, HIP_SYMBOL(g_pub), 16 * 8));
+        CK(hipMemcpyFromSymbol(fe, HIP_SYMBOL(g_fence), 16 * 8));
         CK(hipMemcpyFromSymbol(hi, HIP_SYMBOL(g_hist), 256 * 8));
         const char* cn[5] = {"head quadrants", "head 64-tiles", "diagonal", "update tiles", "row-panel"};
         double tot_work = 0;
@@ -256,6 +289,12 @@ int main(int argc, char** argv) {
                  pr[3 * c + 2] / 100.0, pr[3 * c] ? pr[3 * c + 2] / 100.0 / pr[3 * c] : 0.0);
           tot_work += pr[3 * c + 2] / 100.0;
         }
+        // the publish segment of the tile roles (last C store of thread 0 -> publish done: drain, barrier, [release fence,] flag add) and the
+        // release fences of every class (the signaller's time in fence + wait)
+        for (int c = 0; c < 5; c++)
+          printf("  class %-14s: publish %6llu x avg %5.2f us = %8.1f us of slot-time | release fences %6llu x avg %5.2f us = %8.1f us\n", cn[c], pb[3 * c],
+                 pb[3 * c] ? pb[3 * c + 1] / 100.0 / pb[3 * c] : 0.0, pb[3 * c + 1] / 100.0, fe[3 * c], fe[3 * c] ? fe[3 * c + 1] / 100.0 / fe[3 * c] : 0.0,
+                 fe[3 * c + 1] / 100.0);
         printf("  slot occupancy (working workgroup-time / (512 slots x launch time)): %.3f\n", tot_work / (512.0 * ms * 1e3));
         printf("  working slots per 100 us bucket (of 512):");
         for (int b = 0; b < 256 && b * 100.0 < ms * 1e3; b++) printf(" %d", (int)(hi[b] / 10000.0 + 0.5));
