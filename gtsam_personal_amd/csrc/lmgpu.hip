@@ -32,6 +32,7 @@
 #include "kernels_dense.hpp"
 #include "kernels_potrf.hpp"
 #include "kernels_step.hpp"
+#include "dense_schedule.hpp"
 #include "kernels_batched.hpp"
 #include "kernels_level.hpp"
 #include "kernels_bayes.hpp"
@@ -168,7 +169,7 @@ const int kNumBins = 12;  // 0..5: LDS fronts by size; 6..11: the same sizes for
 const int kLdsLimitN = 139;
 const int kLdsFrontExtra = LDSF_EXTRA_BYTES;
 const int NB = 64;    // potrf / trsm step
-const int NBO = 256;  // outer panel: rows eliminated per trailing update of the HBM front
+const int NBO = DENSE_NBO;  // outer panel: rows eliminated per trailing update of the HBM front
 const int kSyrkLds = 2 * 2 * SYRK_KC * SYRK_LDW * 8;
 
 }  // namespace
@@ -239,8 +240,13 @@ struct lmgpu_handle {
   double* inv16 = nullptr;                     // 16 x (16x16) inverses of the current outer panel's diagonal tiles
   bool two_launch_panel = false;               // LMGPU_PANEL_2L=1: diag_potrf + panel_trsm for every outer panel (A/B)
   bool no_fuse = false;                        // LMGPU_NO_FUSE=1: trailing update and next panel as separate launches (A/B)
-  struct ChainPlan { int i0 = -1, nsteps = 0, ntasks = 0; int2* d_tasks = nullptr; double flop = 0; };
-  std::map<int, std::vector<ChainPlan>> chain_plans;  // per HBM front: ticket order of its chained launch(es) (built at first use)
+  // per dense front on the per-front path: its launch schedule (dense_schedule.hpp) and, per DENSE_CHAIN record, the ticket order of
+  // that launch as a range of d_chain_tasks.  Built by ensure_dense_schedules before a solve is queued; dense_mode = the communicator
+  // they were built for (-1: not built)
+  struct DensePlan { std::vector<DenseStep> steps; std::vector<int> task_begin, task_count; };
+  std::vector<DensePlan> dense_plans;
+  int2* d_chain_tasks = nullptr;
+  int dense_mode = -1;
   int chain_split_pct = 60;                    // LMGPU_CHAIN_SPLIT (development): share of a block's update tasks listed in front of its row-panel workgroups
   bool chain_merge = true;                     // LMGPU_NO_MERGE: update tiles one step per pass instead of pairs of steps (chain_schedule)
   int chain_far_pct = 50;                      // LMGPU_CHAIN_FAR: tile rows beyond this percentage of the front are scheduled late (chain_schedule)
@@ -643,6 +649,104 @@ static void add_fill(std::vector<FillChunk>& t, const void* p, size_t bytes, uin
     t.push_back(FillChunk{(unsigned long long)(uintptr_t)p + o, (uint32_t)std::min<size_t>(FILL_CHUNK_BYTES, bytes - o), value});
 }
 
+// own factors and children's update matrices of HBM front fi, assembled at pool offset aoff: one wave per row of the front walks that
+// row's sources in a fixed order (no atomics, bitwise reproducible); with_factors = false on the ranks that leave the own terms to rank 0
+static void launch_assemble_rows(lmgpu_handle* h, int fi, int64_t aoff, bool with_factors) {
+  const FrontDesc& F = h->h_fronts[fi];
+  if (h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))
+    hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((F.n + 3) / 4), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi], (const int32_t*)(h->d_rowptr + h->row_begin[fi]),
+                       (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const FrontFac*)h->d_ffac,
+                       (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0);
+}
+
+static void launch_hbm_damp(lmgpu_handle* h, int fi, int64_t aoff, double lambda_v, const double* lambda_p) {
+  const FrontDesc& F = h->h_fronts[fi];
+  hipLaunchKernelGGL(hbm_damp_kernel, dim3((F.nf + 255) / 256), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi], (const int32_t*)h->d_fxoff, h->pool, lambda_v,
+                     lambda_p, (const double*)h->dampw, (const double*)h->gex_active);
+}
+
+// how the assembled rows of HBM front fi reach its working matrix (dense_schedule.hpp): in place, or -- a replicated front with a
+// partial-assembly buffer, once a communicator is attached -- in row chunks summed over the ranks
+static int dense_mode_of(const lmgpu_handle* h, int fi) {
+  const bool replicated = (h->h_fronts[fi].pad & 1) != 0;
+  if (h->s_off[fi] < 0 || !replicated || !(h->comm || h->lgroup)) return DENSE_SINGLE;
+  return h->comm ? DENSE_SPLIT_EVENTS : DENSE_SPLIT_HOST;
+}
+
+// chunk c of a split front = rows [256 c, 256 (c+1)) from the first column of its diagonal block to the end of its last row
+static void chunk_range(int n, int ld, int c, size_t& begin, size_t& count) {
+  const int r0c = c * NBO, rows = std::min(n, r0c + NBO) - r0c;
+  begin = (size_t)r0c * ld + r0c;  // r0c is a multiple of 256: 16-aligned
+  count = (size_t)rows * ld - r0c;
+}
+
+// chunk c of the partial assembly Asm is complete (summed over the ranks) for everything queued on the main stream after this call
+static int wait_chunk(lmgpu_handle* h, double* Asm, int n, int ld, int c) {
+  if (h->comm) {
+    HIPCHECK(hipStreamWaitEvent(h->stream, h->chunk_ev[c], 0));
+    return LMGPU_OK;
+  }
+  size_t cb, cn;  // in-process group: synchronous
+  chunk_range(n, ld, c, cb, cn);
+  return allreduce_sum(h, Asm + cb, cn, h->stream);
+}
+
+// fold chunk c into the working matrix A (which already carries the trailing updates of earlier panels)
+static int add_chunk(lmgpu_handle* h, double* A, double* Asm, int n, int ld, int c) {
+  hipStream_t s = h->stream;
+  const int ktc = h->kt.begin(LMGPU_KT_ALLREDUCE, s);
+  const int rcw = wait_chunk(h, Asm, n, ld, c);
+  if (rcw) return rcw;
+  size_t cb, cn;
+  chunk_range(n, ld, c, cb, cn);
+  hipLaunchKernelGGL(local_sum_kernel, dim3(std::min<size_t>(2048, (cn + 255) / 256)), dim3(256), 0, s, A + cb, (const double*)(Asm + cb), cn);
+  h->kt.end(ktc, s, (double)cn * 8.0);
+  return LMGPU_OK;
+}
+
+// Everything the dense fronts of the per-front path need before a solve is queued or captured: their launch schedules, the ticket
+// orders of their chained launches (chain_schedule) in device memory, and the chunk events of the split fronts.  Built at the first
+// solve, and again when a communicator has been attached since (the split fronts' schedules depend on it).
+static int ensure_dense_schedules(lmgpu_handle* h) {
+  const int mode = h->comm ? DENSE_SPLIT_EVENTS : h->lgroup ? DENSE_SPLIT_HOST : DENSE_SINGLE;
+  if (h->dense_mode == mode) return LMGPU_OK;
+  const unsigned forms = (h->two_launch_panel ? DENSE_FORM_TWO_LAUNCH : 0u) | (h->no_fuse ? DENSE_FORM_NO_FUSE : 0u) |
+                         (h->no_chain ? DENSE_FORM_NO_CHAIN : 0u) | (h->no_tail ? DENSE_FORM_NO_TAIL : 0u);
+  std::vector<int2> tasks;
+  h->dense_plans.assign(h->h_fronts.size(), lmgpu_handle::DensePlan());
+  for (const LevelWork& L : h->levels)
+    for (int fi : L.hbm) {
+      if (h->is_med[fi]) continue;
+      const FrontDesc& F = h->h_fronts[fi];
+      if ((F.nf + NBO - 1) / NBO + 1 > h->pflags_panels) {
+        h->err = "panel flag buffer too small";
+        return LMGPU_INVALID;
+      }
+      lmgpu_handle::DensePlan& P = h->dense_plans[fi];
+      P.steps = dense_front_schedule(F.n, F.nf, dense_mode_of(h, fi), forms);
+      P.task_begin.assign(P.steps.size(), 0);
+      P.task_count.assign(P.steps.size(), 0);
+      for (size_t r = 0; r < P.steps.size(); r++) {
+        if (P.steps[r].kind != DENSE_CHAIN) continue;
+        const std::vector<int2> t = chain_schedule(F.n, F.nf, P.steps[r].i, P.steps[r].nsteps, h->chain_far_pct, h->chain_merge, h->chain_split_pct);
+        P.task_begin[r] = (int)tasks.size();
+        P.task_count[r] = (int)t.size();
+        tasks.insert(tasks.end(), t.begin(), t.end());
+      }
+      if (dense_mode_of(h, fi) != DENSE_SINGLE)
+        while ((int)h->chunk_ev.size() < 2 * ((F.n + NBO - 1) / NBO)) {
+          hipEvent_t e;
+          HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+          h->chunk_ev.push_back(e);
+        }
+    }
+  if (h->d_chain_tasks) HIPCHECK(hipFree(h->d_chain_tasks));
+  const int rcu = upload(h, &h->d_chain_tasks, tasks);
+  if (rcu) return rcu;
+  h->dense_mode = mode;
+  return LMGPU_OK;
+}
+
 int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  // lambda by value (eager) or in device memory (graph replay)
   hipStream_t s = h->stream;
   const bool merge_el = h->merge_elim && !h->elim_segs.empty();
@@ -721,16 +825,11 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - E.jcap) * 8 + 64 + (size_t)E.nmax * E.nmax * sizeof(double);
       const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
       unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + E.lvl_hi;
-      if (E.threads == 1024)
-        hipLaunchKernelGGL(lds_front_merged_kernel<1024>, dim3(e0 - b0), dim3(1024), lds, s, (const int32_t*)h->d_lists, b0, e0, (const FrontDesc*)h->d_fronts,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, E.nmax, E.jcap,
-                           (const double*)h->gex_active, ticket);
-      else
-        hipLaunchKernelGGL(lds_front_merged_kernel<256>, dim3(e0 - b0), dim3(E.threads), lds, s, (const int32_t*)h->d_lists, b0, e0, (const FrontDesc*)h->d_fronts,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, E.nmax, E.jcap,
-                           (const double*)h->gex_active, ticket);
+      auto* kernel = E.threads == 1024 ? lds_front_merged_kernel<1024> : lds_front_merged_kernel<256>;
+      hipLaunchKernelGGL(kernel, dim3(e0 - b0), dim3(E.threads), lds, s, (const int32_t*)h->d_lists, b0, e0, (const FrontDesc*)h->d_fronts,
+                         (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
+                         (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, E.nmax, E.jcap,
+                         (const double*)h->gex_active, ticket, (int*)nullptr);  // (no relay: the status word is read back with the solve's scalars)
       h->kt.end(kt, s);
     }
     const bool fused = h->fuse_levels && L.fuse_task_count > 0;
@@ -740,18 +839,13 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
                                           (size_t)DIAG_LDS_BYTES);
       unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + li;
       const int kt = h->kt.begin(LMGPU_KT_PANEL, s);
-      if (L.fuse_threads == 1024)
-        hipLaunchKernelGGL(level_fused_kernel<1024>, dim3(L.fuse_task_count), dim3(1024), lds, s, (const LevelTask*)(h->d_level_tasks + L.fuse_task_begin), ticket,
-                           (const int32_t*)h->d_lists, (const FrontDesc*)h->d_fronts, (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd,
-                           (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p,
-                           (const double*)h->dampw, h->d_status, L.fuse_nmax, L.fuse_jcap, (const double*)h->gex_active, ML, (const int32_t*)h->d_rowptr,
-                           (const RowSrc*)h->d_rowsrc, h->inv16_med, h->d_level_sync + L.med_begin);
-      else
-        hipLaunchKernelGGL(level_fused_kernel<256>, dim3(L.fuse_task_count), dim3(256), lds, s, (const LevelTask*)(h->d_level_tasks + L.fuse_task_begin), ticket,
-                           (const int32_t*)h->d_lists, (const FrontDesc*)h->d_fronts, (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd,
-                           (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p,
-                           (const double*)h->dampw, h->d_status, L.fuse_nmax, L.fuse_jcap, (const double*)h->gex_active, ML, (const int32_t*)h->d_rowptr,
-                           (const RowSrc*)h->d_rowsrc, h->inv16_med, h->d_level_sync + L.med_begin);
+      const bool wide = L.fuse_threads == 1024;
+      auto* kernel = wide ? level_fused_kernel<1024> : level_fused_kernel<256>;
+      hipLaunchKernelGGL(kernel, dim3(L.fuse_task_count), dim3(wide ? 1024 : 256), lds, s, (const LevelTask*)(h->d_level_tasks + L.fuse_task_begin), ticket,
+                         (const int32_t*)h->d_lists, (const FrontDesc*)h->d_fronts, (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd,
+                         (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p,
+                         (const double*)h->dampw, h->d_status, L.fuse_nmax, L.fuse_jcap, (const double*)h->gex_active, ML, (const int32_t*)h->d_rowptr,
+                         (const RowSrc*)h->d_rowsrc, h->inv16_med, h->d_level_sync + L.med_begin);
       h->kt.end(kt, s);
     }
     for (int b = 0; b < kNumBins && seg == -1 && !fused; b++) {
@@ -766,27 +860,14 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       // a handful of wide fronts (the upper levels of a general sparse tree, where a launch lasts as long as its slowest front and the
       // device is idle): sixteen waves per front -- the rank-4 trailing updates, the extend-add and the emission all scale with them
       const bool wide16 = b >= 3 && b < 6 && cnt <= h->wide16_max && !h->no_wide16;
-      if (wide16)
-        hipLaunchKernelGGL((lds_front_kernel<false, 1024>), dim3(cnt), dim3(1024), lds, s,
-                           (const int32_t*)(h->d_lists + L.list_begin + L.bin_begin[b]), (const FrontDesc*)h->d_fronts,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, nmax, srows, h->d_gcorner, jcap,
-                           (const double*)h->gex_active, (const char*)(h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr),
-                           L.pack_stride[b]);
-      else if (b < 6)
-        hipLaunchKernelGGL(lds_front_kernel<false>, dim3(cnt), dim3(threads), lds, s,
-                           (const int32_t*)(h->d_lists + L.list_begin + L.bin_begin[b]), (const FrontDesc*)h->d_fronts,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, nmax, srows, h->d_gcorner, jcap,
-                           (const double*)h->gex_active, (const char*)(h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr),
-                           L.pack_stride[b]);
-      else
-        hipLaunchKernelGGL(lds_front_kernel<true>, dim3(cnt), dim3(threads), lds, s,
-                           (const int32_t*)(h->d_lists + L.list_begin + L.bin_begin[b]), (const FrontDesc*)h->d_fronts,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, nmax, srows, h->d_gcorner, jcap,
-                           (const double*)h->gex_active, (const char*)(h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr),
-                           L.pack_stride[b]);
+      auto* kernel = lds_front_kernel<false, 1024>;
+      if (!wide16) kernel = b < 6 ? lds_front_kernel<false> : lds_front_kernel<true>;
+      hipLaunchKernelGGL(kernel, dim3(cnt), dim3(wide16 ? 1024 : threads), lds, s,
+                         (const int32_t*)(h->d_lists + L.list_begin + L.bin_begin[b]), (const FrontDesc*)h->d_fronts,
+                         (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
+                         (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, nmax, srows, h->d_gcorner, jcap,
+                         (const double*)h->gex_active, (const char*)(h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr),
+                         L.pack_stride[b]);
       h->kt.end(kt, s);
     }
     if (L.med_count > 0 && !fused) {  // medium fronts of this level: six launches for all of them
@@ -819,270 +900,144 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       const int64_t off = h->f_off[fi];
       const int ld = h->f_ld[fi];
       double* A = h->pool + off;
-      const bool replicated = (F.pad & 1) != 0, own_terms = (F.pad & 2) == 0;
+      const bool own_terms = (F.pad & 2) == 0;
       const lmgpu_handle::GatherRange& G = h->gather[fi];
-      const int np = (F.nf + NBO - 1) / NBO;
       const int nchunks = (F.n + NBO - 1) / NBO;
       // `split`: the assembled contributions go to a buffer of their own (aoff) and reach the working matrix A (which starts
       // from zero and collects the trailing updates) in 256-row chunks, each just before its panel is factored.
       //   multi-rank   : the chunks are summed over the ranks (RCCL on the communication stream / the in-process group)
       // (gathering the chunks on a second stream beside the factorisation was measured in round 1 -- 13.5 vs 10.4 ms per step: two
       //  resident workgroups of the update kernel hold every VGPR of a SIMD, the gather waves only get in between -- and removed)
-      const bool multi = replicated && (h->comm || h->lgroup);
-      const bool split = h->s_off[fi] >= 0 && multi;
+      const int mode = dense_mode_of(h, fi);
+      const bool split = mode != DENSE_SINGLE;
       const int64_t aoff = split ? h->s_off[fi] : off;
       double* Asm = h->pool + aoff;
-      hipStream_t sa = s;
-      if (split)
-        while ((int)h->chunk_ev.size() < 2 * nchunks) {
-          hipEvent_t e;
-          HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          h->chunk_ev.push_back(e);
-        }
-      // chunk c = rows [256 c, 256 (c+1)) from the first column of its diagonal block to the end of its last row
-      auto chunk_range = [&](int c, size_t& begin, size_t& count) {
-        const int r0c = c * NBO, rows = std::min(F.n, r0c + NBO) - r0c;
-        begin = (size_t)r0c * ld + r0c;  // r0c is a multiple of 256: 16-aligned
-        count = (size_t)rows * ld - r0c;
-      };
-      int kt = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, sa);
+
+      // ---- assembly
+      const int kt = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
       const bool gwrite = gather_writes(h, fi);
       if (gwrite && G.zero_count > 0)
-        hipLaunchKernelGGL(zero_blocks_kernel, dim3(G.zero_count), dim3(128), 0, sa, (const GZeroBlock*)(h->d_gzero + G.zero_begin), h->pool, aoff, ld);
-      // own factors and children's update matrices: one wave per row of the front walks that row's sources in a fixed order (no
-      // atomics, bitwise reproducible); with_factors = 0 on the ranks that leave the own terms to rank 0
-      auto assemble_rows = [&](bool with_factors) {
-        if (h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))
-          hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((F.n + 3) / 4), dim3(256), 0, sa, F, aoff, ld, (const int32_t*)(h->d_rowptr + h->row_begin[fi]),
-                             (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const FrontFac*)h->d_ffac,
-                             (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0);
-      };
-      assemble_rows(own_terms && !gwrite);
-      auto own_additive_terms = [&]() {  // the front's own factors and the damping (added: after whatever initialises the entries)
-        if (F.fac_count > 0 && own_terms) assemble_rows(true);  // (a gather-write front has no update-matrix children: only its factors are added here)
-        if (own_terms)
-          hipLaunchKernelGGL(hbm_damp_kernel, dim3((F.nf + 255) / 256), dim3(256), 0, sa, F, aoff, ld, (const int32_t*)h->d_fxoff, h->pool, lambda_v,
-                             lambda_p, (const double*)h->dampw, (const double*)h->gex_active);
-      };
-      if (!gwrite && own_terms)
-        hipLaunchKernelGGL(hbm_damp_kernel, dim3((F.nf + 255) / 256), dim3(256), 0, sa, F, aoff, ld, (const int32_t*)h->d_fxoff, h->pool, lambda_v,
-                           lambda_p, (const double*)h->dampw, (const double*)h->gex_active);
-      // leaf children in Schur form: deterministic gather instead of atomics; rows [c0, c1) of the chunk table
+        hipLaunchKernelGGL(zero_blocks_kernel, dim3(G.zero_count), dim3(128), 0, s, (const GZeroBlock*)(h->d_gzero + G.zero_begin), h->pool, aoff, ld);
+      launch_assemble_rows(h, fi, aoff, own_terms && !gwrite);
+      if (!gwrite && own_terms) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
+      // leaf children in Schur form: deterministic gather instead of atomics
       const int schur_masked = dev_switch("LMGPU_SCHUR_UNMASKED") ? 0 : 2;  // (operand loads that only the lanes holding an element take part in)
-      auto gather_chunks = [&](int c0, int c1, bool whole) {
-        const int s0 = whole ? 0 : G.cs[c0], s1 = whole ? G.pblk_short : G.cs[c1];
-        const int l0 = whole ? 0 : G.cl[c0], l1 = whole ? G.pblk_long : G.cl[c1];
-        const int v0 = whole ? 0 : G.cv[c0], v1 = whole ? G.vblk_count : G.cv[c1];
-        if (s1 > s0)
-          hipLaunchKernelGGL((schur_pairs_kernel<1>), dim3((s1 - s0 + 7) & ~7), dim3(64), 0, sa, (const GPairBlock*)(h->d_gpblk + G.pblk_begin + s0),
-                             (const GPairEntry*)h->d_gpent, h->pool, aoff, ld, s1 - s0, (gwrite ? 1 : 0) | schur_masked);
-        if (l1 > l0)
-          hipLaunchKernelGGL((schur_pairs_kernel<4>), dim3((l1 - l0 + 7) & ~7), dim3(256), 0, sa,
-                             (const GPairBlock*)(h->d_gpblk + G.pblk_begin + G.pblk_short + l0), (const GPairEntry*)h->d_gpent, h->pool, aoff, ld,
-                             l1 - l0, (gwrite ? 1 : 0) | schur_masked);
-        if (v1 > v0)
-          hipLaunchKernelGGL(schur_factor_kernel, dim3(v1 - v0), dim3(64 * SCHUR_FW), 0, sa, (const GVarBlock*)(h->d_gvblk + G.vblk_begin + v0),
-                             (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
-        if (G.leaf_count > 0 && (whole || c1 == nchunks)) {  // the (rhs, rhs) corner lives in the last chunk
-          double* scal = h->dscal + 4;
-          reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, sa, nullptr);
-          hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, sa, Asm + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
-        }
-      };
-      gather_chunks(0, nchunks, true);
-      if (gwrite) own_additive_terms();
-      h->kt.end(kt, sa);
-      if (multi && h->comm && split) {  // RCCL: all chunks queued on the communication stream, one event each
+      if (G.pblk_short > 0)
+        hipLaunchKernelGGL((schur_pairs_kernel<1>), dim3((G.pblk_short + 7) & ~7), dim3(64), 0, s, (const GPairBlock*)(h->d_gpblk + G.pblk_begin),
+                           (const GPairEntry*)h->d_gpent, h->pool, aoff, ld, G.pblk_short, (gwrite ? 1 : 0) | schur_masked);
+      if (G.pblk_long > 0)
+        hipLaunchKernelGGL((schur_pairs_kernel<4>), dim3((G.pblk_long + 7) & ~7), dim3(256), 0, s,
+                           (const GPairBlock*)(h->d_gpblk + G.pblk_begin + G.pblk_short), (const GPairEntry*)h->d_gpent, h->pool, aoff, ld,
+                           G.pblk_long, (gwrite ? 1 : 0) | schur_masked);
+      if (G.vblk_count > 0)
+        hipLaunchKernelGGL(schur_factor_kernel, dim3(G.vblk_count), dim3(64 * SCHUR_FW), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
+                           (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
+      if (G.leaf_count > 0) {  // the (rhs, rhs) corner
+        double* scal = h->dscal + 4;
+        reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, s, nullptr);
+        hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, s, Asm + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
+      }
+      if (gwrite && own_terms) {  // the front's own factors and the damping are added: after the gather has initialised the entries
+        if (F.fac_count > 0) launch_assemble_rows(h, fi, aoff, true);  // (a gather-write front has no update-matrix children: only its factors are added here)
+        launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
+      }
+      h->kt.end(kt, s);
+      if (mode == DENSE_SPLIT_EVENTS) {  // RCCL: all chunks queued on the communication stream, one event each
         HIPCHECK(hipEventRecord(h->asm_ev, s));
         HIPCHECK(hipStreamWaitEvent(h->comm_stream, h->asm_ev, 0));
         for (int c = 0; c < nchunks; c++) {
           size_t cb, cn;
-          chunk_range(c, cb, cn);
+          chunk_range(F.n, ld, c, cb, cn);
           NCCLCHECK(ncclAllReduce(Asm + cb, Asm + cb, cn, ncclDouble, ncclSum, h->comm_data ? h->comm_data : h->comm, h->comm_stream));
           HIPCHECK(hipEventRecord(h->chunk_ev[c], h->comm_stream));
         }
       }
-      // chunk c is complete (gathered / reduced) for everything queued on the main stream after this call
-      auto wait_chunk = [&](int c) -> int {
-        if (!split || c >= nchunks) return LMGPU_OK;
-        if (h->comm) {
-          HIPCHECK(hipStreamWaitEvent(s, h->chunk_ev[c], 0));
-        } else {  // in-process group: synchronous
-          size_t cb, cn;
-          chunk_range(c, cb, cn);
-          const int rca = allreduce_sum(h, Asm + cb, cn, s);
-          if (rca) return rca;
-        }
-        return LMGPU_OK;
-      };
-      // fold chunk c into the working matrix (which already carries the trailing updates of earlier panels)
-      auto add_chunk = [&](int c) -> int {
-        if (!split || c >= nchunks) return LMGPU_OK;
-        const int ktc = h->kt.begin(LMGPU_KT_ALLREDUCE, s);
-        const int rcw = wait_chunk(c);
-        if (rcw) return rcw;
-        size_t cb, cn;
-        chunk_range(c, cb, cn);
-        hipLaunchKernelGGL(local_sum_kernel, dim3(std::min<size_t>(2048, (cn + 255) / 256)), dim3(256), 0, s, A + cb, (const double*)(Asm + cb), cn);
-        h->kt.end(ktc, s, (double)cn * 8.0);
-        return LMGPU_OK;
-      };
-      { const int rc0 = add_chunk(0); if (rc0) return rc0; }
-      // Blocked right-looking partial Cholesky, outer panels of NBO = 256 rows.  Panel 0 is one dataflow launch
-      // (panel_dataflow_kernel); after that ONE launch per outer panel i (step_kernel): trailing update with panel i
-      // + factorisation of panel i+1 beside/behind it (look-ahead inside the launch, kernels_step.hpp).  A panel whose row
-      // count is not a multiple of 64 (the last one) takes the two-launch form diag_potrf_kernel + panel_trsm_kernel.
-      if (np + 1 > h->pflags_panels) {
-        h->err = "panel flag buffer too small";
-        return LMGPU_INVALID;
-      }
-      HIPCHECK(hipMemsetAsync(h->d_pflags, 0, (size_t)(np + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), s));
-      auto rows_of = [&](int i) { return std::min(F.nf, (i + 1) * NBO) - i * NBO; };
-      auto dataflow_ok = [&](int i) {  // panel i can run as block-column workgroups with flag hand-offs
-        return rows_of(i) % 64 == 0 && !h->two_launch_panel && (F.n - i * NBO + 63) / 64 <= PDF_MAX_COLTILES;
-      };
-      auto panel_flop = [&](int i) {
-        const double kb = rows_of(i), cols = F.n - i * NBO - kb;
-        return kb * kb * kb / 3.0 + kb * kb * cols;
-      };
-      auto panel_alone = [&](int i) {
-        const int k0 = i * NBO, kb = rows_of(i), cols = F.n - k0 - kb;
-        const int ktp = h->kt.begin(LMGPU_KT_PANEL, s);
-        if (dataflow_ok(i)) {
-          hipLaunchKernelGGL(panel_dataflow_kernel, dim3(kb / 64 + (cols + 63) / 64), dim3(256), PDF_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id,
-                             h->d_status, h->inv16 + (size_t)i * 4096, h->d_pflags + (size_t)i * PDF_FLAG_WORDS);
-        } else {
-          hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, s, A, ld, F.nf, k0, kb, F.id, h->d_status, h->inv16 + (size_t)i * 4096);
-          if (cols > 0)
-            hipLaunchKernelGGL(panel_trsm_kernel, dim3((cols + 63) / 64), dim3(256), 0, s, A, ld, F.n, k0, kb, (const double*)(h->inv16 + (size_t)i * 4096));
-        }
-        h->kt.end(ktp, s, panel_flop(i));
-      };
-      panel_alone(0);
+
+      // ---- factorisation: the front's schedule (dense_schedule.hpp, built by ensure_dense_schedules), record by record
+      const lmgpu_handle::DensePlan& plan = h->dense_plans[fi];
       h->inv16_owner = fi;  // the per-panel 16x16 inverses now belong to this front (read again by its back-substitution)
-      int kt_run = -1, run_launches = 0;  // one event pair around a run of consecutive step launches
+      int kt_run = -1, run_launches = 0;  // one event pair around a run of consecutive fused-step launches
       double run_flop = 0;
-      auto close_run = [&]() {
-        if (run_launches > 0) h->kt.end(kt_run, s, run_flop, run_launches);
-        kt_run = -1;
-        run_launches = 0;
-        run_flop = 0;
-      };
-      // a step that can be fused with the factorisation of the next panel; consecutive ones with full panels go as ONE launch
-      auto fusable = [&](int i) { return (i + 1 < np) && dataflow_ok(i + 1) && !h->no_fuse && F.n - i * NBO - rows_of(i) > 0; };
-      // multi-rank (RCCL): the steps still go as chained launches -- their head tiles fold the all-reduced row chunks in -- but in
-      // SEGMENTS of 1, 1, 2, 4, 8, ... steps, each launched behind a stream wait for the event of the last chunk it touches: no
-      // workgroup ever waits for the network inside a launch (nothing to deadlock on), the first panels start after two chunks, and
-      // the communication stream gets further ahead with every segment (one launch per step cost 6.9 vs 6.2 ms for the C4 root in
-      // round 1).  The in-process test communicator sums on the host between the launches and keeps the per-step form.
-      const bool chain_split = split && h->comm != nullptr;
-      auto chainable = [&](int i) {
-        return fusable(i) && (!split || chain_split) && !h->no_chain && rows_of(i) == NBO && (F.n - (i + 1) * NBO + 127) / 128 <= PDF_MAX_CHAIN_T;
-      };
-      for (int i = 0; i < np; i++) {
-        const int k0 = i * NBO, kb = rows_of(i), r0 = k0 + kb, m = F.n - r0;
-        if (m <= 0) break;
-        if (chainable(i) && chainable(i + 1)) {
-          // the run of chainable steps starting here: one launch (single rank) or a few segment launches (multi-rank), ticket order
-          // built once per front and segment (chain_schedule)
-          int run = 0;
-          while (chainable(i + run)) run++;
-          std::vector<lmgpu_handle::ChainPlan>& plans = h->chain_plans[fi];
-          if (plans.empty() || plans[0].i0 != i) {
-            for (auto& p : plans)
-              if (p.d_tasks) HIPCHECK(hipFree(p.d_tasks));
-            plans.clear();
-            int at = i, seg = 1, nseg = 0;
-            while (at < i + run) {
-              lmgpu_handle::ChainPlan cp;
-              cp.i0 = at;
-              cp.nsteps = chain_split ? std::min(seg, i + run - at) : run;
-              if (chain_split && i + run - (at + cp.nsteps) == 1) cp.nsteps++;  // no one-step remainder
-              for (int q = 0; q < cp.nsteps; q++) {
-                const int is = at + q, ms = F.n - (is + 1) * NBO;
-                cp.flop += 2.0 * NBO * ((double)ms * (ms + 1) / 2.0) + panel_flop(is + 1);
-              }
-              const std::vector<int2> tasks = chain_schedule(F.n, F.nf, cp.i0, cp.nsteps, h->chain_far_pct, h->chain_merge, h->chain_split_pct);
-              cp.ntasks = (int)tasks.size();
-              HIPCHECK(hipMalloc((void**)&cp.d_tasks, tasks.size() * sizeof(int2)));
-              HIPCHECK(hipMemcpyAsync(cp.d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-              HIPCHECK(hipStreamSynchronize(s));  // `tasks` is a local
-              at += cp.nsteps;
-              if (++nseg >= 2) seg *= 2;
-              plans.push_back(cp);
+      for (size_t r = 0; r < plan.steps.size(); r++) {
+        const DenseStep& st = plan.steps[r];
+        // panel i = rows [k0, r0), m columns behind it (panel records only)
+        const int i = st.i, k0 = i * NBO, kb = std::min(F.nf, k0 + NBO) - k0, r0 = k0 + kb, m = F.n - r0;
+        // the wait of a fused step that folds its chunk in itself stays inside the run; everything else is timed on its own
+        const bool in_run = st.kind == DENSE_STEP_FUSED || (st.kind == DENSE_WAIT_CHUNK && plan.steps[r + 1].kind == DENSE_STEP_FUSED);
+        if (!in_run && run_launches > 0) {
+          h->kt.end(kt_run, s, run_flop, run_launches);
+          run_launches = 0;
+          run_flop = 0;
+        }
+        switch (st.kind) {
+          case DENSE_PANEL_DATAFLOW:
+          case DENSE_PANEL_TWO_LAUNCH: {
+            if (i == 0) HIPCHECK(hipMemsetAsync(h->d_pflags, 0, (size_t)((F.nf + NBO - 1) / NBO + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), s));
+            double* inv16 = h->inv16 + (size_t)i * 4096;
+            const int ktp = h->kt.begin(LMGPU_KT_PANEL, s);
+            if (st.kind == DENSE_PANEL_DATAFLOW) {
+              hipLaunchKernelGGL(panel_dataflow_kernel, dim3(kb / 64 + (m + 63) / 64), dim3(256), PDF_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id,
+                                 h->d_status, inv16, h->d_pflags + (size_t)i * PDF_FLAG_WORDS);
+            } else {
+              hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, s, A, ld, F.nf, k0, kb, F.id, h->d_status, inv16);
+              if (m > 0) hipLaunchKernelGGL(panel_trsm_kernel, dim3((m + 63) / 64), dim3(256), 0, s, A, ld, F.n, k0, kb, (const double*)inv16);
             }
+            h->kt.end(ktp, s, st.flop);
+            break;
           }
-          close_run();
-          for (const lmgpu_handle::ChainPlan& cp : plans) {
-            if (split) {  // every row chunk the segment folds in (cp.i0 + 1 .. cp.i0 + cp.nsteps) is summed over the ranks
-              const int rcw = wait_chunk(cp.i0 + cp.nsteps);
-              if (rcw) return rcw;
-            }
-            ChainArgs ca{A, ld, F.n, F.nf, cp.i0, cp.nsteps, F.id, h->d_status, h->inv16, h->d_pflags, cp.d_tasks, split ? (const double*)Asm : nullptr};
+          case DENSE_CHAIN: {  // (a split front: behind the wait for the last row chunk the launch folds in)
+            ChainArgs ca{A, ld, F.n, F.nf, i, st.nsteps, F.id, h->d_status, h->inv16, h->d_pflags, h->d_chain_tasks + plan.task_begin[r],
+                         split ? (const double*)Asm : nullptr};
 #ifdef LMGPU_TEST_HOOKS
             ca.dev_forms = h->chain_forms;
 #endif
             const int ktc = h->kt.begin(LMGPU_KT_CHAIN, s);
-            hipLaunchKernelGGL(chain_kernel, dim3(cp.ntasks), dim3(256), STEP_LDS_BYTES, s, ca);
-            h->kt.end(ktc, s, cp.flop, 1);
+            hipLaunchKernelGGL(chain_kernel, dim3(plan.task_count[r]), dim3(256), STEP_LDS_BYTES, s, ca);
+            h->kt.end(ktc, s, st.flop, 1);
+            break;
           }
-          i += run - 1;
-          continue;
-        }
-        // the end of the front as one small launch: update with panel i, factor the last (partial) panel, update what follows
-        if (!split && !h->no_tail && i + 2 == np && kb <= TAIL_MAX_KP && m <= TAIL_MAX_M && rows_of(i + 1) < 64) {
-          close_run();
-          const int ktt = h->kt.begin(LMGPU_KT_PANEL, s);
-          hipLaunchKernelGGL(front_tail_kernel, dim3(1), dim3(256), TAIL_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
-                             h->inv16 + (size_t)(i + 1) * 4096);
-          h->kt.end(ktt, s, 2.0 * kb * ((double)m * (m + 1) / 2.0) + panel_flop(i + 1));
-          break;
-        }
-        const bool fuse = fusable(i);
-        // rows of panel i+1 (and, for i = np-1, of the separator part): a fused step folds them in itself (its 64x64 head tiles
-        // cover exactly those rows), otherwise an add kernel does
-        const bool fold_in_step = split && fuse && r0 == (i + 1) * NBO;
-        if (fold_in_step) {
-          const int rcw = wait_chunk(i + 1);
-          if (rcw) return rcw;
-        } else {
-          if (split && i + 1 < nchunks) close_run();  // the fold-in kernel is timed separately
-          const int rcc = add_chunk(i + 1);
-          if (rcc) return rcc;
-        }
-        const int T = (m + 127) / 128;
-        // algorithmic flop of the update: 2 x kb x (upper-triangle entries of the m x m trailing matrix)
-        const double upd_flop = 2.0 * kb * ((double)m * (m + 1) / 2.0);
-        if (fuse) {
-          const int kbn = rows_of(i + 1);
-          StepArgs a{A, ld, F.n, F.nf, k0, kb, kbn, F.id, h->d_status, h->inv16 + (size_t)(i + 1) * 4096, h->d_pflags + (size_t)(i + 1) * PDF_FLAG_WORDS,
-                     fold_in_step ? (const double*)Asm : nullptr};
+          case DENSE_STEP_FUSED: {  // (a split front: behind the wait for the chunk of panel i + 1, which its head tiles fold in)
+            const int kbn = std::min(F.nf, r0 + NBO) - r0;
+            StepArgs a{A, ld, F.n, F.nf, k0, kb, kbn, F.id, h->d_status, h->inv16 + (size_t)(i + 1) * 4096, h->d_pflags + (size_t)(i + 1) * PDF_FLAG_WORDS,
+                       split ? (const double*)Asm : nullptr};
 #ifdef LMGPU_TEST_HOOKS
-          a.dev_forms = h->chain_forms;
+            a.dev_forms = h->chain_forms;
 #endif
-          const int grid = step_grid(m, kbn);
-          if (run_launches == 0) kt_run = h->kt.begin(LMGPU_KT_SYRK, s);
-          hipLaunchKernelGGL(step_kernel, dim3(grid), dim3(256), STEP_LDS_BYTES, s, a);
-          run_launches++;
-          run_flop += upd_flop + panel_flop(i + 1);
-        } else {
-          close_run();
-          const int kts = h->kt.begin(LMGPU_KT_SYRK, s);
-          if (m <= 1024) {  // a few tiles: one workgroup per 32 x 32 quadrant instead (each 128-tile is K / 4 x 16 dependent MFMAs on one CU)
-            const int S = (m + 63) / 64;
-            hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * S, S), dim3(256), 0, s, A, ld, F.n, k0, kb, r0);
-          } else {
-            hipLaunchKernelGGL(syrk_mfma_kernel, dim3(T, T), dim3(256), kSyrkLds, s, A, ld, F.n, k0, kb, r0, F.n);
+            if (run_launches == 0) kt_run = h->kt.begin(LMGPU_KT_SYRK, s);
+            hipLaunchKernelGGL(step_kernel, dim3(step_grid(m, kbn)), dim3(256), STEP_LDS_BYTES, s, a);
+            run_launches++;
+            run_flop += st.flop;
+            break;
           }
-          h->kt.end(kts, s, upd_flop);
-          if (i + 1 < np) panel_alone(i + 1);
+          case DENSE_UPDATE_QUADRANTS:
+          case DENSE_UPDATE_MFMA: {
+            const int kts = h->kt.begin(LMGPU_KT_SYRK, s);
+            if (st.kind == DENSE_UPDATE_QUADRANTS) {
+              const int S = (m + 63) / 64;
+              hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * S, S), dim3(256), 0, s, A, ld, F.n, k0, kb, r0);
+            } else {
+              const int T = (m + 127) / 128;
+              hipLaunchKernelGGL(syrk_mfma_kernel, dim3(T, T), dim3(256), kSyrkLds, s, A, ld, F.n, k0, kb, r0, F.n);
+            }
+            h->kt.end(kts, s, st.flop);
+            break;
+          }
+          case DENSE_TAIL: {
+            const int ktt = h->kt.begin(LMGPU_KT_PANEL, s);
+            hipLaunchKernelGGL(front_tail_kernel, dim3(1), dim3(256), TAIL_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
+                               h->inv16 + (size_t)(i + 1) * 4096);
+            h->kt.end(ktt, s, st.flop);
+            break;
+          }
+          case DENSE_ADD_CHUNK:
+          case DENSE_WAIT_CHUNK: {
+            const int rcc = st.kind == DENSE_ADD_CHUNK ? add_chunk(h, A, Asm, F.n, ld, st.chunk) : wait_chunk(h, Asm, F.n, ld, st.chunk);
+            if (rcc) return rcc;
+            break;
+          }
         }
       }
-      close_run();
-      for (int c = np + 1; c < nchunks; c++) {  // separator rows beyond the chunk after the last panel
-        const int rcc = add_chunk(c);
-        if (rcc) return rcc;
-      }
+      if (run_launches > 0) h->kt.end(kt_run, s, run_flop, run_launches);
     }
   }
   HIPCHECK(hipGetLastError());
@@ -1462,8 +1417,9 @@ static bool graph_eligible(const lmgpu_handle* h) {
 int do_solve_enqueue(lmgpu_handle* h, double lambda) {
   if (use_pcg(h)) return pcg_solve_enqueue(h, lambda);
   hipStream_t s = h->stream;
+  int rc = ensure_dense_schedules(h);  // (allocates and uploads at the first solve: before anything is queued or captured)
+  if (rc) return rc;
   (void)hipEventRecord(h->ev[1], s);
-  int rc;
   if (graph_eligible(h)) {
     hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(1), 0, s, h->d_lambda, lambda);  // the replay reads lambda from device memory
     hipGraphExec_t& exec = h->solve_graph[h->gex_active ? 1 : 0];
@@ -2067,8 +2023,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
       if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     for (hipEvent_t e : h->kt.pool) (void)hipEventDestroy(e);
     fr(h->bs_inv); fr(h->bs_x); fr(h->bs_flags); fr(h->inv16); fr(h->d_pflags); fr(h->d_bs_parent); fr(h->d_bs_pos); fr(h->d_bs_done); fr(h->d_fill_upper); fr(h->d_level_tasks); fr(h->d_level_sync); fr(h->d_bsd_table); fr(h->d_bsd_run_table); fr(h->d_fill_elim); fr(h->d_fill_backsub); fr(h->d_zero_ranges); fr(h->d_bsd_x); fr(h->d_bsd_ticket); fr(h->d_leafpack); fr(h->d_gzero);
-    for (auto& kv : h->chain_plans)
-      for (auto& cp : kv.second) fr(cp.d_tasks);
+    fr(h->d_chain_tasks);
     fr(h->d_gpblk); fr(h->d_gpent); fr(h->d_gvblk); fr(h->d_gvent); fr(h->d_gcorner); fr(h->d_row_begin); fr(h->d_rowptr); fr(h->d_rowsrc);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
@@ -3942,6 +3897,17 @@ int lmgpu_local_group_create(int32_t world_size, lmgpu_local_group** out) {
   return LMGPU_OK;
 }
 #endif
+// Host-only view of the launch schedule of a dense front (dense_schedule.hpp): (kind, i, nsteps, chunk) per record into `out`; returns
+// the number of records, negative for refused geometry or when max_records is too small.
+int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int max_records, int32_t* out) {
+  const std::vector<DenseStep> steps = dense_front_schedule(n, nf, mode, forms);
+  if (steps.empty() || !out || (int)steps.size() > max_records) return -1;
+  for (const DenseStep& st : steps) {
+    const int32_t rec[4] = {st.kind, st.i, st.nsteps, st.chunk};
+    out = std::copy(rec, rec + 4, out);
+  }
+  return (int)steps.size();
+}
 // Host-only check of the ticket order of a chained launch (kernels_step.hpp: chain_schedule): every logical workgroup of every
 // step exactly once, and every dependency step_body waits for at an earlier ticket.  0 = valid, else the 1-based ticket at fault.
 int lmgpu_selftest_chain_schedule(int n, int nf, int i0, int nsteps, int far_pct) {

@@ -486,6 +486,15 @@ int lmgpu_joint_marginal_covariance(lmgpu_handle* h, int32_t nslots, const int32
  * one Eigen LLT call, gtsam/base/cholesky.cpp:108-159); it exists so that the CPU test-suite can check the scheduler. */
 int lmgpu_selftest_chain_schedule(int n, int nf, int i0, int nsteps, int far_pct);
 
+/* Host-only self-test (no GPU work, no handle): the launches that factor one dense front of n columns (nf frontal) on the per-front
+ * path, in execution order.  mode: 0 single rank, 1 row chunks summed on the host (in-process group), 2 row chunks behind events
+ * (RCCL); forms: bit 0 LMGPU_PANEL_2L, 1 LMGPU_NO_FUSE, 2 LMGPU_NO_CHAIN, 3 LMGPU_NO_TAIL.  Four int32 per record into `out`:
+ * kind (0 dataflow panel, 1 two-launch panel, 2 chained launch, 3 fused step, 4 quadrant update, 5 tile update, 6 tail, 7 add row
+ * chunk, 8 wait for row chunk), outer panel i (-1 for 7, 8), steps of a chained launch, row chunk (7, 8; else -1).  Returns the
+ * number of records; negative for refused geometry (n <= 0, nf <= 0, nf > n, unknown mode) or more than max_records records.  No
+ * reference counterpart (see lmgpu_selftest_chain_schedule); it is what the elimination runs, so the CPU test-suite can pin it. */
+int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int max_records, int32_t* out);
+
 /* ---- ISAM2 (gtsam/nonlinear/ISAM2.h): incremental smoothing on a device-resident Bayes tree (BASELINE config 5) ----
  * ISAM2::update(newFactors, newTheta) (gtsam/nonlinear/ISAM2.cpp:419-480) = lmgpu_isam2_add_variables + lmgpu_isam2_add_factors
  * (the pending input) + lmgpu_isam2_update: add the variables, (every relinearizeSkip-th update) refresh delta, mark and

@@ -12,8 +12,9 @@ dense enough (an injected defect has to show).
 A case is a dict in the shape of schur_cases: graph, initial, ordering; plus
   fronts    the intended fronts in front order: dict(nf, n, parent, cls)   (asserted from a structure-only handle, no GPU)
   switches  environment the case runs under in its default comparison (one_panel: LMGPU_NO_MED)
-  launches  per solve, from reading the dispatch in csrc/lmgpu.hip: dict(panel, syrk, chain[, panel_work]) = launch counters of
-            kernel_times(); panel_work False = the batched medium path (its launches carry no flop count)
+  launches  per solve, from reading the planner (csrc/dense_schedule.hpp: dense_front_schedule) and the level loop of do_eliminate in
+            csrc/lmgpu.hip: dict(panel, syrk, chain[, panel_work]) = launch counters of kernel_times(); panel_work False = the batched
+            medium path (its launches carry no flop count)
 
 The cases (nf = frontal scalars of the front under test; a root has n = nf + 1):
   medium_batch         one graph, seven components with a dense front of nf = 63, 64, 65, 128, 193, 255, 256, all on level 0:
@@ -42,7 +43,7 @@ Departures from the plan the cases were drawn up from, each from reading the dis
     wide separator part.  (300, 138) and (1030, 66) take the per-front path by default.
   * beyond_1024 has six panels, not five (1290 = 5 x 256 + 10).
   * the launch counters cannot tell a dataflow panel from diag_potrf + panel_trsm (one counted event either way); which of the two a
-    size takes is `rows % 64 == 0`, asserted on the sizes themselves.
+    size takes is `rows % 64 == 0`, asserted on the planner's records (test_dense_schedule.py).
 """
 import functools
 
@@ -204,9 +205,10 @@ def _launches(panel, syrk, chain, panel_work=True):
 
 
 def front_launches(nf, n, two_launch=False, no_fuse=False, no_chain=False, no_tail=False):
-    """the launch counters one dense front on the per-front path adds per solve: the loop over outer panels of do_eliminate
-    (csrc/lmgpu.hip) restated -- dataflow_ok, fusable, chainable, the tail condition -- with the switches LMGPU_PANEL_2L, LMGPU_NO_FUSE,
-    LMGPU_NO_CHAIN, LMGPU_NO_TAIL.  The GPU test holds the library's own counters against it."""
+    """the launch counters one dense front on the per-front path adds per solve: the planner dense_front_schedule
+    (csrc/dense_schedule.hpp) restated -- dataflow_ok, fusable, chainable, the tail condition -- with the switches LMGPU_PANEL_2L,
+    LMGPU_NO_FUSE, LMGPU_NO_CHAIN, LMGPU_NO_TAIL.  test_dense_schedule.py holds the planner's records against it on the CPU, the GPU
+    test the library's own counters."""
     panels = -(-nf // 256)
 
     def rows(i):
@@ -256,7 +258,7 @@ def per_front_launches(fronts, switch=None):
     return out
 
 
-# per solve, by the dispatch of do_eliminate (rows(i) = rows of outer panel i, m = columns behind it):
+# per solve, by the planner dense_front_schedule (rows(i) = rows of outer panel i, m = columns behind it):
 #   panel 0 is one `panel` event; a run of >= 2 chainable steps one `chain` event; the tail kernel one `panel` event; a fused step one
 #   `syrk` launch; an unfused step one `syrk` event plus one `panel` event when a panel follows it
 _TAIL_LAUNCHES = {257: _launches(2, 0, 0), 303: _launches(2, 0, 0),  # panel 0, tail kernel
