@@ -651,11 +651,17 @@ __global__ __launch_bounds__(256) void hbm_backsolve_dataflow_kernel(FrontDesc F
 //     finished BEFORE x_{b+1} arrives: one 64 x 64 matrix-vector product behind the poll instead of the fold, an LDS round trip, a
 //     barrier and the product with the inverse.  (3) y = d is read from the front's right-hand-side column when the front has no
 //     separator (a root): no launch to copy it.  Measured on the C4 root (141 hops): see DESIGN.md section 6, round 3.
+// Since round 6 the product runs hbm_backsolve_wide_kernel (below) in its place; this form stays in the TEST library under
+// LMGPU_BACKSOLVE_HOP64 as the other arm of the A/B and a second opinion for the tests.  STAMP (tools/backsolve_bench.hip only):
+// block b leaves the 100 MHz clock at its start, when its neighbour's x arrived and after its own publish in stamps[3 b ..].
+#ifdef LMGPU_TEST_HOOKS
+template <bool STAMP = false>
 __global__ __launch_bounds__(256) void hbm_backsolve_dataflow2_kernel(FrontDesc F, int64_t f_off, int ld, const int32_t* __restrict__ fxoff,
                                                                        const double* __restrict__ pool, const double* __restrict__ inv16,
                                                                        const double* __restrict__ y /* nullptr: the rhs column itself */,
                                                                        double* __restrict__ xbuf, unsigned int* __restrict__ flags,
-                                                                       double* __restrict__ delta, int* __restrict__ status) {
+                                                                       double* __restrict__ delta, int* __restrict__ status,
+                                                                       unsigned long long* __restrict__ stamps = nullptr) {
   typedef double d4_t __attribute__((ext_vector_type(4)));
   constexpr int NB = 64;
   __shared__ double Rl[64][65];   // R_bb, then R_{b,b+1}
@@ -671,6 +677,7 @@ __global__ __launch_bounds__(256) void hbm_backsolve_dataflow2_kernel(FrontDesc 
   const int r0 = b * NB, nb = min(NB, F.nf - r0);
   const int tid = threadIdx.x, row = tid >> 2, quarter = tid & 3, lane = tid & 63, wave = tid >> 6;
   const int kk = lane >> 4, cc = lane & 15;
+  if (STAMP && tid == 0) stamps[3 * b] = wall_clock64();
   const double* A = pool + f_off;
   const int n = F.n;
   if (tid < NB) acc[tid] = (tid < nb) ? (y ? y[r0 + tid] : A[(size_t)(r0 + tid) * ld + n - 1]) : 0.0;
@@ -793,6 +800,7 @@ __global__ __launch_bounds__(256) void hbm_backsolve_dataflow2_kernel(FrontDesc 
   double xr;
   if (b + 1 < nblk && ok) {
     poll(b + 1);
+    if (STAMP && tid == 0) stamps[3 * b + 1] = wall_clock64();
     __syncthreads();
     double s = 0;
 #pragma unroll
@@ -811,6 +819,339 @@ __global__ __launch_bounds__(256) void hbm_backsolve_dataflow2_kernel(FrontDesc 
     delta[fxoff[F.fx_begin + r0 + row]] = xr;
     if (xr != xr) atomicMin(status, F.id);
   }
+  if (STAMP && tid == 0) stamps[3 * b + 2] = wall_clock64();
+}
+#endif  // LMGPU_TEST_HOOKS
+
+// ---- round 6: the same hop at twice the width.  The hop is a round trip between two CUs (an agent-scope store and a poll); its
+// length is the hardware's, so the chain gets shorter only by fewer hops: one workgroup per 128-row block B (71 hops at the C4 root
+// instead of 141), with the inverse of the whole 128 x 128 diagonal block EXPLICIT so that the hop stays one matrix-vector product
+// behind the poll with no hand-off inside the block.  A 128-row block is eight consecutive 16-blocks of one 256-row panel.
+//   build (while the workgroup waits for its turn; 64 x 64 tiles through LDS, matrix cores):
+//     X_11 = inv(R_11), X_22 = inv(R_22) by the block back-substitution over the 16 x 16 inverses of the factorisation (one wave
+//     each), X_12 = -X_11 (R_12 X_22);  M_B = X_B R_{B,B+1}: wave w makes rows 16 w .. 16 w + 15 of it in its accumulators and parks
+//     them in memory (mpark, 32 doubles per thread) -- the folds need the registers.  Every operand of the build is fetched at the
+//     top in one round trip.
+//   folds off the chain (j = last .. B+2): wave w owns rows 16 w .. of the block, a lane the columns `lane` and `64 + lane` of block
+//     j, which are the two values of x_j it polls itself: no barrier, no shuffle and no LDS on a fold; the per-lane partial sums of
+//     the 16 rows are reduced ONCE.  TWO tiles are in flight (64 + 64 registers): a workgroup has to stream 128 KB of R per hop to
+//     keep up with the chain, and with one tile in flight per wave the chain ran at the tile's round trip, 4.4 us, not at the hop's
+//     (DESIGN.md section 6, round 6).  M_B comes back in place of "tile B + 1", one fold ahead of the hop.
+//   u_B = X_B (y_B - folds) through LDS, before x_{B+1} arrives.
+//   hop: every wave polls x_{B+1} itself, passes it to its lanes through its own 1 KB of LDS (no workgroup barrier),
+//     x_B = u_B - M_B x_{B+1}  (four independent sums of eight per lane, then five shuffles over the 16 lanes of a row) and
+//     publishes its 16 rows.  A partial last block is identity-padded and publishes zeros for the rows past nf.
+// xbuf: 128 entries per block, preset to the sentinel; flags[gridDim.x] is the ticket.  Every spin is bounded (status[1]).
+__device__ __forceinline__ void bsw_invert64(const double (*Rl)[65], double (*Xl)[65], const double (*Il)[16][17], int kk, int cc) {
+  typedef double d4_t __attribute__((ext_vector_type(4)));
+  // block back-substitution on the matrix cores, one wave: X_hh = I_h;  X_gh = -I_g (sum_{k = g+1..h} R_gk X_kh)
+#pragma unroll
+  for (int h = 0; h < 4; h++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) Xl[16 * h + kk + 4 * r][16 * h + cc] = Il[h][kk + 4 * r][cc];
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int g = h - 1; g >= 0; g--) {
+      d4_t m = d4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int k = g + 1; k <= h; k++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) m = __builtin_amdgcn_mfma_f64_16x16x4f64(Rl[16 * g + cc][16 * k + 4 * r + kk], Xl[16 * k + 4 * r + kk][16 * h + cc], m, 0, 0, 0);
+      d4_t x = d4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int r = 0; r < 4; r++) x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Il[g][cc][4 * r + kk], m[r], x, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; r++) Xl[16 * g + kk + 4 * r][16 * h + cc] = x[r];
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+  }
 }
 
+#define BSW_NB 128
+#define BSW_SPIN_LIMIT 2000000L
+template <bool STAMP = false>
+__global__ __launch_bounds__(512) void hbm_backsolve_wide_kernel(FrontDesc F, int64_t f_off, int ld, const int32_t* __restrict__ fxoff,
+                                                                  const double* __restrict__ pool, const double* __restrict__ inv16,
+                                                                  const double* __restrict__ y /* nullptr: the rhs column itself */,
+                                                                  double* __restrict__ xbuf, unsigned int* __restrict__ flags,
+                                                                  double* __restrict__ delta, int* __restrict__ status,
+                                                                  double* mpark /* 128 x 128 doubles per block */,
+                                                                  unsigned long long* __restrict__ stamps = nullptr) {
+  typedef double d4_t __attribute__((ext_vector_type(4)));
+  constexpr int NB = BSW_NB;
+  __shared__ double T[4][64][65];  // build: R_11 R_22 X_11 X_22, then X_12 in [0] and the staging tile in [1]
+  __shared__ double Il[8][16][17];
+  __shared__ double rhs[NB], ub[NB];
+  __shared__ double xs[8][NB];  // a wave's own copy of x_{B+1}
+  __shared__ int s_ticket;
+  const int nblk = gridDim.x;
+  if (threadIdx.x == 0) s_ticket = (int)atomicAdd(&flags[nblk], 1u);
+  __syncthreads();
+  const int b = nblk - 1 - s_ticket;  // a workgroup only waits for workgroups that started before it
+  const int nf = F.nf, n = F.n;
+  const int r0 = b * NB, nb = min(NB, nf - r0);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kk = lane >> 4, cc = lane & 15;
+  const double* A = pool + f_off;
+  if (STAMP && tid == 0) stamps[3 * b] = wall_clock64();
+  // ---- what the end of the launch needs, fetched first: the row whose fold total wave_reduce_slots leaves in this lane, the row
+  // this lane publishes after the hop, their right-hand side / offset in delta
+  const int myslot = ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
+  const int frow = 16 * wave + myslot;
+  const int frc = min(r0 + frow, nf - 1);
+  const double yv = y ? y[frc] : A[(size_t)frc * ld + n - 1];
+  const int hr = 2 * ((cc >> 3) & 1) + ((cc >> 2) & 1);  // the hop's reduction leaves row 16 wave + kk + 4 hr in this lane
+  const int prow = 16 * wave + kk + 4 * hr;
+  const int po = fxoff[F.fx_begin + min(r0 + prow, nf - 1)];
+  // ---- everything the build reads from the front, fetched at once (one memory round trip instead of one per stage): thread (wave, lane)
+  // holds the entries (wave + 8 i, lane), i = 0..7, of each 64 x 64 piece.  R_BB is identity-padded in a partial block.
+  const bool has_next = b + 1 < nblk;
+  const int c0n = (b + 1) * NB, ncoln = has_next ? min(NB, nf - c0n) : 0;
+  double g11[8], g22[8], g12[8], gn[2][2][8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int p = wave + 8 * i, q = lane;
+    const double e = (p == q) ? 1.0 : 0.0;
+    g11[i] = (p < nb && q < nb && q >= p) ? A[(size_t)(r0 + p) * ld + r0 + q] : e;
+    g22[i] = (64 + p < nb && 64 + q < nb && q >= p) ? A[(size_t)(r0 + 64 + p) * ld + r0 + 64 + q] : e;
+    g12[i] = (p < nb && 64 + q < nb) ? A[(size_t)(r0 + p) * ld + r0 + 64 + q] : 0.0;
+#pragma unroll
+    for (int kh = 0; kh < 2; kh++)
+#pragma unroll
+      for (int ch = 0; ch < 2; ch++)
+        gn[kh][ch][i] = (64 * kh + p < nb && 64 * ch + q < ncoln) ? A[(size_t)(r0 + 64 * kh + p) * ld + c0n + 64 * ch + q] : 0.0;
+  }
+  // ---- X_11, X_22; a 16-block wholly past the block's rows counts as identity
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int p = wave + 8 * i, q = lane;
+    T[0][p][q] = g11[i];
+    T[1][p][q] = g22[i];
+    T[2][p][q] = 0.0;
+    T[3][p][q] = 0.0;
+  }
+  const double* I16 = inv16 + (size_t)(b >> 1) * 4096 + (size_t)(8 * (b & 1)) * 256;
+  for (int idx = tid; idx < 8 * 256; idx += 512) {
+    const int h = idx >> 8, i = (idx >> 4) & 15, j = idx & 15;
+    Il[h][i][j] = (16 * h < nb) ? I16[idx] : ((i == j) ? 1.0 : 0.0);
+  }
+  __syncthreads();
+  if (wave < 2) bsw_invert64(T[wave], T[2 + wave], Il + 4 * wave, kk, cc);
+  __syncthreads();
+  // ---- X_12 = -X_11 (R_12 X_22): R_12 into [0], W = R_12 X_22 into [1], X_12 into [0]; wave w makes two 16 x 16 tiles of each
+#pragma unroll
+  for (int i = 0; i < 8; i++) T[0][wave + 8 * i][lane] = g12[i];
+  __syncthreads();
+  {
+    const int ti = wave >> 1;
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int tj = 2 * (wave & 1) + u;
+      d4_t m = d4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 16; k++) m = __builtin_amdgcn_mfma_f64_16x16x4f64(T[0][16 * ti + cc][4 * k + kk], T[3][4 * k + kk][16 * tj + cc], m, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; r++) T[1][16 * ti + kk + 4 * r][16 * tj + cc] = m[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int tj = 2 * (wave & 1) + u;
+      d4_t m = d4_t{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < 16; k++) m = __builtin_amdgcn_mfma_f64_16x16x4f64(-T[2][16 * ti + cc][4 * k + kk], T[1][4 * k + kk][16 * tj + cc], m, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; r++) T[0][16 * ti + kk + 4 * r][16 * tj + cc] = m[r];
+    }
+    __syncthreads();
+  }
+  // ---- M_B = X_B R_{B,B+1}: rows 16 wave .. of it in mB[h][r] = M[16 wave + kk + 4 r][16 h + cc].  Four passes over 64 x 64 pieces of
+  // R_{B,B+1} staged in [1]: rows 0..63 meet X_11 (waves 0-3), rows 64..127 meet X_12 (waves 0-3) and X_22 (waves 4-7)
+  d4_t mB[8];
+#pragma unroll
+  for (int h = 0; h < 8; h++) mB[h] = d4_t{0, 0, 0, 0};
+  if (has_next) {
+#pragma unroll
+    for (int kh = 0; kh < 2; kh++) {
+#pragma unroll
+      for (int ch = 0; ch < 2; ch++) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) T[1][wave + 8 * i][lane] = gn[kh][ch][i];
+        __syncthreads();
+        if (wave < 4 || kh == 1) {
+          const double(*Xop)[65] = (wave >= 4) ? T[3] : (kh == 0 ? T[2] : T[0]);
+          const int xr0 = 16 * (wave & 3);
+#pragma unroll
+          for (int hh = 0; hh < 4; hh++)
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+              mB[4 * ch + hh] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xop[xr0 + cc][4 * k + kk], T[1][4 * k + kk][16 * hh + cc], mB[4 * ch + hh], 0, 0, 0);
+        }
+        __syncthreads();
+      }
+    }
+  }
+  // The folds need the registers (two tiles in flight): M_B waits in memory, 32 doubles per thread where that thread finds them
+  // again, and comes back in place of "tile B + 1", which is never folded -- one fold ahead of the hop.
+  double* Mp = mpark + (size_t)b * NB * NB + tid;
+  if (has_next) {
+#pragma unroll
+    for (int h = 0; h < 8; h++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) Mp[(4 * h + r) * 512] = mB[h][r];
+  }
+  // ---- the folds that are not on the chain.  (Every load is unconditional on a clamped address, as in hbm_backsolve_blocks_kernel.)
+  auto load_tile = [&](int j, double(&t)[32]) {
+    // tile j > B + 1: rows of this wave, columns `lane` and `64 + lane` of block j (only whole blocks fold: every row is there).
+    // j = B + 1: this thread's part of M_B.  j <= B: nothing is needed any more; one cached element, so that nothing long sits in
+    // front of the hop's poll (vector memory operations of a wave return in order).  In all three cases entry (2 k, 2 k + 1) is at
+    // base + k stride + (o0, o1) with base and stride the same for the whole wave.
+    const bool real = j > b + 1, parked = j == b + 1 && has_next;
+    const double* base = real ? A + (size_t)(r0 + 16 * wave) * ld : (parked ? mpark + (size_t)b * NB * NB : A + (size_t)r0 * ld);
+    const int stride = real ? ld : (parked ? 1024 : 0);
+    const int o0 = real ? min(NB * j + lane, nf - 1) : (parked ? tid : r0), o1 = real ? min(NB * j + 64 + lane, nf - 1) : (parked ? tid + 512 : r0);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const double* row = base + (size_t)k * stride;
+      t[2 * k] = row[o0];
+      t[2 * k + 1] = row[o1];
+    }
+  };
+  bool dead = false;
+  auto poll2 = [&](int j, double& x0, double& x1) {  // the two values of x_j this lane folds, by value: the buffer is preset to the sentinel
+    long spins = 0;
+    for (;;) {
+      x0 = __hip_atomic_load(&xbuf[NB * j + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      x1 = __hip_atomic_load(&xbuf[NB * j + 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (__double_as_longlong(x0) != -1LL && __double_as_longlong(x1) != -1LL) break;
+      if (dead || ++spins > BSW_SPIN_LIMIT) {
+        dead = true;
+        x0 = x1 = 0.0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+  };
+  // Two tiles are in flight.  Vector memory operations of a wave return in order, so a poll issued behind a tile's loads returns
+  // no sooner than the tile: the first look at x_{j-1} is therefore issued BEFORE the loads of tile j - 2, and only a workgroup that
+  // has caught up with the chain (it waits anyway) polls behind them.  A workgroup that lags streams R at two tiles per round trip.
+  auto look = [&](int j, double& x0, double& x1) {
+    x0 = __hip_atomic_load(&xbuf[NB * j + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x1 = __hip_atomic_load(&xbuf[NB * j + 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  double acc[16], ta[32], tb[32], e0, e1;
+#pragma unroll
+  for (int k = 0; k < 16; k++) acc[k] = 0.0;
+  look(nblk - 1, e0, e1);
+  __builtin_amdgcn_sched_barrier(0);  // (in this order, as in the loop: the compiler counts the loads in flight from here on)
+  load_tile(nblk - 1, ta);
+  __builtin_amdgcn_sched_barrier(0);
+  load_tile(nblk - 2, tb);
+  __builtin_amdgcn_sched_barrier(0);
+  auto fold = [&](int j, double(&t)[32]) {  // x_j into acc with tile j (in t), then tile j - 2 into t
+    double x0 = e0, x1 = e1;
+    if (__double_as_longlong(x0) == -1LL || __double_as_longlong(x1) == -1LL) poll2(j, x0, x1);
+    look(j - 1, e0, e1);
+    __builtin_amdgcn_sched_barrier(0);  // (the order of issue is the point: look, then the sums, then the whole tile)
+#pragma unroll
+    for (int k = 0; k < 16; k++) acc[k] = fma(t[2 * k + 1], x1, fma(t[2 * k], x0, acc[k]));
+    __builtin_amdgcn_sched_barrier(0);
+    load_tile(j - 2, t);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  {
+    int j = nblk - 1;
+    for (; j - 1 > b + 1; j -= 2) {  // whole pairs, so that the loads in flight are the same in number at every turn of the loop
+      fold(j, ta);
+      fold(j - 1, tb);
+    }
+    if (j > b + 1) fold(j, ta);
+  }
+  // ---- u_B = X_B (y_B - folds), before the neighbour's x is there
+  {
+    int slot;
+    const double tot = wave_reduce_slots<16>(acc, lane, slot);
+    if ((lane & 3) == 0) rhs[frow] = (frow < nb) ? yv - tot : 0.0;
+    __syncthreads();
+    const int row = tid >> 2, q = tid & 3;
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    if (row < 64) {  // 32 columns of [X_11 X_12]
+      const double* xr = (q < 2) ? &T[2][row][32 * q] : &T[0][row][32 * (q - 2)];
+      const double* rr = rhs + 32 * q;
+#pragma unroll
+      for (int k = 0; k < 32; k += 4) {
+        s0 = fma(xr[k], rr[k], s0);
+        s1 = fma(xr[k + 1], rr[k + 1], s1);
+        s2 = fma(xr[k + 2], rr[k + 2], s2);
+        s3 = fma(xr[k + 3], rr[k + 3], s3);
+      }
+    } else {  // 16 columns of X_22
+      const double* xr = &T[3][row - 64][16 * q];
+      const double* rr = rhs + 64 + 16 * q;
+#pragma unroll
+      for (int k = 0; k < 16; k += 4) {
+        s0 = fma(xr[k], rr[k], s0);
+        s1 = fma(xr[k + 1], rr[k + 1], s1);
+        s2 = fma(xr[k + 2], rr[k + 2], s2);
+        s3 = fma(xr[k + 3], rr[k + 3], s3);
+      }
+    }
+    double s = (s0 + s1) + (s2 + s3);
+    s += __shfl_xor(s, 1);
+    s += __shfl_xor(s, 2);
+    if (q == 0) ub[row] = s;
+    __syncthreads();
+  }
+  double xr = ub[prow];
+  // ---- the hop
+  if (has_next) {
+    double x0 = e0, x1 = e1;  // (the last look was at x_{B+1})
+    if (__double_as_longlong(x0) == -1LL || __double_as_longlong(x1) == -1LL) poll2(b + 1, x0, x1);
+    if (STAMP && tid == 0) stamps[3 * b + 1] = wall_clock64();
+    xs[wave][lane] = x0;
+    xs[wave][64 + lane] = x1;
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    double sa[4], sb[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) sa[r] = sb[r] = 0.0;
+    auto sums = [&](const double(&mv)[32]) {  // mv[4 h + r] = M[16 wave + kk + 4 r][16 h + cc]
+#pragma unroll
+      for (int h = 0; h < 8; h += 2) {
+        const double xa = xs[wave][16 * h + cc], xc = xs[wave][16 * h + 16 + cc];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          sa[r] = fma(mv[4 * h + r], xa, sa[r]);
+          sb[r] = fma(mv[4 * h + 4 + r], xc, sb[r]);
+        }
+      }
+    };
+    if (((nblk - b) & 1) == 0)  // "tile B + 1" went where the tiles of its parity go: nblk - 1, nblk - 3, .. into ta
+      sums(ta);
+    else
+      sums(tb);
+#pragma unroll
+    for (int r = 0; r < 4; r++) sa[r] += sb[r];
+    // rows 0..3 of this lane over its 16 columns' lanes: halve the values as the lanes are halved (wave_reduce_slots)
+    const bool h8 = (cc & 8) != 0, h4 = (cc & 4) != 0;
+    const double k0 = h8 ? sa[2] : sa[0], k1 = h8 ? sa[3] : sa[1], d0 = h8 ? sa[0] : sa[2], d1 = h8 ? sa[1] : sa[3];
+    const double t0 = k0 + __shfl_xor(d0, 8), t1 = k1 + __shfl_xor(d1, 8);
+    double v = (h4 ? t1 : t0) + __shfl_xor(h4 ? t0 : t1, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    xr -= v;
+  }
+  if ((cc & 3) == 0) {
+    const double pub = (prow < nb) ? ((xr != xr) ? __longlong_as_double(0x7ff8000000000000LL) : xr) : 0.0;  // never the sentinel
+    __hip_atomic_store(&xbuf[r0 + prow], pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (prow < nb) {
+      delta[po] = xr;
+      if (xr != xr) atomicMin(status, F.id);
+    }
+  }
+  if (STAMP && tid == 0) stamps[3 * b + 2] = wall_clock64();
+  if (__any(dead) && lane == 0) atomicExch(status + 1, 1 + F.id);  // never expected: spin bound hit (a fault, reported apart from pivot failures)
+}
 }  // namespace lmgpu

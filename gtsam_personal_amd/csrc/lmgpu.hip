@@ -1151,19 +1151,28 @@ int do_backsub(lmgpu_handle* h) {
       const int64_t off = h->f_off[fi];
       const int ld = h->f_ld[fi];
       const int kt = h->kt.begin(LMGPU_KT_BACKSUB_HBM, s);
-      const int nblk = (F.nf + NB - 1) / NB;
       const bool has_sep = F.n - F.nf - 1 > 0;
       if (has_sep)  // y = d - S x_S (a root reads d in place)
         hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
                            (const double*)h->delta, h->ywork);
       // ONE dataflow launch: workgroup b waits for x_j (j > b); the inverses of the diagonal blocks are built inside it when the 16 x 16
-      // inverses of this front's factorisation are still there (else by a launch of their own in front of it)
+      // inverses of this front's factorisation are still there (else by a launch of their own in front of it).  128-row blocks with
+      // explicit inverses then (hbm_backsolve_wide_kernel); 64-row blocks in the fallback and, test library only, under LMGPU_BACKSOLVE_HOP64
+      const bool reuse = h->inv16_owner == fi && !dev_switch("LMGPU_NO_INV16_REUSE");
+      const bool wide = reuse && !dev_switch("LMGPU_BACKSOLVE_HOP64");
+      const int bw = wide ? BSW_NB : NB, nblk = (F.nf + bw - 1) / bw;
       HIPCHECK(hipMemsetAsync(h->bs_flags, 0, (nblk + 1) * sizeof(unsigned int), s));  // flags + ticket
-      HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * NB * sizeof(double), s));  // sentinel: "not published yet"
-      if (h->inv16_owner == fi && !dev_switch("LMGPU_NO_INV16_REUSE")) {
-        hipLaunchKernelGGL(hbm_backsolve_dataflow2_kernel, dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
+      HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * bw * sizeof(double), s));  // sentinel: "not published yet"
+      if (wide) {
+        hipLaunchKernelGGL((hbm_backsolve_wide_kernel<false>), dim3(nblk), dim3(512), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
                            (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
-                           h->d_status);
+                           h->d_status, h->bs_inv, (unsigned long long*)nullptr);
+#ifdef LMGPU_TEST_HOOKS
+      } else if (reuse) {
+        hipLaunchKernelGGL((hbm_backsolve_dataflow2_kernel<false>), dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
+                           (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
+                           h->d_status, (unsigned long long*)nullptr);
+#endif
       } else {
         if (!has_sep)
           hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
@@ -2884,12 +2893,14 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
     for (int fi = 0; fi < NF; fi++)
       if (h->front_active[fi] && P.fronts[fi].cls == 1) max_nf = std::max(max_nf, P.fronts[fi].nf);
     const int max_blk = (max_nf + NB - 1) / NB;
-    HIPCHECK(hipMalloc((void**)&h->bs_inv, (size_t)max_blk * NB * NB * sizeof(double)));
+    // (inverses of the 64 x 64 diagonal blocks in the fallback; the wide form parks M_B there, 128 x 128 per 128-row block)
+    HIPCHECK(hipMalloc((void**)&h->bs_inv, (size_t)((max_nf + BSW_NB - 1) / BSW_NB) * BSW_NB * BSW_NB * sizeof(double)));
     HIPCHECK(hipMalloc((void**)&h->inv16, (size_t)((P.max_front_n + NBO - 1) / NBO + 2) * 16 * 256 * sizeof(double)));  // 16 blocks per outer panel
     h->pflags_panels = (P.max_front_n + NBO - 1) / NBO + 1;
     HIPCHECK(hipMalloc((void**)&h->d_pflags, (size_t)h->pflags_panels * PDF_FLAG_WORDS * sizeof(unsigned int)));
 
-    HIPCHECK(hipMalloc((void**)&h->bs_x, (size_t)max_blk * NB * sizeof(double)));
+    // (x of the dataflow back-substitutions: whole 128-row blocks for the wide form, which covers the 64-row blocks of the others)
+    HIPCHECK(hipMalloc((void**)&h->bs_x, (size_t)((max_nf + BSW_NB - 1) / BSW_NB) * BSW_NB * sizeof(double)));
     HIPCHECK(hipMalloc((void**)&h->bs_flags, (size_t)(max_blk + 1) * sizeof(unsigned int)));
   }
   return LMGPU_OK;
