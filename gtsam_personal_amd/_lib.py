@@ -179,6 +179,8 @@ SYMBOLS = {
     "lmgpu_joint_marginal_covariance": (ct.c_int, [_H, ct.c_int32, _I, _D]),
     "lmgpu_selftest_chain_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
     "lmgpu_selftest_dense_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_uint, ct.c_int, _I]),
+    "lmgpu_selftest_dogleg_step": (ct.c_int, [ct.c_int, _D, _D]),
+    "lmgpu_bt_products": (ct.c_int, [_H, _D, ct.c_double, _D, _D]),
     "lmgpu_isam2_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(_H)]),
     "lmgpu_isam2_destroy": (ct.c_int, [_H]),
     "lmgpu_isam2_last_error": (ct.c_char_p, [_H]),

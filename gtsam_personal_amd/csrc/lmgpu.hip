@@ -33,6 +33,7 @@
 #include "kernels_potrf.hpp"
 #include "kernels_step.hpp"
 #include "dense_schedule.hpp"
+#include "dogleg_step.hpp"
 #include "kernels_batched.hpp"
 #include "kernels_level.hpp"
 #include "kernels_bayes.hpp"
@@ -1789,17 +1790,13 @@ int dl_iterate(lmgpu_handle* h) {
   double new_f = f_error;
   bool stay = true, moved = true;
   while (stay) {
-    // ComputeDoglegPoint / ComputeBlend
-    const double deltaSq = delta * delta;
-    if (deltaSq < uu) {
-      const double f = std::sqrt(deltaSq / uu);
+    // ComputeDoglegPoint / ComputeBlend (dogleg_step.hpp)
+    const DoglegTrial trial = dogleg_trial_point(delta, uu, nn, un);
+    if (trial.branch == DOGLEG_STEEPEST) {
+      const double f = trial.scalar;
       for (int i = 0; i < n; i++) dx_d[i] = f * dx_u[i];
-    } else if (deltaSq < nn) {
-      const double a = uu - 2. * un + nn, b = 2. * (un - uu), c = uu - delta * delta;
-      const double sq = std::sqrt(b * b - 4 * a * c);
-      const double tau1 = (-b + sq) / (2. * a), tau2 = (-b - sq) / (2. * a);
-      const double eps = std::numeric_limits<double>::epsilon();
-      const double tau = (-eps <= tau1 && tau1 <= 1.0 + eps) ? tau1 : tau2;
+    } else if (trial.branch == DOGLEG_BLEND) {
+      const double tau = trial.scalar;
       for (int i = 0; i < n; i++) dx_d[i] = (1. - tau) * dx_u[i] + tau * dx_n[i];
     } else {
       dx_d = dx_n;
@@ -1815,26 +1812,14 @@ int dl_iterate(lmgpu_handle* h) {
     new_f = h->h_scal[0];
     h->tim.inner_iterations += 1;
     const double rho = (std::abs(f_error - new_f) < 1e-15 || std::abs(M_error - new_M) < 1e-15) ? 0.5 : (f_error - new_f) / (M_error - new_M);
-    if (rho >= 0.75) {
-      double nd = 0;
+    double nd = 0;
+    if (rho >= 0.75)
       for (int i = 0; i < n; i++) nd += dx_d[i] * dx_d[i];
-      delta = std::max(delta, 3.0 * std::sqrt(nd));
-      stay = false;
-    } else if (rho >= 0.25) {
-      stay = false;
-    } else if (rho >= 0.0) {
-      if (delta > 1e-5) delta *= 0.5;
-      stay = false;  // ONE_STEP_PER_ITERATION
-    } else {  // f increased (NaN lands here too): halve the radius until it does not
-      if (delta > 1e-5) {
-        delta *= 0.5;
-        stay = true;
-      } else {
-        moved = false;  // dx_d = 0: keep the values, keep the error
-        new_f = f_error;
-        stay = false;
-      }
-    }
+    const DoglegRadius upd = dogleg_radius_update(rho, delta, std::sqrt(nd));  // (a NaN rho: f increased)
+    delta = upd.delta;
+    stay = upd.stay;
+    moved = upd.moved;
+    if (!moved) new_f = f_error;  // dx_d = 0: keep the values, keep the error
   }
   if (moved) {
     h->cur ^= 1;
@@ -3222,6 +3207,32 @@ int lmgpu_dl_iterate(lmgpu_handle* h, lmgpu_lm_state* inout) {
   if (inout) *inout = h->lm;
   return rc;
 }
+// Read-only tap on the Bayes-tree products of the last solve (bt_gradient, bt_forward): h->delta, the values and the optimizer state
+// stay as they are; h->bt_vec is the scratch vector dl_iterate overwrites first thing.
+int lmgpu_bt_products(lmgpu_handle* h, const double* x_packed, double alpha, double* sq_norm, double* gradient_packed) {
+  if (!h) return LMGPU_INVALID;
+  if (!h->finalized || h->cfg.world_size > 1 || h->solver == LMGPU_SOLVER_PCG || !h->solved) {
+    h->err = "lmgpu_bt_products: needs a finalized single-rank handle of the direct solver with a factor in the pool (call lmgpu_solve first)";
+    return LMGPU_INVALID;
+  }
+  int rc = need_device(h);
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+  const int n = h->ntot;
+  if (!h->bt_vec) HIPCHECK(hipMalloc((void**)&h->bt_vec, std::max(1, n) * sizeof(double)));
+  if (gradient_packed) {
+    rc = bt_gradient(h);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(gradient_packed, h->bt_vec, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
+  if (x_packed && sq_norm) {
+    HIPCHECK(hipMemcpyAsync(h->bt_vec, x_packed, n * sizeof(double), hipMemcpyHostToDevice, s));
+    rc = bt_forward(h, h->bt_vec, alpha, sq_norm);  // synchronises
+    if (rc) return rc;
+  }
+  return LMGPU_OK;
+}
 int lmgpu_dl_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* inout) {
   if (!h) return LMGPU_INVALID;
   if (!p || !h->finalized || !h->have_values) {
@@ -3918,6 +3929,25 @@ int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int m
     out = std::copy(rec, rec + 4, out);
   }
   return (int)steps.size();
+}
+// Host-only view of the arithmetic of one Dogleg trial (dogleg_step.hpp).  which = 0: in = (delta, uu, nn, un), out = (branch, scalar);
+// which = 1: in = (rho, delta, |dx_d|), out = (new delta, stay, moved).  0, or -1 for a missing argument or an unknown `which`.
+int lmgpu_selftest_dogleg_step(int which, const double* in, double* out) {
+  if (!in || !out) return -1;
+  if (which == 0) {
+    const DoglegTrial t = dogleg_trial_point(in[0], in[1], in[2], in[3]);
+    out[0] = t.branch;
+    out[1] = t.scalar;
+    return 0;
+  }
+  if (which == 1) {
+    const DoglegRadius r = dogleg_radius_update(in[0], in[1], in[2]);
+    out[0] = r.delta;
+    out[1] = r.stay ? 1.0 : 0.0;
+    out[2] = r.moved ? 1.0 : 0.0;
+    return 0;
+  }
+  return -1;
 }
 // Host-only check of the ticket order of a chained launch (kernels_step.hpp: chain_schedule): every logical workgroup of every
 // step exactly once, and every dependency step_body waits for at an earlier ticket.  0 = valid, else the 1-based ticket at fault.

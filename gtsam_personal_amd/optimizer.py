@@ -370,6 +370,15 @@ class LevenbergMarquardtOptimizer:
         return self.delta_by_key(d)
 
     # ------------------------------------------------------------ parity taps
+    def bt_products(self, x=None, alpha=0.0):
+        """the Dogleg's two products with the Bayes tree of the last solve (lmgpu_bt_products; nothing on the device changes):
+        (sum over the cliques of ||[R S] x - alpha d||^2, or None without x;  the gradient - sum [R S]^T d), both packed by slot"""
+        g, sq = np.empty(self._ntot), ct.c_double()
+        xp = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+        assert xp is None or xp.shape == (self._ntot,)
+        self._check(self.lib.lmgpu_bt_products(self._h, None if xp is None else _dp(xp), float(alpha), ct.byref(sq), _dp(g)))
+        return (None if xp is None else sq.value), g
+
     def jacobian(self, graph_index):
         r, c = ct.c_int32(), ct.c_int32()
         self._check(self.lib.lmgpu_get_jacobian(self._h, graph_index, None, ct.byref(r), ct.byref(c)))

@@ -217,6 +217,13 @@ int lmgpu_dl_iterate(lmgpu_handle* h, lmgpu_lm_state* inout);
 int lmgpu_dl_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* inout);
 int lmgpu_get_timings(const lmgpu_handle* h, lmgpu_timings* out);
 
+/* Read-only tap on the two products DoglegOptimizer takes with the Bayes tree of the last solve, read as a GaussianFactorGraph of
+ * unit-noise Jacobian factors [R S | d], one per clique (gtsam/linear/GaussianBayesTree.cpp:73-92): gradient_packed (if not NULL) =
+ * - sum_c [R S]^T d (GaussianFactorGraph::gradientAtZero, GaussianFactorGraph.cpp:369-378); *sq_norm (if x_packed and sq_norm are not
+ * NULL) = sum_c ||[R S] x - alpha d||^2.  Vectors are packed by slot like lmgpu_solve's delta_packed.  Needs a finalized single-rank
+ * handle of the direct solver that has solved (else LMGPU_INVALID); the step, the values and the LM / Dogleg state are not touched. */
+int lmgpu_bt_products(lmgpu_handle* h, const double* x_packed, double alpha, double* sq_norm, double* gradient_packed);
+
 /* ---- linear solver: NonlinearOptimizerParams::linearSolverType (gtsam/nonlinear/NonlinearOptimizerParams.h; dispatch
  *      NonlinearOptimizer.cpp:154-173).  LMGPU_SOLVER_PCG = Iterative with PCGSolverParameters (gtsam/linear/PCGSolver.h:36-50):
  *      preconditionedConjugateGradient (gtsam/linear/ConjugateGradientSolver.h:109-171) on A = sum J^T J + lambda D, b = -gradientAtZero
@@ -494,6 +501,13 @@ int lmgpu_selftest_chain_schedule(int n, int nf, int i0, int nsteps, int far_pct
  * number of records; negative for refused geometry (n <= 0, nf <= 0, nf > n, unknown mode) or more than max_records records.  No
  * reference counterpart (see lmgpu_selftest_chain_schedule); it is what the elimination runs, so the CPU test-suite can pin it. */
 int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int max_records, int32_t* out);
+
+/* Host-only self-test (no GPU work, no handle): the arithmetic of one Dogleg trial as lmgpu_dl_iterate runs it.  which = 0, the trial
+ * point (DoglegOptimizerImpl::ComputeDoglegPoint / ComputeBlend, DoglegOptimizerImpl.cpp:26-91): in = (delta, dx_u . dx_u, dx_n . dx_n,
+ * dx_u . dx_n), out = (branch: 0 steepest-descent cut, 1 blend, 2 Newton step; its scalar: the factor on dx_u, tau, 1).  which = 1, the
+ * radius update (DoglegOptimizerImpl.h:139-254, ONE_STEP_PER_ITERATION): in = (rho, delta, |dx_d|), out = (new delta, 1 if the trial is
+ * repeated with it, 0 if the step is dropped at the radius floor else 1).  Returns 0; -1 for a NULL argument or an unknown `which`. */
+int lmgpu_selftest_dogleg_step(int which, const double* in, double* out);
 
 /* ---- ISAM2 (gtsam/nonlinear/ISAM2.h): incremental smoothing on a device-resident Bayes tree (BASELINE config 5) ----
  * ISAM2::update(newFactors, newTheta) (gtsam/nonlinear/ISAM2.cpp:419-480) = lmgpu_isam2_add_variables + lmgpu_isam2_add_factors

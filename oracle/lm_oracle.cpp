@@ -1337,6 +1337,7 @@ static bool dl_iterate(Problem& p) {
     const Values x_d = retract_all(p.values, dx_d);
     new_f = graph_error(p, x_d);
     const double new_M = 0.5 * bt_residual_sq(p.bt, dx_d, 1.0);
+    p.totalInner += 1;  // one per trial point
     const double rho = (std::abs(f_error - new_f) < 1e-15 || std::abs(M_error - new_M) < 1e-15) ? 0.5 : (f_error - new_f) / (M_error - new_M);
     if (rho >= 0.75) {
       const double nrm = std::sqrt(vv_dot(dx_d, dx_d));
