@@ -4,11 +4,14 @@
 // where a factor only touches ONE separator variable (its other variable is the leaf's frontal one), so the first term
 // is block-diagonal.  Instead of every leaf scattering its dense (ns+1)^2 update (BAL: 100 000 x 4186 FP64 atomics =
 // 3.35 GB of atomic traffic), the parent GATHERS:
-//   schur_pairs_kernel    per destination block (variable pair a <= b of the parent, or (a, rhs)):
+//   schur_pairs_kernel    per destination block (variable pair a < b of the parent):
 //                         A[a][b] -= sum over the leaves that see both of S_a^T S_b   (reads the leaves' [R S d] rows,
 //                         which are in HBM anyway for the back-substitution; the 218 MB of S at C4 sit in the Infinity Cache)
-//   schur_factor_kernel   per separator variable: A[v][v] += sum A_v^T A_v,  A[v][rhs] += sum A_v^T b
-//   the (rhs, rhs) corner is a fixed-order reduction of one scalar per leaf.
+//   schur_var_kernel      per separator variable v, one walk over the leaves that see it and their factors on it:
+//                         A[v][v | rhs] += sum A_v^T [A_v b] - sum S_v^T [S_v d];
+//                         its extra workgroup adds the (rhs, rhs) corner, a fixed-order reduction of one scalar per leaf.
+//   (test library, LMGPU_SCHUR_SPLIT_DIAG: the earlier form -- (v, v) and (v, rhs) as pair blocks, schur_factor_kernel for the factor
+//    terms, the corner through the scalar reduction)
 // Every destination entry is owned by exactly one lane, source lists have a fixed order and long lists are cut into
 // fixed contiguous chunks (one per wave) whose partial sums are added in chunk order => reproducible sums.
 // Entries are self-contained 16-byte records, fetched 64 at a time by the lanes and broadcast with v_readlane, so the only
@@ -35,11 +38,12 @@ struct GPairEntry {  // 16 bytes
 struct GVarBlock {
   int32_t pv;       // parent column of the variable
   int16_t dv, pad;
-  int32_t begin, count;
+  int32_t begin, count;  // the variable's entries: lcount leaf entries, then count - lcount factor entries
+  int32_t lcount;        // (0 in the split-diagonal form, where the leaves' (v, v) and (v, rhs) terms are pair blocks)
 };
-struct GVarEntry {   // 16 bytes
-  int64_t joff;      // pool offset of the factor's [A b]
-  int16_t rows, c0, cb, pad;  // rows, first column of the separator variable, column of b
+struct GVarEntry {   // 16 bytes: a column-major block of `rows` rows at pool offset joff -- a leaf factor's [A b] or, as a
+  int64_t joff;      // leaf entry, the leaf's transposed [S d] (rows = nf of the leaf)
+  int16_t rows, c0, cb, pad;  // rows, first column of the separator variable, column of b (of d)
 };
 
 typedef double double4s_t __attribute__((ext_vector_type(4)));
@@ -176,6 +180,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(8, 8
   }
 }
 
+#ifdef LMGPU_TEST_HOOKS
+// The split-diagonal form (LMGPU_SCHUR_SPLIT_DIAG, test library only: the A/B partner and cross-check of schur_var_kernel below): the
+// leaves' (v, v) and (v, rhs) terms are pair blocks of schur_pairs_kernel, the factor terms and the corner come from the two kernels here.
 // 16 waves per separator variable (BAL: ~1000 factors per camera):  [A_v^T A_v | A_v^T b]  as one MFMA per factor,
 // A operand lane (i, k): A_v[k][i];  B operand lane (j, k): A_v[k][j] for j < d, b[k] for j == d.
 #define SCHUR_FW 16
@@ -274,6 +281,176 @@ __global__ __launch_bounds__(64 * SCHUR_FW) void schur_factor_kernel(const GVarB
 }
 
 __global__ void add_scalar_kernel(double* __restrict__ dst, const double* __restrict__ src) { *dst += *src; }
+#endif  // LMGPU_TEST_HOOKS
+
+// ---- one pass per separator variable v: both of its blocks, (v, v) and (v, rhs), from ONE load per list entry.
+//     D = sum_{leaf factors f on v} A_v^T [A_v b]  -  sum_{leaves l that see v} S_v^T [S_v d]          (dv x (dv + 1))
+// is one 16 x 16 MFMA tile: lane (cc, kk) loads element [kk][cc] of the entry's block -- column cc < dv of S_v (A_v), or d (b) for
+// cc == dv -- and hands it to the MFMA as the B operand and, for cc < dv, as the A operand too (negated for a leaf entry, which
+// is exact: the leaves' part is subtracted inside the same accumulators).  dv + 1 <= 16 (the host checks).
+//   leaf entries     nf <= 4: one MFMA each.
+//   factor entries   two list neighbours (positions 2i, 2i + 1 of the wave's chunk) of at most two rows each share one MFMA:
+//                    k-slots 0-1 carry the first, 2-3 the second; the last of an odd chunk goes alone in slots 0-1.
+//   a round is SCHUR_VU MFMAs: its SCHUR_VU (2 SCHUR_VU) entries are loaded with masked loads, waited for once, multiplied.  A round
+//   that holds a wider entry (nf > 4; a factor of more than two rows) takes every entry of it alone and loops over k0 = 0, 4, ...
+//   (factors of 3-4 rows: one MFMA each).
+// Order of the sums (fixed => two identical solves are bitwise equal): a wave takes one contiguous chunk of the leaf entries, then one
+// of the factor entries (chunk = ceil(count / WAVES), rounded up to even for the factors so that the pairs do not depend on WAVES'
+// remainder); MFMA j of a round goes to accumulator j mod 2 on the masked path (on the k0 path: entry u of its group of two to
+// accumulator u), in list order, the leaf list before the factor list; the wave's sum is acc0 + acc1; wave 0 adds the waves' sums in
+// wave order, starting from 0, and stores cur + sum (sum in write mode).  Positive and negative terms are thus combined inside the
+// accumulators, entry by entry, never as two totals.
+// grid = nblocks + (ncorner > 0): the extra workgroup sums the leaves' (rhs, rhs) scalars -- thread t takes t, t + T, ... in order,
+// then a fixed tree over the threads -- and adds the sum to (writes it into) the front's corner.
+// (tests/schur_var_cases.py restates SCHUR_VU, SCHUR_VAR_SHORT, SCHUR_VAR_WAVES and the 64-entry fetch: its list lengths sit at these
+//  boundaries, and tests/test_schur_var_cases.py reads the defines below to hold the two files together)
+#ifndef SCHUR_VU
+#define SCHUR_VU 8    // MFMAs (= masked loads) in flight per wave and round (8 or 4)
+#endif
+#define SCHUR_VACC 2  // accumulators they alternate between
+#define SCHUR_VAR_SHORT 32  // variables with at most this many leaf entries and at most this many factor entries: one wave
+#ifndef SCHUR_VAR_WAVES
+#define SCHUR_VAR_WAVES 8   // the others
+#endif
+
+template <bool LEAF>
+__device__ __forceinline__ void schur_var_walk(const GVarEntry* __restrict__ entries, int cb, int ce, const double* __restrict__ pool, int dv,
+                                               int lane, double4s_t (&acc)[SCHUR_VACC]) {
+  constexpr int PER = LEAF ? 1 : 2;      // entries per MFMA on the masked path
+  constexpr int MAXROWS = LEAF ? 4 : 2;  // rows of an entry on the masked path
+  constexpr int NE = SCHUR_VU * PER;     // entries per round
+  const int kk = lane >> 4, cc = lane & 15;
+  const bool va = cc < dv, vb = cc <= dv;
+  const bool second = !LEAF && kk >= 2;  // (this lane holds an element of the second entry of its pair)
+  const int kr = LEAF ? kk : (kk & 1);   // row inside the entry
+  for (int base = cb; base < ce; base += 64) {
+    const int cnt = min(64, ce - base);
+    long long moff = 0, mmeta = 0;
+    if (lane < cnt) {
+      const GVarEntry E = entries[base + lane];
+      moff = E.joff;
+      mmeta = ((long long)(unsigned short)E.rows) | ((long long)(unsigned short)E.c0 << 16) | ((long long)(unsigned short)E.cb << 32);
+    }
+    const unsigned long long wide = __builtin_amdgcn_ballot_w64((int)(mmeta & 0xffff) > MAXROWS);  // (the entries this batch cannot take masked)
+    for (int e = 0; e < cnt; e += NE) {
+      if (((wide >> e) & ((1ull << NE) - 1)) == 0) {  // (wave-uniform)
+        double v[SCHUR_VU];
+        bool kv[SCHUR_VU];
+#pragma unroll
+        for (int u = 0; u < SCHUR_VU; u++) {
+          const int e0 = min(e + u * PER, cnt - 1), e1 = min(e + u * PER + PER - 1, cnt - 1);
+          const long long off0 = readlane_ll(moff, e0), meta0 = readlane_ll(mmeta, e0);
+          const long long off1 = readlane_ll(moff, e1), meta1 = readlane_ll(mmeta, e1);
+          const long long off = second ? off1 : off0, meta = second ? meta1 : meta0;
+          const bool valid = e + u * PER + (second ? 1 : 0) < cnt;
+          const int rows = (int)(meta & 0xffff), c0 = (int)((meta >> 16) & 0xffff), cbc = (int)((meta >> 32) & 0xffff);
+          kv[u] = valid && vb && kr < rows;
+          v[u] = schur_load_masked(pool + off + (va ? c0 + cc : cbc) * rows + kr, __builtin_amdgcn_ballot_w64(kv[u]));
+        }
+#if SCHUR_VU == 8
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])::"memory");
+#else
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])::"memory");
+        static_assert(SCHUR_VU == 4, "the wait above names four values");
+#endif
+#pragma unroll
+        for (int u = 0; u < SCHUR_VU; u++) {
+          const double b = kv[u] ? v[u] : 0.0;
+          const double a = va ? (LEAF ? -b : b) : 0.0;
+          acc[u % SCHUR_VACC] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[u % SCHUR_VACC], 0, 0, 0);
+        }
+        continue;
+      }
+      for (int q = 0; q < NE && e + q < cnt; q += SCHUR_VACC) {
+#pragma unroll
+        for (int u = 0; u < SCHUR_VACC; u++) {
+          const int eq = e + q + u;
+          if (eq >= cnt) continue;  // (wave-uniform: the short last group)
+          const long long off = readlane_ll(moff, eq), meta = readlane_ll(mmeta, eq);
+          const int rows = (int)(meta & 0xffff), c0 = (int)((meta >> 16) & 0xffff), cbc = (int)((meta >> 32) & 0xffff);
+          const double* J = pool + off;
+          for (int k0 = 0; k0 < rows; k0 += 4) {
+            const int k = k0 + kk;
+            const bool kb = vb && k < rows;
+            const double x = J[kb ? (va ? c0 + cc : cbc) * rows + k : 0];
+            const double b = kb ? x : 0.0;
+            const double a = va ? (LEAF ? -b : b) : 0.0;
+            acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[u], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void schur_var_kernel(
+    const GVarBlock* __restrict__ blocks, const GVarEntry* __restrict__ entries, double* __restrict__ pool, int64_t f_off, int ld, int n, int nblocks,
+    int write_mode, const double* __restrict__ corner, int ncorner) {
+  __shared__ double part[WAVES][4][64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double* A = pool + f_off;
+  if ((int)blockIdx.x >= nblocks) {  // the (rhs, rhs) corner
+    double* red = &part[0][0][0];
+    constexpr int T = 64 * WAVES;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < ncorner; i += T) s += corner[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = T / 2; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      double* dst = A + (size_t)(n - 1) * ld + n - 1;
+      *dst = (write_mode & 1) ? red[0] : *dst + red[0];
+    }
+    return;
+  }
+  const GVarBlock B = blocks[blockIdx.x];
+  const int d = B.dv, kk = lane >> 4, cc = lane & 15;
+  double4s_t acc[SCHUR_VACC];
+#pragma unroll
+  for (int u = 0; u < SCHUR_VACC; u++) acc[u] = double4s_t{0, 0, 0, 0};
+  {
+    const int per = (B.lcount + WAVES - 1) / WAVES;
+    const int cb = B.begin + wave * per;
+    schur_var_walk<true>(entries, cb, min(B.begin + B.lcount, cb + per), pool, d, lane, acc);
+  }
+  {
+    const int fb = B.begin + B.lcount, fe = B.begin + B.count;
+    const int per = (((fe - fb) + WAVES - 1) / WAVES + 1) & ~1;
+    const int cb = fb + wave * per;
+    schur_var_walk<false>(entries, cb, min(fe, cb + per), pool, d, lane, acc);
+  }
+  static_assert(SCHUR_VACC == 2, "the sum below names two accumulators");
+  double4s_t sum = acc[0] + acc[1];
+  if (WAVES > 1) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) part[wave][r][lane] = sum[r];
+    __syncthreads();
+    if (wave != 0) return;
+    sum = double4s_t{0, 0, 0, 0};
+#pragma unroll 2  // (all 4 WAVES loads in flight at once would not fit the 64 registers of eight waves per SIMD)
+    for (int w = 0; w < WAVES; w++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) sum[r] += part[w][r][lane];
+  }
+  double cur[4] = {0.0, 0.0, 0.0, 0.0};
+  if (!(write_mode & 1)) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int i = min(kk + 4 * r, d - 1);
+      cur[r] = A[(size_t)(B.pv + i) * ld + (cc < d ? B.pv + cc : n - 1)];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int i = kk + 4 * r, j = cc;
+    if (i < d && ((j < d && i <= j) || j == d)) A[(size_t)(B.pv + i) * ld + (j < d ? B.pv + j : n - 1)] = cur[r] + sum[r];
+  }
+}
 
 // upper blocks of a front that no gather list covers (write-mode gather: nothing else initialises them)
 struct GZeroBlock {

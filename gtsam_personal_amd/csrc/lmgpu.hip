@@ -340,9 +340,7 @@ struct lmgpu_handle {
   // gather-mode (Schur form) assembly of HBM fronts from their leaf children
   struct GatherRange {
     int pblk_begin = 0, pblk_short = 0, pblk_long = 0, vblk_begin = 0, vblk_count = 0, leaf_begin = 0, leaf_count = 0;  // short blocks first
-    // blocks are sorted by destination row: [cs[c], cs[c+1]) = short pair blocks whose rows lie in row chunk c (256 rows),
-    // likewise cl (long pair blocks) and cv (variable blocks); offsets relative to the three list starts
-    std::vector<int> cs, cl, cv;
+    int vblk_short = 0;  // variable blocks of at most SCHUR_VAR_SHORT leaf and factor entries (they come first; split-diagonal form: 0)
     // write mode: every contribution to the front's upper triangle before the gather comes from the gather itself (all children are
     // gather leaves), so the gather writes its blocks and only the blocks no list covers are cleared: [zero_begin, +zero_count)
     bool write_ok = false;
@@ -353,6 +351,7 @@ struct lmgpu_handle {
   GZeroBlock* d_gzero = nullptr;
   int n_hbm_fronts = 0;          // number of HBM-class fronts on this rank (selects the clearing regime in do_eliminate)
   bool no_gather_write = false;  // LMGPU_NO_GATHER_WRITE=1: clear the front and add (A/B)
+  bool schur_split_diag = false; // LMGPU_SCHUR_SPLIT_DIAG (test library): (v, v) and (v, rhs) as pair blocks + schur_factor_kernel (A/B)
   GPairEntry* d_gpent = nullptr;
   GVarBlock* d_gvblk = nullptr;
   GVarEntry* d_gvent = nullptr;
@@ -923,6 +922,7 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       if (!gwrite && own_terms) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
       // leaf children in Schur form: deterministic gather instead of atomics
       const int schur_masked = dev_switch("LMGPU_SCHUR_UNMASKED") ? 0 : 2;  // (operand loads that only the lanes holding an element take part in)
+      // (LMGPU_SCHUR_UNMASKED reaches schur_pairs_kernel and the split form's schur_factor_kernel; schur_var_kernel has the masked loads only)
       if (G.pblk_short > 0)
         hipLaunchKernelGGL((schur_pairs_kernel<1>), dim3((G.pblk_short + 7) & ~7), dim3(64), 0, s, (const GPairBlock*)(h->d_gpblk + G.pblk_begin),
                            (const GPairEntry*)h->d_gpent, h->pool, aoff, ld, G.pblk_short, (gwrite ? 1 : 0) | schur_masked);
@@ -930,13 +930,31 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
         hipLaunchKernelGGL((schur_pairs_kernel<4>), dim3((G.pblk_long + 7) & ~7), dim3(256), 0, s,
                            (const GPairBlock*)(h->d_gpblk + G.pblk_begin + G.pblk_short), (const GPairEntry*)h->d_gpent, h->pool, aoff, ld,
                            G.pblk_long, (gwrite ? 1 : 0) | schur_masked);
-      if (G.vblk_count > 0)
-        hipLaunchKernelGGL(schur_factor_kernel, dim3(G.vblk_count), dim3(64 * SCHUR_FW), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
-                           (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
-      if (G.leaf_count > 0) {  // the (rhs, rhs) corner
-        double* scal = h->dscal + 4;
-        reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, s, nullptr);
-        hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, s, Asm + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
+#ifdef LMGPU_TEST_HOOKS
+      if (h->schur_split_diag) {
+        if (G.vblk_count > 0)
+          hipLaunchKernelGGL(schur_factor_kernel, dim3(G.vblk_count), dim3(64 * SCHUR_FW), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
+                             (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
+        if (G.leaf_count > 0) {  // the (rhs, rhs) corner
+          double* scal = h->dscal + 4;
+          reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, s, nullptr);
+          hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, s, Asm + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
+        }
+      } else
+#endif
+      {
+        // one workgroup per separator variable writes (adds) its (v, v) and (v, rhs); the last launch carries one more workgroup,
+        // which sums the leaves' (rhs, rhs) scalars into the corner
+        const int vlong = G.vblk_count - G.vblk_short;
+        const int corner_short = (G.leaf_count > 0 && vlong == 0) ? 1 : 0, corner_long = (G.leaf_count > 0 && vlong > 0) ? 1 : 0;
+        if (G.vblk_short + corner_short > 0)
+          hipLaunchKernelGGL((schur_var_kernel<1>), dim3(G.vblk_short + corner_short), dim3(64), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
+                             (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, G.vblk_short, gwrite ? 1 : 0,
+                             (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
+        if (vlong + corner_long > 0)
+          hipLaunchKernelGGL((schur_var_kernel<SCHUR_VAR_WAVES>), dim3(vlong + corner_long), dim3(64 * SCHUR_VAR_WAVES), 0, s,
+                             (const GVarBlock*)(h->d_gvblk + G.vblk_begin + G.vblk_short), (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, vlong,
+                             gwrite ? 1 : 0, (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
       }
       if (gwrite && own_terms) {  // the front's own factors and the damping are added: after the gather has initialised the entries
         if (F.fac_count > 0) launch_assemble_rows(h, fi, aoff, true);  // (a gather-write front has no update-matrix children: only its factors are added here)
@@ -1934,6 +1952,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) h->wide16_max = atoi(e);
   h->bsd_ticket = dev_switch("LMGPU_BSD_TICKET") != nullptr;
   h->no_gather_write = dev_switch("LMGPU_NO_GATHER_WRITE") != nullptr;
+  h->schur_split_diag = dev_switch("LMGPU_SCHUR_SPLIT_DIAG") != nullptr;
   h->pcg_fused = dev_switch("LMGPU_PCG_FUSED") != nullptr;
   if (dev_switch("LMGPU_NO_MERGE")) h->chain_merge = false;
   if (const char* e = dev_switch("LMGPU_CHAIN_SPLIT")) h->chain_split_pct = std::max(0, std::min(100, atoi(e)));
@@ -2289,6 +2308,7 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
   struct GVarTmp {
     int32_t pv;
     int16_t dv;
+    bool leaf;  // a leaf entry (the leaf's S_v and d) or a factor entry (the factor's A_v and b)
     GVarEntry ent;
   };
   int n_gleaf = 0;
@@ -2395,9 +2415,21 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
         std::vector<Ent> ents;
         for (size_t k = ch.n_frontal_vars; k < ch.vars.size(); k++) ents.push_back({colof[ch.vars[k]], ch.col_off[k], P.dims[ch.vars[k]]});
         ents.push_back({fr.n - 1, ch.n - 1, 1});
+        // (v, v) and (v, rhs) of a separator variable v come from ONE walk of schur_var_kernel over the leaves that see v: a leaf
+        // entry in v's list; the pair lists keep the blocks pa < pb < rhs  (split-diagonal form: every block is a pair block)
+        if (!h->schur_split_diag)
+          for (size_t x = 0; x + 1 < ents.size(); x++) {
+            if (ents[x].d + 1 > 16) {
+              h->err = "Schur gather: a separator variable of more than 15 dimensions does not fit the 16 x 16 tile of schur_var_kernel";
+              return LMGPU_INVALID;
+            }
+            gv_tmp.push_back(GVarTmp{ents[x].pc, (int16_t)ents[x].d, true,
+                                     GVarEntry{CF.u_off, (int16_t)ch.nf, (int16_t)(ents[x].lc - ch.nf), (int16_t)(ch.n - 1 - ch.nf), 0}});
+          }
         for (size_t x = 0; x < ents.size(); x++)
           for (size_t y = x; y < ents.size(); y++) {
-            if (x + 1 == ents.size()) continue;  // (rhs, rhs): the corner goes through the scalar reduction
+            if (x + 1 == ents.size()) continue;  // (rhs, rhs): the corner is a scalar reduction
+            if (!h->schur_split_diag && (y == x || y + 1 == ents.size())) continue;
             Ent a = ents[x], b = ents[y];
             if (a.pc > b.pc) std::swap(a, b);
             gp_tmp.push_back(GPairTmp{((int64_t)a.pc << 32) | (uint32_t)b.pc, (int16_t)a.d, (int16_t)b.d,
@@ -2408,7 +2440,7 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
             const int v = P.factors[f].slots[pos];
             if (v < 0 || P.front_of_var[v] == c) continue;  // frontal in the leaf: no separator contribution
             const FacDesc& fdd = fd[h->fac_local[f]];
-            gv_tmp.push_back(GVarTmp{colof[v], (int16_t)P.dims[v],
+            gv_tmp.push_back(GVarTmp{colof[v], (int16_t)P.dims[v], false,
                                      GVarEntry{fdd.joff, fdd.rows, (int16_t)(pos == 0 ? 0 : fdd.d0), (int16_t)(fdd.d0 + fdd.d1), 0}});
           }
         continue;
@@ -2463,30 +2495,25 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
       gpblk.insert(gpblk.end(), longs.begin(), longs.end());
       std::stable_sort(gv_tmp.begin(), gv_tmp.end(), [](const GVarTmp& a, const GVarTmp& b) { return a.pv < b.pv; });
       G.vblk_begin = (int)gvblk.size();
+      std::vector<GVarBlock> vlongs;
       for (size_t i = 0; i < gv_tmp.size();) {
         size_t j = i;
         while (j < gv_tmp.size() && gv_tmp[j].pv == gv_tmp[i].pv) j++;
-        gvblk.push_back(GVarBlock{gv_tmp[i].pv, gv_tmp[i].dv, 0, (int32_t)gvent.size(), (int32_t)(j - i)});
-        for (size_t e = i; e < j; e++) gvent.push_back(gv_tmp[e].ent);
+        // the variable's leaf entries first, then its factor entries, each in leaf (elimination) order
+        int nleaf = 0;
+        for (size_t e = i; e < j; e++)
+          if (gv_tmp[e].leaf) nleaf++;
+        const GVarBlock blk{gv_tmp[i].pv, gv_tmp[i].dv, 0, (int32_t)gvent.size(), (int32_t)(j - i), nleaf};
+        const bool is_short = !h->schur_split_diag && nleaf <= SCHUR_VAR_SHORT && (int)(j - i) - nleaf <= SCHUR_VAR_SHORT;
+        if (is_short || h->schur_split_diag) gvblk.push_back(blk); else vlongs.push_back(blk);
+        for (int pass = 0; pass < 2; pass++)
+          for (size_t e = i; e < j; e++)
+            if (gv_tmp[e].leaf == (pass == 0)) gvent.push_back(gv_tmp[e].ent);
         i = j;
       }
+      G.vblk_short = h->schur_split_diag ? 0 : (int)gvblk.size() - G.vblk_begin;
+      gvblk.insert(gvblk.end(), vlongs.begin(), vlongs.end());
       G.vblk_count = (int)gvblk.size() - G.vblk_begin;
-      {  // chunk starts (lists are sorted by destination row)
-        const int nchunks = (fr.n + NBO - 1) / NBO;
-        auto starts = [&](std::vector<int>& out, int count, auto row_of) {
-          out.assign(nchunks + 1, count);
-          int c = 0;
-          out[0] = 0;
-          for (int i = 0; i < count; i++) {
-            const int rc = row_of(i) / NBO;
-            while (c < rc) out[++c] = i;
-          }
-          while (c < nchunks) out[++c] = count;
-        };
-        starts(G.cs, G.pblk_short, [&](int i) { return gpblk[G.pblk_begin + i].pa; });
-        starts(G.cl, G.pblk_long, [&](int i) { return gpblk[G.pblk_begin + G.pblk_short + i].pa; });
-        starts(G.cv, G.vblk_count, [&](int i) { return gvblk[G.vblk_begin + i].pv; });
-      }
       if (F.child_count == 0) {  // no child adds to this front before its own level: the gather can be the first writer
         G.write_ok = true;
         G.zero_begin = (int)gzero.size();
@@ -2499,6 +2526,14 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
         covered.reserve(G.pblk_short + G.pblk_long);
         for (int q = 0; q < G.pblk_short + G.pblk_long; q++)
           covered.push_back(((int64_t)gpblk[G.pblk_begin + q].pa << 32) | (uint32_t)gpblk[G.pblk_begin + q].pb);
+        if (!h->schur_split_diag) {  // a variable block covers (v, v) and (v, rhs); the corner workgroup covers (rhs, rhs)
+          for (int q = 0; q < G.vblk_count; q++) {
+            const int32_t pv = gvblk[G.vblk_begin + q].pv;
+            covered.push_back(((int64_t)pv << 32) | (uint32_t)pv);
+            covered.push_back(((int64_t)pv << 32) | (uint32_t)(fr.n - 1));
+          }
+          if (G.leaf_count > 0) covered.push_back(((int64_t)(fr.n - 1) << 32) | (uint32_t)(fr.n - 1));
+        }
         std::sort(covered.begin(), covered.end());
         (void)gi;
         for (size_t x = 0; x < vb.size(); x++)
