@@ -172,6 +172,9 @@ SYMBOLS = {
     "lmgpu_get_jacobians": (ct.c_int, [_H, _I, _I, _I, _I, ct.POINTER(ct.c_int64), _D]),
     "lmgpu_num_fronts": (ct.c_int, [_H]),
     "lmgpu_front_info": (ct.c_int, [_H, ct.c_int32, _I]),
+    "lmgpu_leaf_group_launches": (ct.c_int, [_H]),
+    "lmgpu_backsub_group_launches": (ct.c_int, [_H, _I]),
+    "lmgpu_get_leaf_corner": (ct.c_int, [_H, ct.c_int32, _D]),
     "lmgpu_get_front": (ct.c_int, [_H, ct.c_int32, _I, _D]),
     "lmgpu_comm_unique_id": (ct.c_int, [ct.c_char_p]),
     "lmgpu_comm_init": (ct.c_int, [_H, ct.c_char_p]),

@@ -978,6 +978,7 @@ __global__ __launch_bounds__(MAXT) void lds_front_merged_kernel(const int32_t* _
 
 // back-substitution for LDS-class fronts with at most LDSB_SMALL_NF frontal scalars (leaves and the levels just above them: the host
 // takes the workgroup-per-front kernels below for anything larger): x_F = R^-1 (d - S x_S).  One wave per front, 4 fronts per block.
+// (A level whose fronts all have nf <= LDSBG_MAXNF takes lds_backsub_group_kernel instead, four fronts per wave: kernels_leaf.hpp.)
 // Built around the number of dependent memory round trips (each ~2-3 us, and BAL's 100 000 leaf fronts are ~12 rounds of resident
 // waves): list -> descriptor -> {separator offsets, frontal offsets, the rows of S and d four at a time, lane i's row of R} in ONE
 // batch of unconditional loads on clamped indices -> x_S -> arithmetic -> store.  The nf x nf solve is a register chain: lane i
@@ -1265,3 +1266,5 @@ __global__ __launch_bounds__(256) void lds_backsub_merged_kernel(const int32_t* 
 }
 
 }  // namespace lmgpu
+
+#include "kernels_leaf.hpp"

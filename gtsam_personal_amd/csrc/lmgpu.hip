@@ -98,12 +98,15 @@ struct LevelWork {
   // LDS fronts of this level, grouped by LDS-size bin: [bin_begin[b], bin_begin[b+1]) inside the level's list
   int list_begin = 0, list_count = 0;
   int lds_nf_max = 0;  // largest frontal dimension among the level's LDS fronts
+  int lds_ns_max = 0;  // largest separator dimension among them
   int lds_rsd_max = 0; // largest nf x (n | 1) among them: doubles of LDS the workgroup-per-front back-substitution stages
   int bin_begin[16] = {0};
   int bin_srows[16] = {0};  // rows of the front kept in LDS for the bin's launch
   int bin_jcap[16] = {0};   // doubles of Jacobian staging per workgroup (largest front of the bin, 96 .. LDSF_JCAP)
   int64_t pack_off[16] = {0};  // byte offset of the launch's packed leaf records in d_leafpack, and their stride (0: none)
   int pack_stride[16] = {0};
+  uint8_t bin_group[16] = {0};  // the bin's launch takes lds_front_group_kernel (kernels_leaf.hpp): 1 = nf <= 3 and binary factors of at most two rows, 2 = the caps
+  int bin_group_out[16] = {0}, bin_group_maxfac[16] = {0};  // ... the largest nf x n and the largest number of factors among its leaves
   std::vector<int> hbm;  // HBM fronts of this level
   int small_begin = 0, small_count = 0;  // those with nf <= BSS_MAX_NF, in d_hbm_small: back-substituted in one launch per level
   int bsd_begin = 0, bsd_count = 0;      // their 64-row blocks in d_bsd_table (hbm_backsolve_blocks_kernel: one workgroup per block)
@@ -273,6 +276,9 @@ struct lmgpu_handle {
   bool use_graph = false;       // replay the solve's launch sequence as a hipGraph (deep trees; LMGPU_GRAPH=0/1 overrides)
   int eager_solves = 0;
   hipGraphExec_t solve_graph[2] = {nullptr, nullptr};  // [1]: with the extra gradient vector of the marginal solves
+  int leaf_group_threads = 256;                // LMGPU_LEAF_GROUP_THREADS=64|128|256: its workgroup size (A/B)
+  bool no_backsub_groups = false;              // LMGPU_NO_BACKSUB_GROUPS: lds_backsub_kernel (a wave per front) where lds_backsub_group_kernel would run (A/B)
+  int n_leaf_group_launches = 0;               // gather-leaf bin launches that take lds_front_group_kernel (lmgpu_leaf_group_launches)
   bool no_wide16 = false;                      // LMGPU_NO_WIDE16=1: LDS fronts always with four waves (A/B)
   int wide16_max = 256;                        // launches of at most this many wide LDS fronts take sixteen waves per front (LMGPU_WIDE16_MAX)
   bool bsd_ticket = false;                     // LMGPU_BSD_TICKET=1: the block back-substitution always draws tickets (tests: the path of levels with more blocks than CUs)
@@ -857,6 +863,20 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       const int jcap = L.bin_jcap[b];
       const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - jcap) * 8 + 64 + (size_t)srows * nmax * sizeof(double);
       const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
+      if (L.bin_group[b]) {  // every leaf of the bin qualifies (leaf_group_form): four leaves per wave, one lane per factor
+        auto* gk = L.bin_group[b] == 1 ? lds_front_group_kernel<2, LEAFGRP_MAXSEP, 3> : lds_front_group_kernel<LEAFGRP_MAXROWS, LEAFGRP_MAXSEP, LEAFGRP_MAXNF>;
+        // LDS per leaf: the staged Jacobians and [R S d]; the second over the first where no lane takes a second factor (kernels_leaf.hpp)
+        const int out_off = L.bin_group_maxfac[b] > LEAFGRP_LANES ? jcap : 0;
+        const int lds_leaf = (std::max(jcap, out_off + L.bin_group_out[b]) + 1) & ~1;
+        int gthreads = h->leaf_group_threads;  // (halved until the workgroup's leaves fit 64 KB of LDS)
+        while (gthreads > 64 && (size_t)(gthreads / LEAFGRP_LANES) * lds_leaf * sizeof(double) > 65536) gthreads >>= 1;
+        const int lpw = gthreads / LEAFGRP_LANES;  // leaves per workgroup
+        hipLaunchKernelGGL(gk, dim3((cnt + lpw - 1) / lpw), dim3(gthreads), (size_t)lpw * lds_leaf * sizeof(double), s,
+                           (const char*)(h->d_leafpack + L.pack_off[b]), L.pack_stride[b], cnt, h->pool, lambda_v,
+                           lambda_p, (const double*)h->dampw, h->d_status, h->d_gcorner, (const double*)h->gex_active, lds_leaf, out_off);
+        h->kt.end(kt, s);
+        continue;
+      }
       // a handful of wide fronts (the upper levels of a general sparse tree, where a launch lasts as long as its slowest front and the
       // device is idle): sixteen waves per front -- the rank-4 trailing updates, the extend-add and the emission all scale with them
       const bool wide16 = b >= 3 && b < 6 && cnt <= h->wide16_max && !h->no_wide16;
@@ -1063,6 +1083,39 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
   return LMGPU_OK;
 }
 
+// Does this front qualify for lds_front_group_kernel (kernels_leaf.hpp)?  0: no; 1: yes, nf <= 3 and every binary factor of at most two rows; 2: yes.
+// A gather leaf ([R S d] stored with ld_rsd = n) with a single-batch packed record (the conditions of the LEAFPACK_* records below, has_xo included), nf <= LEAFGRP_MAXNF,
+// not replicated, every factor unary on a frontal variable or binary between one frontal and one separator variable, at most
+// LEAFGRP_MAXROWS rows and LEAFGRP_MAXSEP separator columns per factor, and no separator variable shared by two factors (a lane owns
+// its factor's separator columns of [R S d]).
+static int leaf_group_form(const FrontDesc& F, const FrontFac* ffac, const FacDesc* fd, int jcap) {
+  if (F.par_ld != -1 || F.pad != 0 || F.nf < 1 || F.nf > LEAFGRP_MAXNF || F.nf > LEAFPACK_MAXNF || F.ld_rsd != F.n) return 0;
+  if (F.fac_count < 1 || F.fac_count > LDSF_MAXB) return 0;
+  int form = F.nf <= 3 ? 1 : 2, tot = 0;
+  int32_t seen[LDSF_MAXB];
+  int nseen = 0;
+  for (int k = 0; k < F.fac_count; k++) {
+    const FrontFac& ff = ffac[F.fac_begin + k];
+    const FacDesc& d = fd[ff.fac];
+    tot += d.rows * (d.d0 + d.d1 + d.d2 + 1);
+    if (d.d2 > 0 || d.rows < 1 || d.rows > LEAFGRP_MAXROWS) return 0;
+    if (d.d1 == 0) {  // unary: on frontal columns
+      if (ff.c0 + d.d0 > F.nf) return 0;
+      continue;
+    }
+    const bool f0 = ff.c0 < F.nf, f1 = ff.c1 < F.nf;
+    if (f0 == f1) return 0;  // both frontal, or none
+    const int cf = f0 ? ff.c0 : ff.c1, df = f0 ? d.d0 : d.d1, cs = f0 ? ff.c1 : ff.c0, ds = f0 ? d.d1 : d.d0;
+    if (cf + df > F.nf || ds > LEAFGRP_MAXSEP || cs + ds > F.n - 1) return 0;
+    for (int q = 0; q < nseen; q++)
+      if (seen[q] == cs) return 0;
+    seen[nseen++] = cs;
+    if (d.rows > 2) form = 2;
+  }
+  if (tot > jcap) return 0;  // no single-batch record
+  return form;
+}
+
 // the LDS fronts of level l as one launch sized for the level's largest front (merged and fused launches): false when the level has none, too
 // many of them (a launch sized for the largest front would cost the small ones their occupancy), or gather leaves
 static bool level_lds_class(const lmgpu_handle* h, int l, int* nmax, int* jcap, int* threads) {
@@ -1081,6 +1134,13 @@ static bool level_lds_class(const lmgpu_handle* h, int l, int* nmax, int* jcap, 
   const bool wide16 = top >= 3 && cnt_top <= h->wide16_max && !h->no_wide16;
   *threads = wide16 ? 1024 : (top == 0 ? 64 : 256);  // (four waves from 25 columns on: the blocked Cholesky of the LDS body needs them)
   return true;
+}
+
+// Which kernel the plain per-level back-substitution launch of level L takes.  0: lds_backsub_kernel / lds_backsub_wide_kernel; 1:
+// lds_backsub_group_kernel<3, 6> (every front nf <= 3, separators of at most 96 columns); 2: lds_backsub_group_kernel<LDSBG_MAXNF, 9>.
+static int backsub_group_form(const lmgpu_handle* h, const LevelWork& L) {
+  if (L.list_count == 0 || L.lds_nf_max > LDSBG_MAXNF || h->no_backsub_groups) return 0;
+  return (L.lds_nf_max <= 3 && L.lds_ns_max <= 6 * LEAFGRP_LANES) ? 1 : 2;
 }
 
 // ---- back-substitution, top-down (a14)
@@ -1120,6 +1180,11 @@ int do_backsub(lmgpu_handle* h) {
       hipLaunchKernelGGL(lds_backsub_wide_kernel, dim3(L.list_count), dim3(256), (size_t)(L.lds_rsd_max + LDSB_TAIL) * sizeof(double), s,
                          (const int32_t*)(h->d_lists + L.list_begin), L.list_count, (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff,
                          (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta, h->d_status);
+    } else if (const int form = backsub_group_form(h, L)) {  // every front of the launch: four fronts per wave, 16 lanes each
+      auto* gk = form == 1 ? lds_backsub_group_kernel<3, 6> : lds_backsub_group_kernel<LDSBG_MAXNF, 9>;
+      hipLaunchKernelGGL(gk, dim3((L.list_count + 15) / 16), dim3(256), 0, s, (const int32_t*)(h->d_lists + L.list_begin), L.list_count,
+                         (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta,
+                         h->d_status);
     } else {
       hipLaunchKernelGGL(lds_backsub_kernel, dim3((L.list_count + 3) / 4), dim3(256), 0, s, (const int32_t*)(h->d_lists + L.list_begin),
                          L.list_count, (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff,
@@ -1949,6 +2014,8 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   h->chain_forms = (dev_switch("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (dev_switch("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
   h->no_tail = dev_switch("LMGPU_NO_TAIL") != nullptr;
   h->no_wide16 = dev_switch("LMGPU_NO_WIDE16") != nullptr;
+  if (const char* e = dev_switch("LMGPU_LEAF_GROUP_THREADS")) h->leaf_group_threads = atoi(e) == 64 ? 64 : (atoi(e) == 128 ? 128 : 256);
+  h->no_backsub_groups = dev_switch("LMGPU_NO_BACKSUB_GROUPS") != nullptr;
   if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) h->wide16_max = atoi(e);
   h->bsd_ticket = dev_switch("LMGPU_BSD_TICKET") != nullptr;
   h->no_gather_write = dev_switch("LMGPU_NO_GATHER_WRITE") != nullptr;
@@ -2609,6 +2676,7 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
       for (int fi : byLevelBin[l][b]) {
         lists.push_back(fi);
         L.lds_nf_max = std::max(L.lds_nf_max, (int)P.fronts[fi].nf);
+        L.lds_ns_max = std::max(L.lds_ns_max, (int)P.fronts[fi].n - (int)P.fronts[fi].nf - 1);
         L.lds_rsd_max = std::max(L.lds_rsd_max, (int)P.fronts[fi].nf * ((int)P.fronts[fi].n | 1));
       }
       c += (int)byLevelBin[l][b].size();
@@ -2616,6 +2684,23 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
     L.bin_begin[kNumBins] = c;
     L.list_count = c;
   }
+  // ---- gather-leaf bins whose launch takes lds_front_group_kernel: decided here, per bin launch, from the structure alone
+  h->n_leaf_group_launches = 0;
+  if (!dev_switch("LMGPU_NO_LEAF_GROUPS") && !dev_switch("LMGPU_NO_LEAFPACK") && !h->pcg_structure)
+    for (LevelWork& L : h->levels)
+      for (int b = 6; b < kNumBins; b++) {
+        const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
+        int form = cnt > 0 ? 1 : 0;
+        for (int q = 0; q < cnt && form; q++) {
+          const FrontDesc& F = h->h_fronts[lists[L.list_begin + L.bin_begin[b] + q]];
+          const int f = leaf_group_form(F, ffac.data(), fd.data(), L.bin_jcap[b]);
+          form = f ? std::max(form, f) : 0;
+          L.bin_group_out[b] = std::max(L.bin_group_out[b], F.nf * F.n);
+          L.bin_group_maxfac[b] = std::max(L.bin_group_maxfac[b], F.fac_count);
+        }
+        L.bin_group[b] = (uint8_t)form;
+        if (form) h->n_leaf_group_launches++;
+      }
   // ---- merged elimination launches: runs of consecutive levels, each a handful of LDS fronts, with no dense front between them (only
   //      the top level of a run may hold dense fronts: they are launched after it and nothing in the run depends on them)
   {
@@ -3883,6 +3968,34 @@ int lmgpu_get_jacobians(lmgpu_handle* h, int32_t* n_out, int32_t* graph_index, i
 }
 
 int lmgpu_num_fronts(const lmgpu_handle* h) { return (h && h->finalized) ? (int)h->plan.fronts.size() : -1; }
+
+int lmgpu_leaf_group_launches(const lmgpu_handle* h) { return (h && h->finalized) ? h->n_leaf_group_launches : -1; }
+
+int lmgpu_backsub_group_launches(const lmgpu_handle* h, int32_t* wide) {
+  if (!h || !h->finalized) return -1;
+  int cnt = 0, w = 0;
+  for (const LevelWork& L : h->levels) {
+    const int form = backsub_group_form(h, L);
+    cnt += form != 0;
+    w += form == 2;
+  }
+  if (wide) *wide = w;
+  return cnt;
+}
+
+int lmgpu_get_leaf_corner(lmgpu_handle* h, int32_t front, double* corner) {
+  if (!h) return LMGPU_INVALID;
+  if (!h->finalized || front < 0 || front >= (int)h->plan.fronts.size() || !corner) {
+    h->err = "lmgpu_get_leaf_corner: refused (!h->finalized || front < 0 || front >= (int)h->plan.fronts.size() || !corner)";
+    return LMGPU_INVALID;
+  }
+  int rc = need_device(h);
+  if (rc) return rc;
+  const FrontDesc& F = h->h_fronts[front];
+  if (!h->solved || !h->front_active[front] || F.par_ld != -1 || !h->d_gcorner) return LMGPU_INVALID;  // (gather leaves only)
+  HIPCHECK(hipMemcpy(corner, h->d_gcorner + F.par_map, sizeof(double), hipMemcpyDeviceToHost));
+  return LMGPU_OK;
+}
 
 int lmgpu_front_info(const lmgpu_handle* h, int32_t front, int32_t* info) {
   if (!h || !h->finalized || front < 0 || front >= (int)h->plan.fronts.size() || !info) return LMGPU_INVALID;

@@ -389,6 +389,21 @@ class LevenbergMarquardtOptimizer:
     def num_fronts(self):
         return self.lib.lmgpu_num_fronts(self._h)
 
+    def leaf_group_launches(self):
+        """structure only: how many gather-leaf bin launches of the plan take the lane-group kernel (four leaves per wave)"""
+        return self.lib.lmgpu_leaf_group_launches(self._h)
+
+    def backsub_group_launches(self):
+        """structure only: (levels whose plain back-substitution launch takes the lane-group kernel, how many of them its <4, 9> form)"""
+        wide = np.zeros(1, dtype=np.int32)
+        return self.lib.lmgpu_backsub_group_launches(self._h, _ip(wide)), int(wide[0])
+
+    def leaf_corner(self, i):
+        """after a solve: the (rhs, rhs) corner scalar of gather leaf i (what its parent's Schur gather sums)"""
+        out = np.zeros(1)
+        self._check(self.lib.lmgpu_get_leaf_corner(self._h, i, _dp(out)))
+        return float(out[0])
+
     def front_info(self, i):
         info = np.zeros(8, dtype=np.int32)
         self._check(self.lib.lmgpu_front_info(self._h, i, _ip(info)))

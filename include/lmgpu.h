@@ -465,6 +465,17 @@ int lmgpu_num_fronts(const lmgpu_handle* h); /* 0 on a handle finalized under LM
 /* info8: n_keys, n_frontal_keys, nf (rows of [R S d]), n (cols), parent front (-1 root), class (0 = LDS front, 1 = HBM front),
  *        owner rank (-1 = replicated on every rank), level (0 = leaf) */
 int lmgpu_front_info(const lmgpu_handle* h, int32_t front, int32_t* info8);
+/* Structure only (answerable on a device = -1 handle): how many of the plan's gather-leaf launches (one per size bin of a tree level) eliminate
+ * their leaves four to a wave, one lane per factor (every leaf of the bin: nf <= 4, factors unary on the leaf's variables or binary to one
+ * separator variable of at most 9 columns, at most 4 rows, no separator variable shared by two factors of the leaf); -1 before finalize. */
+int lmgpu_leaf_group_launches(const lmgpu_handle* h);
+/* Structure only (also on a device = -1 handle): how many tree levels' plain back-substitution launch takes lds_backsub_group_kernel (every
+ * LDS front of the level has nf <= 4: four fronts per wave, 16 lanes each); *wide (may be NULL): how many of them its <4, 9> instantiation
+ * (a front of nf = 4, or a separator wider than 96 columns).  -1 before finalize. */
+int lmgpu_backsub_group_launches(const lmgpu_handle* h, int32_t* wide);
+/* Parity tap (tests): the (rhs, rhs) corner scalar b'b - d'd that a gather leaf hands to its parent's Schur gather, after a solve.
+ * LMGPU_INVALID for a front that is not a gather leaf. */
+int lmgpu_get_leaf_corner(lmgpu_handle* h, int32_t front, double* corner);
 /* slots: the front's variables in Scatter order (gtsam/linear/Scatter.cpp:39-73); RSd: column-major nf x n */
 int lmgpu_get_front(lmgpu_handle* h, int32_t front, int32_t* slots, double* RSd_colmajor);
 
