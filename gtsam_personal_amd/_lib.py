@@ -100,6 +100,20 @@ class lmgpu_ncg_params(ct.Structure):
                 ("relative_error_tol", ct.c_double), ("absolute_error_tol", ct.c_double), ("error_tol", ct.c_double)]
 
 
+LMGPU_TRI_VALID, LMGPU_TRI_DEGENERATE, LMGPU_TRI_BEHIND_CAMERA, LMGPU_TRI_OUTLIER, LMGPU_TRI_FAR_POINT, LMGPU_TRI_CALIBRATE_FAILED = 0, 1, 2, 3, 4, 5
+LMGPU_TRI_CAM_BUNDLER, LMGPU_TRI_CAM_S2 = 0, 1  # camera_model of lmgpu_triangulate_batch
+
+
+class lmgpu_triangulation_params(ct.Structure):
+    _fields_ = [("rankTolerance", ct.c_double), ("enableEPI", ct.c_int32), ("useLOST", ct.c_int32), ("landmarkDistanceThreshold", ct.c_double),
+                ("dynamicOutlierRejectionThreshold", ct.c_double), ("noise_inv_sigma", ct.c_double)]
+
+
+class lmgpu_triangulation_stats(ct.Structure):
+    _fields_ = [("n_points", ct.c_int32), ("n_status", ct.c_int32 * 6), ("max_iterations", ct.c_int32), ("sum_iterations", ct.c_int64),
+                ("device_ms", ct.c_double)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -184,6 +198,11 @@ SYMBOLS = {
     "lmgpu_selftest_dense_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_uint, ct.c_int, _I]),
     "lmgpu_selftest_dogleg_step": (ct.c_int, [ct.c_int, _D, _D]),
     "lmgpu_bt_products": (ct.c_int, [_H, _D, ct.c_double, _D, _D]),
+    "lmgpu_triangulate_batch": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _I, _I, _D, ct.POINTER(lmgpu_triangulation_params),
+                                           _D, _I]),
+    "lmgpu_triangulate_landmarks": (ct.c_int, [_H, ct.POINTER(lmgpu_triangulation_params), ct.c_int32, _D, _I, _I]),
+    "lmgpu_num_points3": (ct.c_int, [_H]),
+    "lmgpu_get_triangulation_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_triangulation_stats)]),
     "lmgpu_isam2_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(_H)]),
     "lmgpu_isam2_destroy": (ct.c_int, [_H]),
     "lmgpu_isam2_last_error": (ct.c_char_p, [_H]),

@@ -219,6 +219,8 @@ __global__ void clamp_diag_kernel(int n, const double* __restrict__ diag, double
 
 struct NcgState;  // ncg.hpp
 static void ncg_release(lmgpu_handle* h);
+struct TriState;  // triangulation.hpp
+static void tri_release(lmgpu_handle* h);
 
 struct lmgpu_handle {
   lmgpu_config cfg;
@@ -422,6 +424,7 @@ struct lmgpu_handle {
 
   // ---- nonlinear conjugate gradient (kernels_ncg.hpp, ncg.hpp; lmgpu_ncg_*): allocated at first use
   NcgState* ncg = nullptr;
+  TriState* tri = nullptr;  // the cached point -> factor index and result buffers of lmgpu_triangulate_landmarks
   const int32_t* err_skip = nullptr;  // set around the trial launches of a line search: BucketDev::skip of the error launches
 };
 
@@ -2113,6 +2116,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
     if (h->asm_ev) (void)hipEventDestroy(h->asm_ev);
     for (hipEvent_t e : h->chunk_ev) (void)hipEventDestroy(e);
   }
+  tri_release(h);  // also on a structure-only handle: its index is host memory
   delete h;
   return LMGPU_OK;
 }
@@ -4408,6 +4412,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 #include "isam2.hpp"
 #include "init_pose3.hpp"
 #include "ncg.hpp"
+#include "triangulation.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py
 extern "C" int lmgpu_debug_ldsf(unsigned long long* out16, int reset) {

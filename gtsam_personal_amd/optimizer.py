@@ -14,7 +14,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from .graph import (CAM_BUNDLER, F_PRIOR_CAM, F_SFM, FACTOR_ARITY, N_UNIT, VAR_DIM, VAR_STORE, VAR_STORE_DEV, NonlinearFactorGraph, Ordering,
+from .graph import (CAM_BUNDLER, POINT3, F_PRIOR_CAM, F_SFM, FACTOR_ARITY, N_UNIT, VAR_DIM, VAR_STORE, VAR_STORE_DEV, NonlinearFactorGraph, Ordering,
                     Values)
 
 
@@ -236,6 +236,25 @@ class LevenbergMarquardtOptimizer:
     def set_values(self, values: Values):
         packed = self._pack(values)
         self._check(self.lib.lmgpu_set_values(self._h, _dp(packed)))
+
+    # ------------------------------------------------------------ triangulation (lmgpu_triangulate_landmarks)
+    def num_points3(self) -> int:
+        return self.lib.lmgpu_num_points3(self._h)
+
+    def triangulate_landmarks(self, params=None, write=True):
+        """triangulateSafe (gtsam/geometry/triangulation.h:701-758) of every POINT3 variable from its GeneralSFMFactor / GenericProjectionFactor
+        observations and the current cameras, on the device.  write=True stores the VALID points into the optimizer's values (the error
+        of `state` is not refreshed, as after set_values).  Returns LandmarkTriangulation(keys, points, status, n_valid, stats): the
+        POINT3 keys in elimination order, their points (NaN where not VALID) and TriangulationResult statuses."""
+        from .triangulation import LandmarkTriangulation, TriangulationParameters, TriangulationStats
+        cp = (params or TriangulationParameters())._c()
+        n = self.num_points3()
+        points, status, n_valid = np.full((n, 3), np.nan), np.zeros(n, dtype=np.int32), ct.c_int32(0)
+        self._check(self.lib.lmgpu_triangulate_landmarks(self._h, ct.byref(cp), 1 if write else 0, _dp(points), _ip(status), ct.byref(n_valid)))
+        st = _lib.lmgpu_triangulation_stats()
+        self._check(self.lib.lmgpu_get_triangulation_stats(self._h, ct.byref(st)))
+        keys = [int(k) for k, t in zip(self.ordering, self._types) if t == POINT3]
+        return LandmarkTriangulation(keys, points, status, n_valid.value, TriangulationStats(st))
 
     # ------------------------------------------------------------ NonlinearOptimizer interface
     def values(self) -> Values:

@@ -520,6 +520,79 @@ int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int m
  * repeated with it, 0 if the step is dropped at the radius floor else 1).  Returns 0; -1 for a NULL argument or an unknown `which`. */
 int lmgpu_selftest_dogleg_step(int which, const double* in, double* out);
 
+/* ---- triangulation (gtsam/geometry/triangulation.h, triangulation.cpp): triangulatePoint3 / triangulateSafe for PinholeCamera<Cal3Bundler>
+ *      and PinholeCamera<Cal3_S2>, batched over landmarks on the device -- one lane per landmark, one launch per degree bin over the
+ *      landmarks sorted by their number of observations, results stored at the landmark's own index.  Each camera carries its own
+ *      calibration (as in testTriangulation.cpp, fourPoses_distinct_Ks).  Per landmark, line by line:
+ *        triangulatePoint3<CAMERA> (triangulation.h:491-549): fewer than 2 observations is underconstrained; projection matrices
+ *          K * pose.inverse()[0:3, :] (PinholeCamera.h:316-318); undistortMeasurements (:252-268): nothing for Cal3_S2, for Cal3Bundler
+ *          K_pinhole.uncalibrate(cal.calibrate(z)) with calibrate's fixed-point loop (at most 10 passes, break at
+ *          distance2(uncalibrate(pn), pi) <= 1e-5, Cal3Bundler.cpp:93-128); triangulateDLT (triangulation.cpp:27-56, 149-157): rows
+ *          x P.row(2) - P.row(0), y P.row(2) - P.row(1); DLT (gtsam/base/Matrix.cpp:556-574): rank = singular values > rankTolerance, a
+ *          rank below 3 is underconstrained, else the point is v[0:3] / v[3] of the last right singular vector.  The cheirality check
+ *          (transformTo(point).z <= 0 for any camera) runs after the refinement; the library is built to the reference's default
+ *          GTSAM_THROW_CHEIRALITY_EXCEPTION = ON.
+ *        refinement, enableEPI != 0 (triangulation.cpp:177-195, triangulation.h:153-221): Levenberg-Marquardt on the 3-vector, one
+ *          TriangulationFactor per observation: error project(point) - z with the full distorted projection, 2x3 Jacobian; a point behind a
+ *          camera contributes the error (2 fx, 2 fx) and a zero Jacobian (TriangulationFactor.h:122-136, PinholeCamera.h:321-323).
+ *          lambdaInitial 1, lambdaFactor 10, maxIterations 100, absoluteErrorTol 1, everything else LevenbergMarquardtParams(); control flow as
+ *          lmgpu_iterate / lmgpu_optimize.  One noise model for all observations: Unit (noise_inv_sigma 0) or Isotropic (one inverse sigma).
+ *        triangulateSafe (triangulation.h:701-758): m < 2 or underconstrained -> DEGENERATE; cheirality failure -> BEHIND_CAMERA, before every
+ *          distance check; then per camera in order landmarkDistanceThreshold -> FAR_POINT; after the loop the maximum reprojection error
+ *          norm against dynamicOutlierRejectionThreshold -> OUTLIER.  A threshold <= 0 is off.
+ *      Deviations: useLOST != 0 is refused with LMGPU_INVALID (LOST is not implemented).  A Cal3Bundler::calibrate that has not converged
+ *      after 10 passes gives the extra status LMGPU_TRI_CALIBRATE_FAILED for that point (the reference lets a std::runtime_error escape
+ *      triangulateSafe there).  A non-finite result (v[3] == 0) is carried through with IEEE semantics, as the reference's expressions give
+ *      it.  The CAM_BUNDLER packing folds the principal point into the measurement (variable types above); the DLT rows
+ *      (x - u0) r2 - f r0 are algebraically independent of (u0, v0), and so are the reprojection errors, so the device works with
+ *      u0 = v0 = 0 and measurements relative to the principal point.  A robust noise model is out of scope.
+ *   lmgpu_triangulate_batch       stand-alone (no handle): upload, launches, download.  camera_model 0 = PinholeCamera<Cal3Bundler>, 15
+ *        doubles per camera (the CAM_BUNDLER packing), obs_z relative to the principal point; 1 = PinholeCamera<Cal3_S2>, 17 doubles per
+ *        camera (POSE3 packing + fx, fy, s, u0, v0).  obs_offsets[n_points + 1]: CSR index of the observations of each landmark into
+ *        obs_cam[] (camera indices) and obs_z[] (2 doubles each).  points_out[3 n_points] is NaN where status_out[n_points] is not VALID.
+ *        Refused with LMGPU_INVALID before any device work: a camera index out of range, offsets that decrease (or start below 0), a
+ *        negative n_points, an unknown camera_model, useLOST != 0, a NULL array that is needed.  n_points == 0 is LMGPU_OK.
+ *   lmgpu_triangulate_landmarks   on a finalized handle with values: every POINT3 variable in slot order (lmgpu_num_points3 of them); its
+ *        observations are its LMGPU_F_SFM factors (camera = the CAM_BUNDLER variable's current value) or its LMGPU_F_PROJECTION factors
+ *        (camera = the POSE3 variable's current value + the K of the factor's measurement), in graph-index order.  The point -> factor
+ *        index is built on the host at the first call and kept; cameras and measurements are read where they lie in device memory, only
+ *        the result crosses the host.  write_values != 0 stores the VALID points into the handle's values (the stored linearization is
+ *        treated as by lmgpu_set_values); points of any other status keep their value.  points_out / status_out / n_valid may be NULL.
+ *        Refused with LMGPU_INVALID and a message before anything runs: a point that has both SFM and PROJECTION factors or a
+ *        PROJECTION_BPS / SFM2 factor; GNC enabled; world_size > 1; a call before lmgpu_set_values.  Works on a handle finalized for
+ *        Cholesky or for PCG (it needs no fronts).  ISAM2 is not affected.
+ *   lmgpu_get_triangulation_stats of the last call on the handle, or with h == NULL of the calling thread's last lmgpu_triangulate_batch:
+ *        points per status, the maximum and the sum over the points of the refinement's tryLambda calls (linear solves), device
+ *        milliseconds of the launches (HIP events).  LMGPU_INVALID before the first call. */
+typedef struct lmgpu_triangulation_params { /* TriangulationParameters, triangulation.h:562-609; defaults 1.0, 0, 0, -1, -1, 0 */
+  double rankTolerance;
+  int32_t enableEPI, useLOST;
+  double landmarkDistanceThreshold, dynamicOutlierRejectionThreshold;
+  double noise_inv_sigma; /* 0: Unit; > 0: Isotropic, one inverse sigma (only the refinement reads it) */
+} lmgpu_triangulation_params;
+enum lmgpu_triangulation_status { /* TriangulationResult::Status, triangulation.h:631 */
+  LMGPU_TRI_VALID = 0,
+  LMGPU_TRI_DEGENERATE = 1,
+  LMGPU_TRI_BEHIND_CAMERA = 2,
+  LMGPU_TRI_OUTLIER = 3,
+  LMGPU_TRI_FAR_POINT = 4,
+  LMGPU_TRI_CALIBRATE_FAILED = 5
+};
+typedef struct lmgpu_triangulation_stats {
+  int32_t n_points;
+  int32_t n_status[6]; /* indexed by lmgpu_triangulation_status */
+  int32_t max_iterations;
+  int64_t sum_iterations;
+  double device_ms;
+} lmgpu_triangulation_stats;
+int lmgpu_triangulate_batch(int32_t device, int32_t camera_model, int32_t n_cams, const double* cams, int32_t n_points,
+                            const int32_t* obs_offsets, const int32_t* obs_cam, const double* obs_z, const lmgpu_triangulation_params* params,
+                            double* points_out, int32_t* status_out);
+int lmgpu_triangulate_landmarks(lmgpu_handle* h, const lmgpu_triangulation_params* params, int32_t write_values, double* points_out,
+                                int32_t* status_out, int32_t* n_valid);
+int lmgpu_num_points3(const lmgpu_handle* h); /* POINT3 variables of the handle; -1 before finalize */
+int lmgpu_get_triangulation_stats(const lmgpu_handle* h, lmgpu_triangulation_stats* out);
+
 /* ---- ISAM2 (gtsam/nonlinear/ISAM2.h): incremental smoothing on a device-resident Bayes tree (BASELINE config 5) ----
  * ISAM2::update(newFactors, newTheta) (gtsam/nonlinear/ISAM2.cpp:419-480) = lmgpu_isam2_add_variables + lmgpu_isam2_add_factors
  * (the pending input) + lmgpu_isam2_update: add the variables, (every relinearizeSkip-th update) refresh delta, mark and

@@ -257,4 +257,43 @@ inline void defaultOptimize(const lmgpu_lm_params& p, lmgpu_lm_state* st, Iterat
   } while (st->iterations < p.maxIterations && std::isfinite(currentError));
 }
 
+/// The arrays of lmgpu_triangulate_batch (include/lmgpu.h, "triangulation"), GTSAM-free: cameras once, then per landmark its observations
+/// as (camera index, pixel).  A Cal3Bundler camera is packed without its principal point, which is subtracted from every pixel measured
+/// in it (the CAM_BUNDLER convention of lmgpu.h).
+struct TriangulationBatch {
+  int32_t camera_model;  // 0 PinholeCamera<Cal3Bundler>, 1 PinholeCamera<Cal3_S2>
+  std::vector<double> cams, obs_z, principal;
+  std::vector<int32_t> offsets{0}, obs_cam;
+  explicit TriangulationBatch(int32_t model) : camera_model(model) {}
+  int32_t numCameras() const { return static_cast<int32_t>(principal.size() / 2); }
+  int32_t numLandmarks() const { return static_cast<int32_t>(offsets.size()) - 1; }
+  /// pose12: R row-major 9, t 3.  Returns the camera's index.
+  int32_t addBundlerCamera(const double* pose12, double f, double k1, double k2, double u0, double v0) {
+    cams.insert(cams.end(), pose12, pose12 + 12);
+    cams.insert(cams.end(), {f, k1, k2});
+    principal.insert(principal.end(), {u0, v0});
+    return numCameras() - 1;
+  }
+  int32_t addS2Camera(const double* pose12, double fx, double fy, double s, double u0, double v0) {
+    cams.insert(cams.end(), pose12, pose12 + 12);
+    cams.insert(cams.end(), {fx, fy, s, u0, v0});
+    principal.insert(principal.end(), {0.0, 0.0});
+    return numCameras() - 1;
+  }
+  void addObservation(int32_t cam, double u, double v) {
+    obs_cam.push_back(cam);
+    obs_z.push_back(u - principal.at(2 * static_cast<size_t>(cam)));
+    obs_z.push_back(v - principal.at(2 * static_cast<size_t>(cam) + 1));
+  }
+  void endLandmark() { offsets.push_back(static_cast<int32_t>(obs_cam.size())); }
+  /// points: 3 per landmark (NaN unless VALID); status: lmgpu_triangulation_status per landmark
+  void run(int device, const lmgpu_triangulation_params& params, std::vector<double>* points, std::vector<int32_t>* status) const {
+    points->assign(3 * static_cast<size_t>(numLandmarks()), 0.0);
+    status->assign(static_cast<size_t>(numLandmarks()), 0);
+    const int rc = lmgpu_triangulate_batch(device, camera_model, numCameras(), cams.data(), numLandmarks(), offsets.data(), obs_cam.data(),
+                                           obs_z.data(), &params, points->data(), status->data());
+    if (rc != LMGPU_OK) throw Error(rc, "lmgpu_triangulate_batch: status " + std::to_string(rc));
+  }
+};
+
 }  // namespace lmgpu_adapter

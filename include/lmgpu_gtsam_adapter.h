@@ -24,6 +24,7 @@
 #include <gtsam/geometry/BearingRange.h>
 #include <gtsam/geometry/Cal3Bundler.h>
 #include <gtsam/geometry/Cal3_S2.h>
+#include <gtsam/geometry/CameraSet.h>
 #include <gtsam/geometry/PinholeCamera.h>
 #include <gtsam/geometry/Point2.h>
 #include <gtsam/geometry/Point3.h>
@@ -31,6 +32,7 @@
 #include <gtsam/geometry/Pose3.h>
 #include <gtsam/geometry/Rot2.h>
 #include <gtsam/geometry/Rot3.h>
+#include <gtsam/geometry/triangulation.h>
 #include <gtsam/inference/Ordering.h>
 #include <gtsam/linear/GaussianFactorGraph.h>
 #include <gtsam/linear/JacobianFactor.h>
@@ -896,5 +898,81 @@ class GpuInitializePose3 {
     }
   };
 };
+
+/// triangulateSafe(cameras, measured, params) (gtsam/geometry/triangulation.h:701-758) on the device, for CameraSet<PinholeCamera<Cal3Bundler>>
+/// and CameraSet<PinholeCamera<Cal3_S2>>: call gtsam::gpuTriangulateSafe where the program called triangulateSafe.  The batched overload
+/// triangulates landmark i from cameras[i] / measured[i] in one lmgpu_triangulate_batch call (one lane per landmark).
+/// params.noiseModel: null, Unit or Isotropic; params.useLOST is refused (std::invalid_argument).  Where Cal3Bundler::calibrate does not
+/// converge the reference lets a std::runtime_error escape triangulateSafe; so does this (status LMGPU_TRI_CALIBRATE_FAILED of the library).
+namespace lmgpu_detail {
+
+inline int32_t addCamera(lmgpu_adapter::TriangulationBatch* b, const PinholeCamera<Cal3Bundler>& c) {
+  double pose[12];
+  packPose3(c.pose(), pose);
+  const Cal3Bundler& K = c.calibration();
+  return b->addBundlerCamera(pose, K.fx(), K.k1(), K.k2(), K.px(), K.py());
+}
+inline int32_t addCamera(lmgpu_adapter::TriangulationBatch* b, const PinholeCamera<Cal3_S2>& c) {
+  double pose[12];
+  packPose3(c.pose(), pose);
+  const Cal3_S2& K = c.calibration();
+  return b->addS2Camera(pose, K.fx(), K.fy(), K.skew(), K.px(), K.py());
+}
+inline int32_t cameraModelOf(const Cal3Bundler*) { return 0; }
+inline int32_t cameraModelOf(const Cal3_S2*) { return 1; }
+
+inline lmgpu_triangulation_params toC(const TriangulationParameters& p) {  // triangulation.h:562-609
+  if (p.useLOST) throw std::invalid_argument("gpuTriangulateSafe: useLOST is not bound");
+  double inv_sigma = 0.0;
+  if (p.noiseModel) {
+    const auto iso = std::dynamic_pointer_cast<noiseModel::Isotropic>(p.noiseModel);
+    if (!iso || iso->dim() != 2) throw std::invalid_argument("gpuTriangulateSafe: the noise model must be Unit or Isotropic of dimension 2");
+    inv_sigma = 1.0 / iso->sigma();
+  }
+  return lmgpu_triangulation_params{p.rankTolerance, p.enableEPI ? 1 : 0, 0, p.landmarkDistanceThreshold, p.dynamicOutlierRejectionThreshold, inv_sigma};
+}
+
+inline TriangulationResult toTriangulationResult(int32_t status, const double* p) {
+  switch (status) {
+    case LMGPU_TRI_VALID: return TriangulationResult(Point3(p[0], p[1], p[2]));
+    case LMGPU_TRI_DEGENERATE: return TriangulationResult::Degenerate();
+    case LMGPU_TRI_BEHIND_CAMERA: return TriangulationResult::BehindCamera();
+    case LMGPU_TRI_OUTLIER: return TriangulationResult::Outlier();
+    case LMGPU_TRI_FAR_POINT: return TriangulationResult::FarPoint();
+    default: throw std::runtime_error("Cal3Bundler::calibrate fails to converge. need a better initialization");
+  }
+}
+
+}  // namespace lmgpu_detail
+
+template <class CALIBRATION>
+std::vector<TriangulationResult> gpuTriangulateSafe(const std::vector<CameraSet<PinholeCamera<CALIBRATION>>>& cameras,
+                                                    const std::vector<Point2Vector>& measured, const TriangulationParameters& params,
+                                                    int device = 0) {
+  if (cameras.size() != measured.size()) throw std::invalid_argument("gpuTriangulateSafe: one measurement vector per camera set");
+  lmgpu_adapter::TriangulationBatch batch(lmgpu_detail::cameraModelOf(static_cast<const CALIBRATION*>(nullptr)));
+  for (size_t i = 0; i < cameras.size(); i++) {
+    if (cameras[i].size() != measured[i].size()) throw std::invalid_argument("gpuTriangulateSafe: one measurement per camera");
+    for (size_t k = 0; k < cameras[i].size(); k++) {
+      const int32_t cam = lmgpu_detail::addCamera(&batch, cameras[i][k]);
+      batch.addObservation(cam, measured[i][k].x(), measured[i][k].y());
+    }
+    batch.endLandmark();
+  }
+  std::vector<double> points;
+  std::vector<int32_t> status;
+  batch.run(device, lmgpu_detail::toC(params), &points, &status);
+  std::vector<TriangulationResult> out;
+  out.reserve(status.size());
+  for (size_t i = 0; i < status.size(); i++) out.push_back(lmgpu_detail::toTriangulationResult(status[i], &points[3 * i]));
+  return out;
+}
+
+template <class CALIBRATION>
+TriangulationResult gpuTriangulateSafe(const CameraSet<PinholeCamera<CALIBRATION>>& cameras, const Point2Vector& measured,
+                                       const TriangulationParameters& params, int device = 0) {
+  return gpuTriangulateSafe<CALIBRATION>(std::vector<CameraSet<PinholeCamera<CALIBRATION>>>{cameras}, std::vector<Point2Vector>{measured}, params,
+                                         device)[0];
+}
 
 }  // namespace gtsam
