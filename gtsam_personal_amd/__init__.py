@@ -14,4 +14,5 @@ from .optimizer import (BlockJacobiPreconditionerParameters, DirectionMethod, Do
 from .init_pose3 import InitializePose3  # noqa: F401
 from .triangulation import (TriangulationCheiralityException, TriangulationParameters, TriangulationResult,  # noqa: F401
                             TriangulationUnderconstrainedException, camera_s2_pack, triangulatePoint3, triangulateSafe, triangulateSafeBatch)
+from .smart import SmartProjectionParams, SmartProjectionPoseFactor  # noqa: F401
 from .isam2 import ISAM2, ISAM2DoglegParams, ISAM2GaussNewtonParams, ISAM2Params, ISAM2Result  # noqa: F401

@@ -114,6 +114,20 @@ class lmgpu_triangulation_stats(ct.Structure):
                 ("device_ms", ct.c_double)]
 
 
+LMGPU_SMART_HESSIAN, LMGPU_SMART_IMPLICIT_SCHUR, LMGPU_SMART_JACOBIAN_Q, LMGPU_SMART_JACOBIAN_SVD = 0, 1, 2, 3
+LMGPU_SMART_IGNORE_DEGENERACY, LMGPU_SMART_ZERO_ON_DEGENERACY, LMGPU_SMART_HANDLE_INFINITY = 0, 1, 2
+
+
+class lmgpu_smart_params(ct.Structure):
+    _fields_ = [("linearizationMode", ct.c_int32), ("degeneracyMode", ct.c_int32), ("retriangulationThreshold", ct.c_double),
+                ("triangulation", lmgpu_triangulation_params)]
+
+
+class lmgpu_smart_stats(ct.Structure):
+    _fields_ = [("n_factors", ct.c_int32), ("retriangulations", ct.c_int32), ("n_status", ct.c_int32 * 6), ("triangulate_ms", ct.c_double),
+                ("linearize_ms", ct.c_double)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -203,6 +217,12 @@ SYMBOLS = {
     "lmgpu_triangulate_landmarks": (ct.c_int, [_H, ct.POINTER(lmgpu_triangulation_params), ct.c_int32, _D, _I, _I]),
     "lmgpu_num_points3": (ct.c_int, [_H]),
     "lmgpu_get_triangulation_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_triangulation_stats)]),
+    "lmgpu_add_smart_factors": (ct.c_int, [_H, ct.c_int32, _I, _I, _I, _D, _D, _D, ct.POINTER(lmgpu_smart_params)]),
+    "lmgpu_num_smart_factors": (ct.c_int, [_H]),
+    "lmgpu_smart_get_points": (ct.c_int, [_H, _D, _I]),
+    "lmgpu_smart_get_hessian": (ct.c_int, [_H, ct.c_int32, _I, _D]),
+    "lmgpu_smart_reset": (ct.c_int, [_H]),
+    "lmgpu_get_smart_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_smart_stats)]),
     "lmgpu_isam2_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(_H)]),
     "lmgpu_isam2_destroy": (ct.c_int, [_H]),
     "lmgpu_isam2_last_error": (ct.c_char_p, [_H]),

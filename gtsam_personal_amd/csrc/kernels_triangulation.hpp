@@ -336,6 +336,74 @@ __device__ inline int tri_refine(int beg, int end, const int32_t* __restrict__ o
   return inner;
 }
 
+// triangulateSafe of one landmark (triangulation.h:701-758 over triangulatePoint3 :491-549), the observations [beg, end) of the CSR with
+// end - beg >= 2: DLT, rank test, optional refinement, then the cheirality / distance / outlier checks in the reference's precedence.
+// Returns the status (enum lmgpu_triangulation_status); x = the point, iters = tryLambda calls of the refinement.  The one definition
+// behind triangulate_kernel and the smart factors' smart_triangulate_kernel (kernels_smart.hpp).
+template <int MODEL, bool EPI>
+__device__ inline int tri_safe_point(int beg, int end, const int32_t* __restrict__ obs_cam, const int2* __restrict__ ref,
+                                     const double* const* __restrict__ meas_tab, const double* __restrict__ cams, const TriParamsDev& prm, D3& x,
+                                     int& iters) {
+  int status = 0;
+  double R[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+#pragma unroll
+    for (int c = 0; c < 4; c++) R[r][c] = 0.0;
+  bool calib_ok = true;
+  for (int o = beg; o < end; o++) {
+    const TriCam k = tri_load<MODEL>(o, obs_cam, ref, meas_tab, cams);
+    double zx = k.zx, zy = k.zy;
+    if constexpr (MODEL == TRI_BUNDLER) calib_ok = tri_undistort_bundler(k, zx, zy) && calib_ok;
+    // P = K [R^T | -R^T t] (PinholeCamera.h:316-318): c_i = row i of the calibrated projection matrix
+    const D3 tc = unrot(k.R, D3{-k.t.x, -k.t.y, -k.t.z});
+    double P0[4], P1[4], P2[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const double c0 = j < 3 ? k.R.m[3 * j + 0] : tc.x;
+      const double c1 = j < 3 ? k.R.m[3 * j + 1] : tc.y;
+      const double c2 = j < 3 ? k.R.m[3 * j + 2] : tc.z;
+      P0[j] = k.fx * c0 + k.s * c1 + k.u0 * c2;
+      P1[j] = k.fy * c1 + k.v0 * c2;
+      P2[j] = c2;
+    }
+    tri_givens_row(R, zx * P2[0] - P0[0], zx * P2[1] - P0[1], zx * P2[2] - P0[2], zx * P2[3] - P0[3]);
+    tri_givens_row(R, zy * P2[0] - P1[0], zy * P2[1] - P1[1], zy * P2[2] - P1[2], zy * P2[3] - P1[3]);
+  }
+  double v[4];
+  const int rank = tri_svd4(R, prm.rank_tol, v);
+  if (!calib_ok) {
+    status = 5;
+  } else if (rank < 3) {
+    status = 1;
+  } else {
+    x = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
+    if constexpr (EPI) iters = tri_refine<MODEL>(beg, end, obs_cam, ref, meas_tab, cams, prm.inv_sigma > 0.0 ? prm.inv_sigma : 1.0, x);
+    // triangulatePoint3's cheirality check, then triangulateSafe's loop (triangulation.h:540-546, 718-745)
+    bool behind = false, far = false;
+    double max_rep = 0.0;
+    for (int o = beg; o < end; o++) {
+      const TriCam k = tri_load<MODEL>(o, obs_cam, ref, meas_tab, cams);
+      const D3 dvec = x - k.t;
+      double u, w;
+      if (!tri_project<MODEL, false>(k, x, u, w, nullptr)) {
+        behind = true;
+      } else {
+        const double eu = u - k.zx, ev = w - k.zy;
+        max_rep = fmax(max_rep, sqrt(eu * eu + ev * ev));
+      }
+      if (prm.dist_thr > 0.0 && sqrt(dot3(dvec, dvec)) > prm.dist_thr) far = true;
+    }
+    if (behind)
+      status = 2;
+    else if (far)
+      status = 4;
+    else if (prm.outlier_thr > 0.0 && max_rep > prm.outlier_thr)
+      status = 3;
+  }
+  return status;
+}
+
 // Landmark order[first + i], i < count: status (enum lmgpu_triangulation_status), point (NaN unless VALID) and tryLambda calls, stored at
 // the landmark's own index.  values (may be null): the handle's POINT3 values, VALID points are stored at 3 * val_idx[landmark].
 template <int MODEL, bool EPI>
@@ -353,62 +421,7 @@ __global__ __launch_bounds__(64) void triangulate_kernel(int first, int count, c
   if (end - beg < 2) {
     status = 1;
   } else {
-    double R[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int c = 0; c < 4; c++) R[r][c] = 0.0;
-    bool calib_ok = true;
-    for (int o = beg; o < end; o++) {
-      const TriCam k = tri_load<MODEL>(o, obs_cam, ref, meas_tab, cams);
-      double zx = k.zx, zy = k.zy;
-      if constexpr (MODEL == TRI_BUNDLER) calib_ok = tri_undistort_bundler(k, zx, zy) && calib_ok;
-      // P = K [R^T | -R^T t] (PinholeCamera.h:316-318): c_i = row i of the calibrated projection matrix
-      const D3 tc = unrot(k.R, D3{-k.t.x, -k.t.y, -k.t.z});
-      double P0[4], P1[4], P2[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const double c0 = j < 3 ? k.R.m[3 * j + 0] : tc.x;
-        const double c1 = j < 3 ? k.R.m[3 * j + 1] : tc.y;
-        const double c2 = j < 3 ? k.R.m[3 * j + 2] : tc.z;
-        P0[j] = k.fx * c0 + k.s * c1 + k.u0 * c2;
-        P1[j] = k.fy * c1 + k.v0 * c2;
-        P2[j] = c2;
-      }
-      tri_givens_row(R, zx * P2[0] - P0[0], zx * P2[1] - P0[1], zx * P2[2] - P0[2], zx * P2[3] - P0[3]);
-      tri_givens_row(R, zy * P2[0] - P1[0], zy * P2[1] - P1[1], zy * P2[2] - P1[2], zy * P2[3] - P1[3]);
-    }
-    double v[4];
-    const int rank = tri_svd4(R, prm.rank_tol, v);
-    if (!calib_ok) {
-      status = 5;
-    } else if (rank < 3) {
-      status = 1;
-    } else {
-      x = {v[0] / v[3], v[1] / v[3], v[2] / v[3]};
-      if constexpr (EPI) iters = tri_refine<MODEL>(beg, end, obs_cam, ref, meas_tab, cams, prm.inv_sigma > 0.0 ? prm.inv_sigma : 1.0, x);
-      // triangulatePoint3's cheirality check, then triangulateSafe's loop (triangulation.h:540-546, 718-745)
-      bool behind = false, far = false;
-      double max_rep = 0.0;
-      for (int o = beg; o < end; o++) {
-        const TriCam k = tri_load<MODEL>(o, obs_cam, ref, meas_tab, cams);
-        const D3 dvec = x - k.t;
-        double u, w;
-        if (!tri_project<MODEL, false>(k, x, u, w, nullptr)) {
-          behind = true;
-        } else {
-          const double eu = u - k.zx, ev = w - k.zy;
-          max_rep = fmax(max_rep, sqrt(eu * eu + ev * ev));
-        }
-        if (prm.dist_thr > 0.0 && sqrt(dot3(dvec, dvec)) > prm.dist_thr) far = true;
-      }
-      if (behind)
-        status = 2;
-      else if (far)
-        status = 4;
-      else if (prm.outlier_thr > 0.0 && max_rep > prm.outlier_thr)
-        status = 3;
-    }
+    status = tri_safe_point<MODEL, EPI>(beg, end, obs_cam, ref, meas_tab, cams, prm, x, iters);
   }
   const double nan = __builtin_nan("");
   points_out[(size_t)lm * 3 + 0] = status == 0 ? x.x : nan;

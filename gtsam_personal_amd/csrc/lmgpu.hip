@@ -221,6 +221,16 @@ struct NcgState;  // ncg.hpp
 static void ncg_release(lmgpu_handle* h);
 struct TriState;  // triangulation.hpp
 static void tri_release(lmgpu_handle* h);
+struct SmartState;  // smart.hpp: the smart projection factors of a handle (hidden points, cache, internal factor bucket)
+static void smart_release(lmgpu_handle* h);
+static int smart_prepare(lmgpu_handle* h);
+static int smart_upload(lmgpu_handle* h);
+static void smart_enqueue_triangulate(lmgpu_handle* h, int which);
+static void smart_commit(lmgpu_handle* h);
+static void smart_enqueue_const(lmgpu_handle* h);
+static void smart_fix_lin0(lmgpu_handle* h);
+static void smart_launch_factors(lmgpu_handle* h, const lmgpu::BucketDev& d, const lmgpu::ValuesDev& vals, bool jac);
+static bool smart_refused(lmgpu_handle* h, const char* who);
 
 struct lmgpu_handle {
   lmgpu_config cfg;
@@ -425,6 +435,9 @@ struct lmgpu_handle {
   // ---- nonlinear conjugate gradient (kernels_ncg.hpp, ncg.hpp; lmgpu_ncg_*): allocated at first use
   NcgState* ncg = nullptr;
   TriState* tri = nullptr;  // the cached point -> factor index and result buffers of lmgpu_triangulate_landmarks
+  SmartState* smart = nullptr;  // smart projection factors (smart.hpp); null on a handle that has none
+  int n_hidden = 0;             // hidden POINT3 variables in front of the caller's slots (one per smart factor with m >= 2); 0 without smart factors
+  bool smart_speculative = false;  // the next error launch is tryLambda's speculative one: its cache update waits for smart_commit
   const int32_t* err_skip = nullptr;  // set around the trial launches of a line search: BucketDev::skip of the error launches
 };
 
@@ -486,6 +499,7 @@ BucketDev bucket_dev(lmgpu_handle* h, const Bucket& b) {
 template <bool JAC>
 void launch_factors(lmgpu_handle* h, int which) {
   const ValuesDev vals = values_dev(h, which);
+  if (h->smart) smart_enqueue_triangulate(h, which);  // SmartProjectionFactor::triangulateSafe at the head of every linearize / error
   for (const Bucket& b : h->buckets) {
     if (b.n_loc == 0) continue;
     const BucketDev d = bucket_dev(h, b);
@@ -541,8 +555,12 @@ void launch_factors(lmgpu_handle* h, int which) {
       case LMGPU_F_PRIOR_VEC9:
         hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
         break;
+      case kSmartObsType:
+        smart_launch_factors(h, d, vals, JAC);
+        break;
     }
   }
+  if (JAC && h->smart) smart_enqueue_const(h);
 }
 
 void reduce_to(lmgpu_handle* h, const double* buf, int n, double* dst, hipStream_t st = nullptr, double* scratch = nullptr) {
@@ -625,6 +643,7 @@ int fill_dampw(lmgpu_handle* h, int diagonal, double min_diag, double max_diag) 
   if (!diagonal) {
     if (!h->dampw_is_ones) {
       std::vector<double> ones(h->ntot, 1.0);
+      std::fill(ones.begin(), ones.begin() + 3 * h->n_hidden, 0.0);  // LM never damps the point a smart factor eliminates
       HIPCHECK(hipMemcpyAsync(h->dampw, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
       HIPCHECK(hipStreamSynchronize(h->stream));
       h->dampw_is_ones = true;
@@ -1541,6 +1560,7 @@ int do_solve_enqueue(lmgpu_handle* h, double lambda) {
     if (rc) return rc;
     h->eager_solves++;
   }
+  if (h->smart) smart_fix_lin0(h);
   (void)hipEventRecord(h->ev[4], s);
   HIPCHECK(hipMemcpyAsync(h->h_scal + 1, h->dscal + 1, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(h->h_status, h->d_status, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1558,7 +1578,7 @@ int do_solve_finish(lmgpu_handle* h) {
   }
   if (*h->h_status < (int)h->h_fronts.size()) {
     const Front& fr = h->plan.fronts[*h->h_status];
-    h->failed_slot = fr.vars[0];
+    h->failed_slot = fr.vars[0] - h->n_hidden;  // (negative: the hidden point of a smart factor)
     return LMGPU_INDETERMINATE;
   }
   return LMGPU_OK;
@@ -1572,10 +1592,12 @@ int do_solve(lmgpu_handle* h, double lambda) {
 
 int do_retract(lmgpu_handle* h, int from, int to) {
   for (int t = 0; t < kNumVarTypes; t++) {
-    const int n = h->plan.type_count[t];
+    // the hidden points of smart factors are the first POINT3 variables: never retracted (their value is the cache's, smart.hpp)
+    const int skip = t == LMGPU_POINT3 ? h->n_hidden : 0;
+    const int n = h->plan.type_count[t] - skip;
     if (n == 0) continue;
-    hipLaunchKernelGGL(retract_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, t, n, (const double*)h->vals[from][t], h->vals[to][t],
-                       (const int32_t*)h->type_xoff[t], (const double*)h->delta, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(retract_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, t, n, (const double*)h->vals[from][t] + 3 * skip,
+                       h->vals[to][t] + 3 * skip, (const int32_t*)h->type_xoff[t] + skip, (const double*)h->delta, (const int32_t*)nullptr);
   }
   HIPCHECK(hipGetLastError());
   return LMGPU_OK;
@@ -1613,7 +1635,9 @@ int try_lambda(lmgpu_handle* h, const lmgpu_lm_params* p, bool* done) {
   double newError = std::numeric_limits<double>::infinity(), costChange = 0.0;
   int rc = do_solve_enqueue(h, st.lambda);
   if (rc) return rc;
+  h->smart_speculative = true;
   rc = enqueue_retract_and_error(h);  // speculative: used only if the solve succeeded and the linearised cost did not go up
+  h->smart_speculative = false;
   if (rc) return rc;
   rc = do_solve_finish(h);
   if (rc != LMGPU_OK && rc != LMGPU_INDETERMINATE) return rc;
@@ -1634,6 +1658,7 @@ int try_lambda(lmgpu_handle* h, const lmgpu_lm_params* p, bool* done) {
       if (std::abs(costChange) < minAbsoluteTolerance) stopSearchingLambda = true;
     }
   }
+  if (retracted && h->smart) smart_commit(h);  // the reference evaluated the error here: its factors' caches moved with it
   accumulate_times(h, retracted);
   h->tim.inner_iterations += 1;
   if (step_is_successful) {
@@ -2117,6 +2142,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
     for (hipEvent_t e : h->chunk_ev) (void)hipEventDestroy(e);
   }
   tri_release(h);  // also on a structure-only handle: its index is host memory
+  smart_release(h);
   delete h;
   return LMGPU_OK;
 }
@@ -2283,12 +2309,21 @@ static int finalize_vectors(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
+static int finalize_structure_impl(lmgpu_handle* h);
 int lmgpu_finalize_structure(lmgpu_handle* h) {
   if (!h) return LMGPU_INVALID;
   if (h->finalized) {
     h->err = "lmgpu_finalize_structure: refused (h->finalized)";
     return LMGPU_INVALID;
   }
+  if (!h->smart) return finalize_structure_impl(h);
+  // smart factors: the hidden points and the internal observation bucket enter the structure first, their device arrays come last
+  int rc = smart_prepare(h);
+  if (rc) return rc;
+  if ((rc = finalize_structure_impl(h))) return rc;
+  return h->device >= 0 ? smart_upload(h) : LMGPU_OK;
+}
+static int finalize_structure_impl(lmgpu_handle* h) {
   h->pcg_structure = h->solver == LMGPU_SOLVER_PCG;  // PCG selected before finalize: no symbolic analysis, no fronts
   std::string e = h->plan.build(kLdsLimitN, !h->pcg_structure);
   if (!e.empty()) {
@@ -3015,8 +3050,9 @@ int lmgpu_finalize_structure(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
-int lmgpu_total_dim(const lmgpu_handle* h) { return (h && h->finalized) ? h->ntot : -1; }
-int lmgpu_total_store(const lmgpu_handle* h) { return (h && h->finalized) ? h->nstore : -1; }
+// (the hidden points of smart factors are no part of any packed vector at the boundary: they are the first 3 * n_hidden scalars inside)
+int lmgpu_total_dim(const lmgpu_handle* h) { return (h && h->finalized) ? h->ntot - 3 * h->n_hidden : -1; }
+int lmgpu_total_store(const lmgpu_handle* h) { return (h && h->finalized) ? h->nstore - 3 * h->n_hidden : -1; }
 
 int lmgpu_set_values(lmgpu_handle* h, const double* packed) {
   if (!h) return LMGPU_INVALID;
@@ -3030,8 +3066,9 @@ int lmgpu_set_values(lmgpu_handle* h, const double* packed) {
   for (int t = 0; t < kNumVarTypes; t++) {
     if (P.type_count[t] == 0) continue;
     std::vector<double> buf((size_t)P.type_count[t] * kVarStore[t]);
-    for (int s = 0; s < P.n_vars; s++)
-      if (P.types[s] == t) std::memcpy(&buf[(size_t)P.tidx[s] * kVarStore[t]], packed + P.voff[s], kVarStore[t] * sizeof(double));
+    for (int s = h->n_hidden; s < P.n_vars; s++)
+      if (P.types[s] == t)
+        std::memcpy(&buf[(size_t)P.tidx[s] * kVarStore[t]], packed + (P.voff[s] - 3 * h->n_hidden), kVarStore[t] * sizeof(double));
     HIPCHECK(hipMemcpy(h->vals[h->cur][t], buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   h->have_values = true;
@@ -3052,8 +3089,9 @@ int lmgpu_get_values(lmgpu_handle* h, double* packed) {
     if (P.type_count[t] == 0) continue;
     std::vector<double> buf((size_t)P.type_count[t] * kVarStore[t]);
     HIPCHECK(hipMemcpy(buf.data(), h->vals[h->cur][t], buf.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int s = 0; s < P.n_vars; s++)
-      if (P.types[s] == t) std::memcpy(packed + P.voff[s], &buf[(size_t)P.tidx[s] * kVarStore[t]], kVarStore[t] * sizeof(double));
+    for (int s = h->n_hidden; s < P.n_vars; s++)
+      if (P.types[s] == t)
+        std::memcpy(packed + (P.voff[s] - 3 * h->n_hidden), &buf[(size_t)P.tidx[s] * kVarStore[t]], kVarStore[t] * sizeof(double));
   }
   return LMGPU_OK;
 }
@@ -3128,11 +3166,13 @@ int lmgpu_solve(lmgpu_handle* h, double lambda, int32_t diagonal_damping, double
   int rc = need_device(h);
   if (rc) return rc;
   if ((rc = need_comm(h))) return rc;
+  if (diagonal_damping && smart_refused(h, "lmgpu_solve with diagonal damping")) return LMGPU_INVALID;
   rc = fill_dampw(h, diagonal_damping, min_diag, max_diag);
   if (rc) return rc;
   rc = do_solve(h, lambda);
   if (rc != LMGPU_OK && rc != LMGPU_INDETERMINATE) return rc;
-  if (delta_packed) HIPCHECK(hipMemcpy(delta_packed, h->delta, h->ntot * sizeof(double), hipMemcpyDeviceToHost));
+  if (delta_packed)
+    HIPCHECK(hipMemcpy(delta_packed, h->delta + 3 * h->n_hidden, (h->ntot - 3 * h->n_hidden) * sizeof(double), hipMemcpyDeviceToHost));
   if (lin_err0) *lin_err0 = h->h_scal[1];
   if (lin_err1) *lin_err1 = h->h_scal[2];
   return rc;
@@ -3154,6 +3194,7 @@ int lmgpu_joint_marginal_covariance(lmgpu_handle* h, int32_t nslots, const int32
     h->err = "lmgpu_joint_marginal_covariance: refused (!cov || !slots || nslots < 1 || !h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "the marginal covariances")) return LMGPU_INVALID;
   for (int a = 0; a < nslots; a++) {
     if (slots[a] < 0 || slots[a] >= h->plan.n_vars) return LMGPU_INVALID;
     for (int b = 0; b < a; b++)
@@ -3219,7 +3260,8 @@ int lmgpu_retract(lmgpu_handle* h, const double* delta_packed) {
   }
   int rc = need_device(h);
   if (rc) return rc;
-  if (delta_packed) HIPCHECK(hipMemcpy(h->delta, delta_packed, h->ntot * sizeof(double), hipMemcpyHostToDevice));
+  if (delta_packed)
+    HIPCHECK(hipMemcpy(h->delta + 3 * h->n_hidden, delta_packed, (h->ntot - 3 * h->n_hidden) * sizeof(double), hipMemcpyHostToDevice));
   rc = do_retract(h, h->cur, h->cur ^ 1);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -3233,6 +3275,7 @@ int lmgpu_hessian_diagonal(lmgpu_handle* h, double* diag) {
     h->err = "lmgpu_hessian_diagonal: refused (!h->finalized || !h->linearized || !diag)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_hessian_diagonal")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if ((rc = need_comm(h))) return rc;
@@ -3248,6 +3291,7 @@ int lmgpu_lm_init(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* out
     h->err = "lmgpu_lm_init: refused (!p || !h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (p->diagonalDamping && smart_refused(h, "lmgpu_lm_init with diagonalDamping")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if ((rc = need_comm(h))) return rc;
@@ -3270,6 +3314,7 @@ int lmgpu_iterate(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* ino
     h->err = "lmgpu_iterate: refused (!p || !h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (p->diagonalDamping && smart_refused(h, "lmgpu_iterate with diagonalDamping")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if ((rc = need_comm(h))) return rc;
@@ -3324,6 +3369,7 @@ int lmgpu_dl_iterate(lmgpu_handle* h, lmgpu_lm_state* inout) {
     h->err = "lmgpu_dl_iterate: refused (!h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_dl_iterate")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if (inout) h->lm = *inout;
@@ -3339,6 +3385,7 @@ int lmgpu_bt_products(lmgpu_handle* h, const double* x_packed, double alpha, dou
     h->err = "lmgpu_bt_products: needs a finalized single-rank handle of the direct solver with a factor in the pool (call lmgpu_solve first)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_bt_products")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   hipStream_t s = h->stream;
@@ -3363,6 +3410,7 @@ int lmgpu_dl_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state*
     h->err = "lmgpu_dl_optimize: refused (!p || !h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_dl_optimize")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if (h->solver == LMGPU_SOLVER_PCG) {
@@ -3390,6 +3438,7 @@ int lmgpu_optimize(lmgpu_handle* h, const lmgpu_lm_params* p, lmgpu_lm_state* in
     h->err = "lmgpu_optimize: refused (!p || !h->finalized || !h->have_values)";
     return LMGPU_INVALID;
   }
+  if (p->diagonalDamping && smart_refused(h, "lmgpu_optimize with diagonalDamping")) return LMGPU_INVALID;
   int rc = need_device(h);
   if (rc) return rc;
   if ((rc = need_comm(h))) return rc;
@@ -3431,6 +3480,7 @@ int lmgpu_set_linear_solver(lmgpu_handle* h, int32_t solver, const lmgpu_pcg_par
     h->solver = solver;
     return LMGPU_OK;
   }
+  if (solver == LMGPU_SOLVER_PCG && smart_refused(h, "LMGPU_SOLVER_PCG")) return LMGPU_INVALID;
   if (solver != LMGPU_SOLVER_PCG || !pcg) {
     h->err = "lmgpu_set_linear_solver: unknown solver, or PCG without parameters (NonlinearOptimizer.cpp:156-158)";
     return LMGPU_INVALID;
@@ -3613,6 +3663,7 @@ int lmgpu_gnc_enable(lmgpu_handle* h, int32_t on, int32_t graph_size) {
     h->err = "lmgpu_gnc_enable: refused (!h->finalized)";
     return LMGPU_INVALID;
   }
+  if (on && smart_refused(h, "lmgpu_gnc_enable")) return LMGPU_INVALID;
   if (on && (h->cfg.world_size > 1 || (h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT))) {
     h->err = "lmgpu_gnc_enable: GNC is single-rank (world_size > 1)";
     return LMGPU_INVALID;
@@ -3907,6 +3958,7 @@ int lmgpu_get_jacobian(lmgpu_handle* h, int32_t graph_index, double* out, int32_
     h->err = "lmgpu_get_jacobian: refused (!h->finalized)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_get_jacobian")) return LMGPU_INVALID;
   auto it = std::lower_bound(h->graph_index_sorted.begin(), h->graph_index_sorted.end(), graph_index);
   if (it == h->graph_index_sorted.end() || *it != graph_index) return LMGPU_INVALID;
   const FactorRef& f = h->plan.factors[it - h->graph_index_sorted.begin()];
@@ -3929,6 +3981,7 @@ int lmgpu_get_jacobians(lmgpu_handle* h, int32_t* n_out, int32_t* graph_index, i
     h->err = "lmgpu_get_jacobians: refused (!h->finalized)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_get_jacobians")) return LMGPU_INVALID;
   const int NFAC = (int)h->plan.factors.size();
   if (n_out) *n_out = NFAC;
   int64_t off = 0;
@@ -4413,6 +4466,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 #include "init_pose3.hpp"
 #include "ncg.hpp"
 #include "triangulation.hpp"
+#include "smart.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py
 extern "C" int lmgpu_debug_ldsf(unsigned long long* out16, int reset) {

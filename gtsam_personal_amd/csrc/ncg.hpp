@@ -72,6 +72,7 @@ static_assert(var_tangent_dim(0) == kVarDim[0] && var_tangent_dim(1) == kVarDim[
 
 // the three states the group refuses
 int ncg_check(lmgpu_handle* h, const char* who) {
+  if (smart_refused(h, who)) return LMGPU_INVALID;
   if (!h->finalized || !h->have_values) {
     h->err = std::string(who) + ": refused (no values: lmgpu_finalize_structure and lmgpu_set_values come first)";
     return LMGPU_INVALID;

@@ -296,6 +296,7 @@ int lmgpu_triangulate_landmarks(lmgpu_handle* h, const lmgpu_triangulation_param
     h->err = "lmgpu_triangulate_landmarks: refused (!h->finalized || !params)";
     return LMGPU_INVALID;
   }
+  if (smart_refused(h, "lmgpu_triangulate_landmarks")) return LMGPU_INVALID;
   if (params->useLOST != 0) {
     h->err = "lmgpu_triangulate_landmarks: refused (useLOST: LOST is not implemented)";
     return LMGPU_INVALID;

@@ -291,6 +291,7 @@ class NonlinearFactorGraph:
         self._buckets = {}
         self._n = 0
         self._final = None
+        self._smart = []  # (graph index, SmartProjectionPoseFactor): smart.py; they are no bucket factors
 
     def size(self):
         return self._n
@@ -327,8 +328,15 @@ class NonlinearFactorGraph:
         for ftype, _, gi, keys, meas, _, models in other.buckets():
             for i, g in enumerate(gi.tolist()):
                 rec[g] = (ftype, keys[i], meas[i], models[i])
-        for ftype, keys, meas, model in rec:
-            self._add(ftype, [keys], [meas], model)
+        for g, f in other._smart:
+            rec[g] = f
+        for r in rec:
+            if r is None:  # an empty slot keeps its index
+                self._n += 1
+            elif isinstance(r, tuple):
+                self._add(r[0], [r[1]], [r[2]], r[3])
+            else:
+                self.add_SmartProjectionPoseFactor(r)
 
     def resize(self, n):
         """FactorGraph::resize: 0 as the incremental examples use it to start the next batch of new factors; n >= size() appends
@@ -397,6 +405,15 @@ class NonlinearFactorGraph:
         else:
             self._add(F_PROJECTION_BPS, [[poseKey, pointKey]], np.concatenate([zk, pose3_pack(body_P_sensor[0], body_P_sensor[1])]), model)
 
+    def add_SmartProjectionPoseFactor(self, factor):
+        """graph.push_back(SmartProjectionPoseFactor<Cal3_S2>) (smart.py): the factor takes the next graph index like any other"""
+        self._smart.append((self._n, factor))
+        self._n += 1
+
+    def smart_factors(self):
+        """[(graph index, SmartProjectionPoseFactor)] in graph order"""
+        return list(self._smart)
+
     # -- bulk access
     def buckets(self):
         """[(ftype, dev_noise_kind, graph_index[n], keys[n, arity], meas[n, ml], noise[n, nl] | None, models[n])]"""
@@ -412,6 +429,8 @@ class NonlinearFactorGraph:
         ks = set()
         for ftype, _, _, keys, _, _, _ in self.buckets():
             ks.update(np.unique(keys).tolist())
+        for _, f in self._smart:
+            ks.update(f.keys())
         return sorted(ks)
 
     def factor_keys_in_graph_order(self):
@@ -420,6 +439,8 @@ class NonlinearFactorGraph:
         for ftype, _, gi, keys, _, _, _ in self.buckets():
             for g, k in zip(gi.tolist(), keys.tolist()):
                 out[g] = tuple(int(x) for x in k)
+        for g, f in self._smart:
+            out[g] = tuple(f.keys())
         return out
 
 

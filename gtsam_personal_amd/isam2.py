@@ -133,6 +133,8 @@ class ISAM2:
         (gtsam/nonlinear/ISAM2.h:146-186, ISAM2UpdateParams.h:30-90).  removeFactorIndices: positions in getFactorsUnsafe();
         constrainedKeys: {key: group} (None = not given); the new factors of this update get the indices size() .. of the list (with
         ISAM2Params.findUnusedFactorSlots: its empty slots first)"""
+        if newFactors is not None and newFactors.smart_factors():
+            raise ValueError("ISAM2.update: smart projection factors are not bound in the incremental path (ISAM2UpdateParams::newAffectedKeys)")
         U64 = ct.POINTER(ct.c_uint64)
         if newTheta is not None and newTheta.size():
             keys = np.array(newTheta.keys(), dtype=np.uint64)

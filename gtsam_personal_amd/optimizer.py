@@ -186,6 +186,8 @@ class LevenbergMarquardtOptimizer:
             nptr = _dp(np.ascontiguousarray(noise)) if kind != N_UNIT else None
             self._check(self.lib.lmgpu_add_factor_bucket_robust(self._h, ftype, len(gi32), _ip(gi32), _ip(slots), _dp(meas), kind, nptr,
                                                                 models[0].robust_kind, models[0].robust_k))
+        self._smart = graph.smart_factors() if hasattr(graph, "smart_factors") else []
+        self._add_smart_factors()
         if pcg is not None:  # before finalize: no symbolic analysis, no fronts
             self._check(self.lib.lmgpu_set_linear_solver(self._h, _lib.LMGPU_SOLVER_PCG, ct.byref(pcg)))
         self._check(self.lib.lmgpu_finalize_structure(self._h))
@@ -236,6 +238,72 @@ class LevenbergMarquardtOptimizer:
     def set_values(self, values: Values):
         packed = self._pack(values)
         self._check(self.lib.lmgpu_set_values(self._h, _dp(packed)))
+
+    # ------------------------------------------------------------ smart projection factors (smart.py; lmgpu_add_smart_factors ...)
+    def _add_smart_factors(self):
+        """one lmgpu_add_smart_factors call per SmartProjectionParams object, in graph order"""
+        if not self._smart:
+            return
+        groups = {}
+        for g, f in self._smart:
+            groups.setdefault(id(f.params), (f.params, []))[1].append((g, f))
+        for params, members in groups.values():
+            cp = params._c()  # ValueError for a mode that is not bound
+            gi = np.array([g for g, _ in members], dtype=np.int32)
+            off = np.concatenate([[0], np.cumsum([f.size() for _, f in members])]).astype(np.int32)
+            try:
+                slots = np.array([self._slot[k] for _, f in members for k in f.keys()], dtype=np.int32)
+            except KeyError:
+                raise KeyError("a smart factor references a key that is not in the ordering") from None
+            z = np.ascontiguousarray(np.array([zz for _, f in members for zz in f.measured()], dtype=np.float64).reshape(-1, 2))
+            K5 = np.ascontiguousarray(np.array([f.K for _, f in members], dtype=np.float64))
+            isig = np.array([f.inv_sigma for _, f in members], dtype=np.float64)
+            self._check(self.lib.lmgpu_add_smart_factors(self._h, len(members), _ip(gi), _ip(off), _ip(slots), _dp(z), _dp(K5), _dp(isig),
+                                                         ct.byref(cp)))
+
+    def num_smart_factors(self) -> int:
+        return self.lib.lmgpu_num_smart_factors(self._h)
+
+    def smart_points(self):
+        """(points (n, 3), NaN unless VALID; status (n,)) of the smart factors in graph order: SmartProjectionFactor::point() of each,
+        as the last linearization / error evaluation on the device left it.  Also refreshes the factor objects' point() / isValid() ...
+        (optimize() calls it at its end; iterate() does not: per factor object it is host work)"""
+        n = max(0, self.num_smart_factors())
+        pts, st = np.full((n, 3), np.nan), np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.lib.lmgpu_smart_get_points(self._h, _dp(pts), _ip(st)))
+            order = [f for _, f in self._smart_in_add_order()]
+            for f, p, s in zip(order, pts, st):
+                f._set_result(int(s), p.copy())
+            back = np.argsort(np.array([g for g, _ in self._smart_in_add_order()]), kind="stable")
+            pts, st = pts[back], st[back]
+        return pts, st
+
+    def _smart_in_add_order(self):
+        groups = {}
+        for g, f in self._smart:
+            groups.setdefault(id(f.params), []).append((g, f))
+        return [m for members in groups.values() for m in members]
+
+    def smart_hessian(self, graph_index):
+        """the augmented information matrix ((6 m + 1) x (6 m + 1)) of the smart factor with this graph index from the device's F, E, b
+        of the last linearization (lmgpu_smart_get_hessian)"""
+        m = ct.c_int32()
+        self._check(self.lib.lmgpu_smart_get_hessian(self._h, int(graph_index), ct.byref(m), None))
+        N = 6 * m.value + 1
+        out = np.empty(N * N)
+        self._check(self.lib.lmgpu_smart_get_hessian(self._h, int(graph_index), ct.byref(m), _dp(out)))
+        return out.reshape(N, N).T.copy()
+
+    def smart_reset(self):
+        """empty every smart factor's triangulation cache (= newly constructed factors)"""
+        self._check(self.lib.lmgpu_smart_reset(self._h))
+
+    def smart_stats(self):
+        st = _lib.lmgpu_smart_stats()
+        self._check(self.lib.lmgpu_get_smart_stats(self._h, ct.byref(st)))
+        return dict(n_factors=st.n_factors, retriangulations=st.retriangulations, n_status=list(st.n_status), triangulate_ms=st.triangulate_ms,
+                    linearize_ms=st.linearize_ms)
 
     # ------------------------------------------------------------ triangulation (lmgpu_triangulate_landmarks)
     def num_points3(self) -> int:
@@ -300,6 +368,8 @@ class LevenbergMarquardtOptimizer:
         cp = self.params._c()
         self._check(self.lib.lmgpu_optimize(self._h, ct.byref(cp), ct.byref(self.state)))
         self._lin_generation = getattr(self, "_lin_generation", 0) + 1
+        if self._smart:
+            self.smart_points()
         return self.values()
 
     def set_linear_solver(self, params):
@@ -553,6 +623,8 @@ class GaussNewtonOptimizer(LevenbergMarquardtOptimizer):
         cp = self.params._c()
         self._check(self.lib.lmgpu_gn_optimize(self._h, ct.byref(cp), ct.byref(self.state)))
         self._lin_generation = getattr(self, "_lin_generation", 0) + 1
+        if self._smart:
+            self.smart_points()
         return self.values()
 
 

@@ -593,6 +593,69 @@ int lmgpu_triangulate_landmarks(lmgpu_handle* h, const lmgpu_triangulation_param
 int lmgpu_num_points3(const lmgpu_handle* h); /* POINT3 variables of the handle; -1 before finalize */
 int lmgpu_get_triangulation_stats(const lmgpu_handle* h, lmgpu_triangulation_stats* out);
 
+/* ---- smart projection factors: SmartProjectionPoseFactor<Cal3_S2> (gtsam/slam/SmartProjectionPoseFactor.h:43-152 over SmartProjectionFactor.h
+ *      and SmartFactorBase.h; parameters SmartFactorParams.h:31-133) on the batch handle -- one factor per landmark over the m poses that saw
+ *      it, the landmark re-triangulated at every linearization and eliminated inside the factor, so that the optimizer sees poses only.
+ *      A factor: m >= 1 observations (POSE3 slot, z) with distinct slots, one Cal3_S2 (K5 = fx, fy, s, u0, v0), one Isotropic(2, sigma) noise
+ *      model (SmartFactorBase.h:109-115 refuses any other), one lmgpu_smart_params.
+ *        member triangulateSafe (SmartProjectionFactor.h:127-184), at the head of EVERY linearization and EVERY error evaluation: m < 2 is
+ *          DEGENERATE and leaves the cache alone; else re-triangulate iff the cache is empty or a camera pose is not
+ *          Pose3::equals(cached, retriangulationThreshold) (gtsam/geometry/Pose3.cpp:184-186 -> fpEqual, gtsam/base/Vector.cpp:42-77: in
+ *          effect |a - b| <= tol on the nine rotation and three translation entries); re-triangulating stores the current poses and
+ *          result_ = gtsam::triangulateSafe(cameras, measured, params.triangulation) (the "triangulation" section above).  The result
+ *          therefore depends on the history of calls; the library makes them in the reference's order (LevenbergMarquardtOptimizer:
+ *          constructor error, per iteration linearize, per trial lambda one error evaluation iff the damped system was solved and its
+ *          linearized cost did not rise, LevenbergMarquardtOptimizer.cpp:206-216).  The cache belongs to the handle: lmgpu_set_values,
+ *          lmgpu_retract, lmgpu_restore_values keep it; lmgpu_smart_reset empties it (= newly constructed factors).
+ *        error (:411-439): valid result: 0.5 sum |(project(point) - z) / sigma|^2 at result_; otherwise 0.
+ *        linearize (:198-237), HESSIAN: valid result: the augmented information of CameraSet::SchurComplement(Fs, E, b, 0)
+ *          (gtsam/geometry/CameraSet.h:145-216), Fs (2x6) / E (2x3) the PinholePose<Cal3_S2> projection Jacobians at result_, b = -(reprojection
+ *          error), all divided by sigma; constant term b'b - b'E (E'E)^-1 E'b.  Otherwise a zero factor on the m keys (ZERO_ON_DEGENERACY).
+ *      How it is carried: a factor with m >= 2 is a HIDDEN POINT3 variable in front of the caller's slots with m internal factors; the
+ *      existing leaf elimination produces exactly F'(I - E (E'E)^-1 E')F.  The hidden point is never damped, never retracted, and no
+ *      part of values, delta, lmgpu_total_dim / lmgpu_total_store or any packed vector at this boundary; slots of this header stay the
+ *      caller's.  lmgpu_solve's lin_err0 is the reference's linear.error(0) (constant terms as above).  The front taps (lmgpu_num_fronts,
+ *      lmgpu_front_info, lmgpu_get_front) show the internal structure: hidden points as leaf fronts, slots shifted up by the number of hidden
+ *      points; they are not parity quantities here.  lmgpu_last_failed_slot is negative for a hidden point.
+ *      Deviation: a VALID cached point that a pose moved within retriangulationThreshold puts behind a camera gives that observation
+ *      GenericProjectionFactor's throwCheirality = false behaviour (zero Jacobians, error 2 fx); the reference lets CheiralityException escape.
+ *      Supported on such a handle: lmgpu_error, lmgpu_linearize, lmgpu_solve / lmgpu_lm_init / lmgpu_iterate / lmgpu_optimize without
+ *      diagonal damping, lmgpu_gn_iterate / lmgpu_gn_optimize, lmgpu_retract, lmgpu_set / get / save / restore_values, lmgpu_get_timings, any
+ *      other factor bucket beside them.  Refused with LMGPU_INVALID and one message (each needs the Schur complement itself, not the
+ *      Jacobians the engine keeps): diagonal damping, lmgpu_hessian_diagonal, PCG, GNC, NCG / lmgpu_gradient, Dogleg, lmgpu_bt_products, the
+ *      marginal covariances, lmgpu_get_jacobian(s), lmgpu_triangulate_landmarks.  Not implemented (refused where expressible): the other
+ *      linearization and degeneracy modes, body_P_sensor, SmartProjectionRigFactor, Cal3Bundler smart factors, ISAM2 (newAffectedKeys).
+ *   lmgpu_add_smart_factors   before lmgpu_finalize_structure, any number of times, each call with its own params.  graph_index[n]: the
+ *        factor's index in the NonlinearFactorGraph; obs_offsets[n + 1]: CSR into obs_slots[] (the caller's POSE3 slots) and obs_z[] (2
+ *        doubles each); K5[5 n]; inv_sigma[n] = 1 / sigma.  Refused with LMGPU_INVALID and a message before any device work: a mode other
+ *        than HESSIAN / ZERO_ON_DEGENERACY, useLOST, a slot that is not POSE3, a slot twice in one factor, a factor without observations,
+ *        decreasing offsets, inv_sigma <= 0, world_size > 1.
+ *   lmgpu_smart_get_points    SmartProjectionFactor::point() of every factor in the order added: NaN unless VALID, with the status
+ *        (lmgpu_triangulation_status); DEGENERATE before the first evaluation.  Either output may be NULL.
+ *   lmgpu_smart_get_hessian   parity tap: the augmented information ((6 m + 1)^2, column-major, symmetric) of the factor with this graph
+ *        index, built on the host from the device's own F, E, b of the last linearization.  aug_info_colmajor may be NULL (m only).
+ *   lmgpu_get_smart_stats     of the last linearize / error evaluation that counts (a dropped speculative one does not): factors
+ *        re-triangulated, factors per status, device ms of its triangulation launches and of the last smart linearize launches (HIP events). */
+enum lmgpu_smart_linearization_mode { LMGPU_SMART_HESSIAN = 0, LMGPU_SMART_IMPLICIT_SCHUR = 1, LMGPU_SMART_JACOBIAN_Q = 2, LMGPU_SMART_JACOBIAN_SVD = 3 };
+enum lmgpu_smart_degeneracy_mode { LMGPU_SMART_IGNORE_DEGENERACY = 0, LMGPU_SMART_ZERO_ON_DEGENERACY = 1, LMGPU_SMART_HANDLE_INFINITY = 2 };
+typedef struct lmgpu_smart_params { /* SmartProjectionParams, SmartFactorParams.h:42-133; defaults HESSIAN, IGNORE_DEGENERACY, 1e-5 */
+  int32_t linearizationMode, degeneracyMode;
+  double retriangulationThreshold;
+  lmgpu_triangulation_params triangulation;
+} lmgpu_smart_params;
+typedef struct lmgpu_smart_stats {
+  int32_t n_factors, retriangulations;
+  int32_t n_status[6]; /* indexed by lmgpu_triangulation_status */
+  double triangulate_ms, linearize_ms;
+} lmgpu_smart_stats;
+int lmgpu_add_smart_factors(lmgpu_handle* h, int32_t n, const int32_t* graph_index, const int32_t* obs_offsets, const int32_t* obs_slots,
+                            const double* obs_z, const double* K5, const double* inv_sigma, const lmgpu_smart_params* params);
+int lmgpu_num_smart_factors(const lmgpu_handle* h); /* -1 before finalize */
+int lmgpu_smart_get_points(lmgpu_handle* h, double* points3, int32_t* status);
+int lmgpu_smart_get_hessian(lmgpu_handle* h, int32_t graph_index, int32_t* m, double* aug_info_colmajor);
+int lmgpu_smart_reset(lmgpu_handle* h);
+int lmgpu_get_smart_stats(const lmgpu_handle* h, lmgpu_smart_stats* out);
+
 /* ---- ISAM2 (gtsam/nonlinear/ISAM2.h): incremental smoothing on a device-resident Bayes tree (BASELINE config 5) ----
  * ISAM2::update(newFactors, newTheta) (gtsam/nonlinear/ISAM2.cpp:419-480) = lmgpu_isam2_add_variables + lmgpu_isam2_add_factors
  * (the pending input) + lmgpu_isam2_update: add the variables, (every relinearizeSkip-th update) refresh delta, mark and

@@ -15,8 +15,10 @@
 //   p.iterate(params) ...                                     // LevenbergMarquardtOptimizer::iterate
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -124,7 +126,72 @@ class Problem {
     if (nn) b.noise.insert(b.noise.end(), noise, noise + nn);
   }
 
+  /// one SmartProjectionPoseFactor<Cal3_S2> (include/lmgpu.h, "smart projection factors"): its pose keys and measurements (2 doubles
+  /// each), K5 = (fx, fy, s, u0, v0), 1 / sigma of its isotropic noise model.  Factors that share `params` travel in one call.
+  void addSmartFactor(int32_t graphIndex, const std::vector<uint64_t>& keys, const std::vector<double>& z, const double* K5, double invSigma,
+                      const lmgpu_smart_params& params) {
+    if (z.size() != 2 * keys.size()) throw Error(LMGPU_INVALID, "smart factor: one measurement per key");
+    SmartGroup* g = nullptr;
+    for (SmartGroup& c : smart_)
+      if (std::memcmp(&c.params, &params, sizeof params) == 0) g = &c;
+    if (!g) {
+      smart_.emplace_back();
+      g = &smart_.back();
+      std::memset(&g->params, 0, sizeof params);  // (padding bytes take part in the comparison above)
+      g->params.linearizationMode = params.linearizationMode;
+      g->params.degeneracyMode = params.degeneracyMode;
+      g->params.retriangulationThreshold = params.retriangulationThreshold;
+      g->params.triangulation.rankTolerance = params.triangulation.rankTolerance;
+      g->params.triangulation.enableEPI = params.triangulation.enableEPI;
+      g->params.triangulation.useLOST = params.triangulation.useLOST;
+      g->params.triangulation.landmarkDistanceThreshold = params.triangulation.landmarkDistanceThreshold;
+      g->params.triangulation.dynamicOutlierRejectionThreshold = params.triangulation.dynamicOutlierRejectionThreshold;
+      g->params.triangulation.noise_inv_sigma = params.triangulation.noise_inv_sigma;
+      g->offsets.push_back(0);
+    }
+    g->gi.push_back(graphIndex);
+    for (uint64_t k : keys) {
+      const int32_t s = slotOf(k);
+      if (types_[(size_t)s] != LMGPU_POSE3) throw Error(LMGPU_INVALID, "smart factor: its variables must be Pose3");
+      g->slots.push_back(s);
+    }
+    g->z.insert(g->z.end(), z.begin(), z.end());
+    g->K5.insert(g->K5.end(), K5, K5 + 5);
+    g->invSigma.push_back(invSigma);
+    g->offsets.push_back((int32_t)g->slots.size());
+  }
+  /// graph indices of the smart factors in the order lmgpu_smart_get_points reports them (valid after finalize())
+  const std::vector<int32_t>& smartGraphIndices() const { return smartOrder_; }
+  int numSmartFactors() const { return lmgpu_num_smart_factors(h_); }
+  /// SmartProjectionFactor::point() of every smart factor: 3 doubles each (NaN unless VALID) and the TriangulationResult status
+  void smartPoints(std::vector<double>* points3, std::vector<int32_t>* status) const {
+    const size_t n = (size_t)std::max(0, numSmartFactors());
+    points3->assign(3 * n, 0.0);
+    status->assign(n, 0);
+    check(lmgpu_smart_get_points(h_, points3->data(), status->data()));
+  }
+  /// the augmented information matrix of one smart factor ((6 m + 1)^2, column-major) from the last linearization
+  std::vector<double> smartHessian(int32_t graphIndex, int32_t* m) const {
+    check(lmgpu_smart_get_hessian(h_, graphIndex, m, nullptr));
+    std::vector<double> out((size_t)(6 * *m + 1) * (size_t)(6 * *m + 1));
+    check(lmgpu_smart_get_hessian(h_, graphIndex, m, out.data()));
+    return out;
+  }
+  void smartReset() { check(lmgpu_smart_reset(h_)); }
+  lmgpu_smart_stats smartStats() const {
+    lmgpu_smart_stats st{};
+    check(lmgpu_get_smart_stats(h_, &st));
+    return st;
+  }
+
   void finalize() {
+    smartOrder_.clear();
+    for (const SmartGroup& g : smart_) {
+      check(lmgpu_add_smart_factors(h_, (int32_t)g.gi.size(), g.gi.data(), g.offsets.data(), g.slots.data(), g.z.data(), g.K5.data(),
+                                    g.invSigma.data(), &g.params));
+      smartOrder_.insert(smartOrder_.end(), g.gi.begin(), g.gi.end());
+    }
+    smart_.clear();
     for (auto& kv : buckets_) {
       const Bucket& b = kv.second;
       check(lmgpu_add_factor_bucket_robust(h_, std::get<0>(kv.first), (int32_t)b.gi.size(), b.gi.data(), b.slots.data(), b.meas.data(),
@@ -237,6 +304,13 @@ class Problem {
   std::unordered_map<uint64_t, int32_t> slot_;
   std::vector<size_t> xoff_, voff_;
   std::map<std::tuple<int32_t, int32_t, int32_t, double>, Bucket> buckets_;
+  struct SmartGroup {
+    lmgpu_smart_params params;
+    std::vector<int32_t> gi, offsets, slots;
+    std::vector<double> z, K5, invSigma;
+  };
+  std::vector<SmartGroup> smart_;
+  std::vector<int32_t> smartOrder_;
 };
 
 /// NonlinearOptimizer::defaultOptimize (gtsam/nonlinear/NonlinearOptimizer.cpp:62-117) around an iterate() callable: what the

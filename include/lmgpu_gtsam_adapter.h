@@ -56,6 +56,7 @@
 #include <gtsam/slam/BetweenFactor.h>
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
+#include <gtsam/slam/SmartProjectionPoseFactor.h>
 
 #include <algorithm>
 #include <memory>
@@ -204,6 +205,52 @@ inline bool extractFactor(const NonlinearFactor::shared_ptr& f, const Values& in
   return true;
 }
 
+typedef SmartProjectionPoseFactor<Cal3_S2> SmartPoseFactor;
+
+/// The parameters, noise model, sensor pose and cached result of a smart factor are protected members without accessors
+/// (gtsam/slam/SmartProjectionFactor.h:57-66, SmartFactorBase.h:73-83): read through pointers to members formed in a derived class.
+struct SmartAccess : SmartPoseFactor {
+  static const SmartProjectionParams& params(const SmartPoseFactor& f) { return f.*(&SmartAccess::params_); }
+  static double sigma(const SmartPoseFactor& f) { return (f.*(&SmartAccess::noiseModel_))->sigma(); }
+  static bool hasSensorPose(const SmartPoseFactor& f) {
+    const auto& b = f.*(&SmartAccess::body_P_sensor_);
+    return b && !b->equals(Pose3(), 0.0);
+  }
+  /// result_ is mutable (SmartProjectionFactor.h:62): point() / isValid() ... of the caller's factor answer with the device's result
+  static void setResult(const SmartPoseFactor& f, const TriangulationResult& r) {
+    const_cast<TriangulationResult&>(f.*(&SmartAccess::result_)) = r;  // (a pointer to member does not carry `mutable`)
+  }
+};
+
+inline lmgpu_triangulation_params smartTriangulationToC(const TriangulationParameters& p) {  // triangulation.h:562-609
+  if (p.useLOST) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: useLOST is not bound");
+  double inv = 0.0;
+  if (p.noiseModel && !std::dynamic_pointer_cast<noiseModel::Unit>(p.noiseModel)) {
+    const auto iso = std::dynamic_pointer_cast<noiseModel::Isotropic>(p.noiseModel);
+    if (!iso || iso->dim() != 2) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: the triangulation noise model must be Unit or Isotropic(2)");
+    inv = 1.0 / iso->sigma();
+  }
+  return lmgpu_triangulation_params{p.rankTolerance, p.enableEPI ? 1 : 0, 0, p.landmarkDistanceThreshold, p.dynamicOutlierRejectionThreshold, inv};
+}
+
+/// SmartProjectionParams (gtsam/slam/SmartFactorParams.h:42-133) -> lmgpu_smart_params; what the device does not implement throws
+inline lmgpu_smart_params toC(const SmartProjectionParams& p) {
+  if (p.linearizationMode != HESSIAN) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: only linearizationMode HESSIAN is bound");
+  if (p.degeneracyMode != ZERO_ON_DEGENERACY) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: only degeneracyMode ZERO_ON_DEGENERACY is bound");
+  if (p.throwCheirality || p.verboseCheirality) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: throwCheirality / verboseCheirality are not bound");
+  return lmgpu_smart_params{LMGPU_SMART_HESSIAN, LMGPU_SMART_ZERO_ON_DEGENERACY, p.retriangulationThreshold, smartTriangulationToC(p.triangulation)};
+}
+
+inline TriangulationResult smartResult(int32_t status, const double* p) {  // triangulation.h:631-660
+  switch (status) {
+    case LMGPU_TRI_VALID: return TriangulationResult(Point3(p[0], p[1], p[2]));
+    case LMGPU_TRI_BEHIND_CAMERA: return TriangulationResult::BehindCamera();
+    case LMGPU_TRI_OUTLIER: return TriangulationResult::Outlier();
+    case LMGPU_TRI_FAR_POINT: return TriangulationResult::FarPoint();
+    default: return TriangulationResult::Degenerate();
+  }
+}
+
 /// shared by the three optimizers: the device-resident problem + Values / VectorValues marshalling
 class Device {
  public:
@@ -218,6 +265,16 @@ class Device {
     p_.setVariables(keys, types);
     for (size_t i = 0; i < graph.size(); i++) {
       if (!graph[i]) continue;  // NonlinearFactorGraph::linearize keeps null factors null (NonlinearFactorGraph.cpp:214-233)
+      if (auto sp = std::dynamic_pointer_cast<SmartPoseFactor>(graph[i])) {  // gtsam/slam/SmartProjectionPoseFactor.h:43-152
+        if (SmartAccess::hasSensorPose(*sp)) throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factor: body_P_sensor is not bound");
+        const Cal3_S2& K = *sp->calibration();
+        const double K5[5] = {K.fx(), K.fy(), K.skew(), K.px(), K.py()};
+        std::vector<uint64_t> fk(sp->keys().begin(), sp->keys().end());
+        std::vector<double> z;
+        for (const Point2& m : sp->measured()) { z.push_back(m.x()); z.push_back(m.y()); }
+        p_.addSmartFactor((int32_t)i, fk, z, K5, 1.0 / SmartAccess::sigma(*sp), toC(SmartAccess::params(*sp)));
+        continue;
+      }
       auto nm = std::dynamic_pointer_cast<NoiseModelFactor>(graph[i]);
       if (!nm) throw std::invalid_argument("lmgpu adapter: only NoiseModelFactors are bound");
       int32_t type;
@@ -297,9 +354,28 @@ class Device {
     }
   }
 
+  /// SmartProjectionFactor::point() of every smart factor of `graph` as the device left it, by graph index (a TriangulationResult for
+  /// every slot of the graph, Degenerate where the slot holds no smart factor; empty for a graph without smart factors); with writeBack the factors' own result_ is set too
+  std::vector<TriangulationResult> smartPoints(const NonlinearFactorGraph& graph, bool writeBack) const {
+    if (p_.numSmartFactors() <= 0) return {};  // (a graph without smart factors pays nothing for this in its iterate())
+    std::vector<TriangulationResult> out(graph.size(), TriangulationResult::Degenerate());
+    std::vector<double> pts;
+    std::vector<int32_t> st;
+    p_.smartPoints(&pts, &st);
+    const std::vector<int32_t>& gi = p_.smartGraphIndices();
+    for (size_t k = 0; k < gi.size(); k++) {
+      out[(size_t)gi[k]] = smartResult(st[k], &pts[3 * k]);
+      if (writeBack)
+        if (auto sp = std::dynamic_pointer_cast<SmartPoseFactor>(graph[(size_t)gi[k]])) SmartAccess::setResult(*sp, out[(size_t)gi[k]]);
+    }
+    return out;
+  }
+
   /// the device-resident linearization as the GaussianFactorGraph NonlinearFactorGraph::linearize returns: one JacobianFactor
   /// per factor, already whitened (unit noise model), index-preserving
   GaussianFactorGraph::shared_ptr downloadLinearGraph(const NonlinearFactorGraph& graph) const {
+    // (a handle with smart factors keeps Jacobians of its internal factors, not the Hessian factors the reference would return: no graph)
+    if (p_.numSmartFactors() > 0) return GaussianFactorGraph::shared_ptr();
     const lmgpu_adapter::Problem::LinearGraph lg = p_.jacobians();  // one device copy per factor bucket
     auto out = std::make_shared<GaussianFactorGraph>();
     out->reserve(graph.size());
@@ -385,6 +461,7 @@ class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
     }
     state_.reset(new internal::LevenbergMarquardtState(dev_.download(cur->values), st.error, st.lambda, st.currentFactor,
                                                        (unsigned)st.iterations, (unsigned)st.totalNumberInnerIterations));
+    (void)dev_.smartPoints(graph_, true);  // the smart factors of the caller's graph answer point() with the device's result
     // the hook's contract (NonlinearOptimizer.h:136, LevenbergMarquardtOptimizer.cpp:281,307; read at tests/testNonlinearOptimizer.cpp:282):
     // the linearization this iteration solved -- lmgpu_iterate leaves it on the device (it linearizes once per outer iteration, before
     // the lambda loop, and the accepted step does not touch the Jacobians).  optimize() below discards the graph like defaultOptimize
@@ -407,6 +484,8 @@ class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
 
   /// LevenbergMarquardtOptimizer::linearize() (LevenbergMarquardtOptimizer.h:113): graph_.linearize(state_->values) on the device
   GaussianFactorGraph::shared_ptr linearize() const override {
+    if (dev_.problem().numSmartFactors() > 0)  // (the reference's loop would damp and solve the graph this returns; there is none to hand over)
+      throw lmgpu_adapter::Error(LMGPU_INVALID, "smart factors: the Piecewise mode is not bound, use WholeIterate");
     dev_.upload(state_->values);
     dev_.problem().linearize();
     return dev_.downloadLinearGraph(graph_);
@@ -421,6 +500,9 @@ class GpuLevenbergMarquardtOptimizer : public LevenbergMarquardtOptimizer {
 
   /// the whitened Jacobians of the last linearization as a GaussianFactorGraph (what iterate() returns in the reference)
   GaussianFactorGraph::shared_ptr lastLinearGraph() const { return dev_.downloadLinearGraph(graph_); }
+
+  /// SmartProjectionFactor::point() of the graph's smart factors by graph index, from the device (also written back after every iterate())
+  std::vector<TriangulationResult> gpuSmartPoints() const { return dev_.smartPoints(graph_, false); }
 
  private:
   lmgpu_pcg_params pcg_{};  // (declared before dev_: the constructor fills it while building dev_)
@@ -445,8 +527,11 @@ class GpuGaussNewtonOptimizer : public GaussNewtonOptimizer {
       throw IndeterminantLinearSystemException(e.key);
     }
     state_.reset(new internal::NonlinearOptimizerState(dev_.download(state_->values), st.error, (unsigned)st.iterations));
+    (void)dev_.smartPoints(graph_, true);
     return discardLinear_ ? GaussianFactorGraph::shared_ptr() : dev_.downloadLinearGraph(graph_);  // GaussNewtonOptimizer.cpp:49,65
   }
+
+  std::vector<TriangulationResult> gpuSmartPoints() const { return dev_.smartPoints(graph_, false); }
 
   const Values& optimize() override {  // see GpuLevenbergMarquardtOptimizer::optimize
     discardLinear_ = true;
