@@ -265,6 +265,7 @@ TEST_SYMBOLS = {
     "lmgpu_local_group_create": (ct.c_int, [ct.c_int32, ct.POINTER(ct.c_void_p)]),
     "lmgpu_local_group_destroy": (ct.c_int, [ct.c_void_p]),
     "lmgpu_comm_init_local": (ct.c_int, [_H, ct.c_void_p]),
+    "lmgpu_debug_table_digest": (ct.c_int, [_H, ct.c_int32, ct.c_char_p, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint64)]),
 }
 
 KT_NAMES = ("linearize", "lds_front", "hbm_assemble", "panel", "syrk", "backsub_hbm", "backsub_lds", "linear_error", "retract_error", "allreduce", "chain")

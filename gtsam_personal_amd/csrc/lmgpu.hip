@@ -240,6 +240,7 @@ struct lmgpu_handle {
   Plan plan;
   std::vector<Bucket> buckets;
   bool finalized = false, have_values = false, linearized = false, solved = false;
+  std::string finalize_err;  // non-empty: lmgpu_finalize_structure failed with this error, and the handle refuses every call but lmgpu_destroy with it
   bool have_jacobians = false;  // the pool holds the [A b] of the last linearization (they outlive `linearized`: an accepted step moves the values, not the Jacobians)
   std::vector<int32_t> graph_index_sorted;  // parallel to plan.factors
 
@@ -329,7 +330,7 @@ struct lmgpu_handle {
   // the clears and sentinel fills at the head of an elimination / a back-substitution, one launch each (fill_chunks_kernel)
   FillChunk* d_fill_elim = nullptr;
   FillChunk* d_fill_backsub = nullptr;
-  int n_fill_elim = -1, n_fill_backsub = -1, fill_backsub_merge = -1;
+  int n_fill_elim = -1, n_fill_backsub = -1;  // (-1: not built yet, ensure_fill_tables)
   double* d_bsd_x = nullptr;            // their published x (64 per block), preset to the all-ones sentinel at the start of a back-substitution
   unsigned int* d_bsd_ticket = nullptr; // one ticket counter per level
   size_t bsd_x_count = 0;
@@ -439,6 +440,13 @@ struct lmgpu_handle {
   int n_hidden = 0;             // hidden POINT3 variables in front of the caller's slots (one per smart factor with m >= 2); 0 without smart factors
   bool smart_speculative = false;  // the next error launch is tryLambda's speculative one: its cache update waits for smart_commit
   const int32_t* err_skip = nullptr;  // set around the trial launches of a line search: BucketDev::skip of the error launches
+#ifdef LMGPU_TEST_HOOKS
+  struct DigestRec {  // lmgpu_debug_table_digest (launch_tables.hpp): name, entries and FNV-1a of one launch table, taken by finalize
+    char name[32];
+    uint64_t count, fnv1a;
+  };
+  std::vector<DigestRec> table_digest;
+#endif
 };
 
 namespace {
@@ -775,52 +783,92 @@ static int ensure_dense_schedules(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
+// How an elimination clears the HBM fronts, which their children add to before their own level runs.  EACH: a memset per front (few large
+// fronts; a front whose gather writes first is left out).  SPAN: many mid-size fronts (general sparse graphs), one fill over their span
+// [lo, hi) of the pool; what lies between them ([R S d] / update storage of LDS fronts, laid out in the same post-order) is rewritten by
+// the elimination before it is read.  RANGES: many fronts scattered through the pool, one launch over the list of their ranges.
+enum { HBM_CLEAR_EACH, HBM_CLEAR_SPAN, HBM_CLEAR_RANGES };
+static int hbm_clear_regime(const lmgpu_handle* h, int64_t* lo_out, int64_t* hi_out) {
+  int n_hbm = 0;
+  int64_t lo = INT64_MAX, hi = 0, sum = 0;
+  for (const LevelWork& L : h->levels)
+    for (int fi : L.hbm) {
+      const int64_t cnt = (int64_t)h->h_fronts[fi].n * h->f_ld[fi] * (h->s_off[fi] >= 0 ? 2 : 1);
+      n_hbm++;
+      sum += cnt;
+      lo = std::min(lo, h->f_off[fi]);
+      hi = std::max(hi, h->f_off[fi] + cnt);
+    }
+  *lo_out = lo;
+  *hi_out = hi;
+  return n_hbm <= 4 ? HBM_CLEAR_EACH : (hi - lo <= 2 * sum ? HBM_CLEAR_SPAN : HBM_CLEAR_RANGES);
+}
+
+// deep trees: the LDS fronts of consecutive levels without HBM fronts in between are back-substituted as ONE dataflow launch
+static bool backsub_merged(const lmgpu_handle* h) {
+  return h->merge_backsub && h->cfg.world_size == 1 && !(h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT);
+}
+
+// The clears and sentinel fills at the head of an elimination and of a back-substitution (one fill_chunks_kernel launch each) and the
+// ranges of HBM_CLEAR_RANGES, in device memory.  They hold device addresses, so they are built at the first solve and not by finalize:
+// before anything is queued or captured, like the dense schedules above.
+static int ensure_fill_tables(lmgpu_handle* h) {
+  int64_t lo, hi;
+  const int regime = hbm_clear_regime(h, &lo, &hi);
+  if (h->n_fill_elim < 0) {
+    std::vector<FillChunk> fills;
+    add_fill(fills, h->d_status, sizeof(int), 0x7f7f7f7fu);
+    add_fill(fills, h->d_status + 1, sizeof(int), 0u);  // [1]: a dataflow hand-off timed out (1 + front id)
+    if (h->merge_elim || h->fuse_levels)  // one ticket counter per level (shared with the back-substitution, which clears them again)
+      add_fill(fills, h->d_bs_done, (size_t)(h->h_fronts.size() + h->levels.size() + 1) * sizeof(unsigned int), 0u);
+    if (h->fuse_levels) add_fill(fills, h->d_level_sync, (size_t)h->n_level_sync * sizeof(LevelSync), 0u);
+    if (regime == HBM_CLEAR_SPAN) add_fill(fills, h->pool + lo, (size_t)(hi - lo) * sizeof(double), 0u);
+    h->n_fill_elim = (int)fills.size();
+    const int rcu = upload(h, &h->d_fill_elim, fills);
+    if (rcu) return rcu;
+  }
+  if (regime == HBM_CLEAR_RANGES && !h->d_zero_ranges) {  // (f_ld and the pool offsets are multiples of 16)
+    std::vector<ZeroRange> zr;
+    for (const LevelWork& L : h->levels)
+      for (int fi : L.hbm) {
+        const bool gw = gather_writes(h, fi);
+        const int64_t cnt = (int64_t)h->h_fronts[fi].n * h->f_ld[fi];
+        if (!gw || h->s_off[fi] >= 0) zr.push_back(ZeroRange{h->f_off[fi], cnt});
+        if (!gw && h->s_off[fi] >= 0) zr.push_back(ZeroRange{h->s_off[fi], cnt});
+      }
+    h->n_zero_ranges = (int)zr.size();
+    const int rcu = upload(h, &h->d_zero_ranges, zr);
+    if (rcu) return rcu;
+  }
+  if (h->n_fill_backsub < 0) {
+    std::vector<FillChunk> fills;
+    if (backsub_merged(h)) {
+      add_fill(fills, h->d_bs_done, (size_t)(h->h_fronts.size() + h->levels.size() + 1) * sizeof(unsigned int), 0u);  // (the ticket counters)
+      add_fill(fills, h->delta, h->ntot * sizeof(double), 0xffffffffu);  // "not published yet": merged launches hand x over through delta itself
+    }
+    if (h->bsd_x_count > 0) {
+      add_fill(fills, h->d_bsd_x, h->bsd_x_count * sizeof(double), 0xffffffffu);  // "not published yet"
+      add_fill(fills, h->d_bsd_ticket, h->levels.size() * sizeof(unsigned int), 0u);
+    }
+    h->n_fill_backsub = (int)fills.size();
+    if (!fills.empty()) {
+      const int rcu = upload(h, &h->d_fill_backsub, fills);
+      if (rcu) return rcu;
+    }
+  }
+  return LMGPU_OK;
+}
+
 int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  // lambda by value (eager) or in device memory (graph replay)
   hipStream_t s = h->stream;
   const bool merge_el = h->merge_elim && !h->elim_segs.empty();
-  std::vector<FillChunk> fills;
-  const bool build_fills = h->n_fill_elim < 0;
-  if (build_fills) {
-    add_fill(fills, h->d_status, sizeof(int), 0x7f7f7f7fu);
-    add_fill(fills, h->d_status + 1, sizeof(int), 0u);  // [1]: a dataflow hand-off timed out (1 + front id)
-    if (merge_el || h->fuse_levels)  // one ticket counter per level (shared with the back-substitution, which clears them again)
-      add_fill(fills, h->d_bs_done, (size_t)(h->h_fronts.size() + h->levels.size() + 1) * sizeof(unsigned int), 0u);
-    if (h->fuse_levels) add_fill(fills, h->d_level_sync, (size_t)h->n_level_sync * sizeof(LevelSync), 0u);
-  }
-  {  // HBM fronts are accumulated into by their children (atomics) before their own level runs: clear them all first
+  {  // the clears: the HBM fronts (hbm_clear_regime), the status words and the counters of the merged and fused launches
     const int kt0 = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
-    int n_hbm = 0;
-    int64_t lo = INT64_MAX, hi = 0, sum = 0;
-    for (const LevelWork& L : h->levels)
-      for (int fi : L.hbm) {
-        const int64_t cnt = (int64_t)h->h_fronts[fi].n * h->f_ld[fi] * (h->s_off[fi] >= 0 ? 2 : 1);
-        n_hbm++;
-        sum += cnt;
-        lo = std::min(lo, h->f_off[fi]);
-        hi = std::max(hi, h->f_off[fi] + cnt);
-      }
-    if (n_hbm > 4 && hi - lo <= 2 * sum) {
-      // many mid-size fronts (general sparse graphs): one memset over their span; what lies between them ([R S d] / update
-      // storage of LDS fronts, laid out in the same post-order) is rewritten by this elimination before it is read
-      if (build_fills) add_fill(fills, h->pool + lo, (size_t)(hi - lo) * sizeof(double), 0u);
-    } else if (n_hbm > 4) {
-      // scattered through the pool: one launch over the list of their ranges (built once; f_ld and the pool offsets are multiples of 16)
-      if (!h->d_zero_ranges) {
-        std::vector<ZeroRange> zr;
-        for (const LevelWork& L : h->levels)
-          for (int fi : L.hbm) {
-            const bool gw = gather_writes(h, fi);
-            const int64_t cnt = (int64_t)h->h_fronts[fi].n * h->f_ld[fi];
-            if (!gw || h->s_off[fi] >= 0) zr.push_back(ZeroRange{h->f_off[fi], cnt});
-            if (!gw && h->s_off[fi] >= 0) zr.push_back(ZeroRange{h->s_off[fi], cnt});
-          }
-        h->n_zero_ranges = (int)zr.size();
-        const int rcu = upload(h, &h->d_zero_ranges, zr);
-        if (rcu) return rcu;
-      }
-      if (h->n_zero_ranges > 0)
-        hipLaunchKernelGGL(zero_ranges_kernel, dim3(16, h->n_zero_ranges), dim3(256), 0, s, (const ZeroRange*)h->d_zero_ranges, h->pool);
-    } else {
+    int64_t lo, hi;
+    const int regime = hbm_clear_regime(h, &lo, &hi);
+    if (regime == HBM_CLEAR_RANGES && h->n_zero_ranges > 0)
+      hipLaunchKernelGGL(zero_ranges_kernel, dim3(16, h->n_zero_ranges), dim3(256), 0, s, (const ZeroRange*)h->d_zero_ranges, h->pool);
+    if (regime == HBM_CLEAR_EACH)
       for (const LevelWork& L : h->levels)
         for (int fi : L.hbm) {
           // gather_writes: the upper triangle of the buffer the front is assembled into is written by the gather and a list of
@@ -830,12 +878,6 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
           if (!gw || h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->f_off[fi], 0, bytes, s));
           if (!gw && h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->s_off[fi], 0, bytes, s));
         }
-    }
-    if (build_fills) {
-      h->n_fill_elim = (int)fills.size();
-      const int rcu = upload(h, &h->d_fill_elim, fills);
-      if (rcu) return rcu;
-    }
     hipLaunchKernelGGL(fill_chunks_kernel, dim3(h->n_fill_elim), dim3(256), 0, s, (const FillChunk*)h->d_fill_elim);
     h->kt.end(kt0, s);
   }
@@ -1169,32 +1211,9 @@ static int backsub_group_form(const lmgpu_handle* h, const LevelWork& L) {
 int do_backsub(lmgpu_handle* h) {
   hipStream_t s = h->stream;
   if (h->cfg.world_size > 1) HIPCHECK(hipMemsetAsync(h->delta, 0, h->ntot * sizeof(double), s));
-  // deep trees: the LDS fronts of consecutive levels without HBM fronts in between go as ONE dataflow launch
-  const bool merge = h->merge_backsub && h->cfg.world_size == 1 && !(h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT);
+  const bool merge = backsub_merged(h);
   const bool no_bsd_runs = dev_switch("LMGPU_NO_BSD_RUNS") != nullptr;
   const int NFR = (int)h->h_fronts.size();
-  if (h->n_fill_backsub < 0 || h->fill_backsub_merge != (int)merge) {
-    std::vector<FillChunk> fills;
-    if (merge) {
-      add_fill(fills, h->d_bs_done, (size_t)(NFR + h->levels.size() + 1) * sizeof(unsigned int), 0u);  // (the ticket counters)
-      add_fill(fills, h->delta, h->ntot * sizeof(double), 0xffffffffu);  // "not published yet": merged launches hand x over through delta itself
-    }
-    if (h->bsd_x_count > 0) {
-      add_fill(fills, h->d_bsd_x, h->bsd_x_count * sizeof(double), 0xffffffffu);  // "not published yet"
-      add_fill(fills, h->d_bsd_ticket, h->levels.size() * sizeof(unsigned int), 0u);
-    }
-    if (h->d_fill_backsub) {
-      HIPCHECK(hipStreamSynchronize(s));
-      (void)hipFree(h->d_fill_backsub);
-      h->d_fill_backsub = nullptr;
-    }
-    h->n_fill_backsub = (int)fills.size();
-    h->fill_backsub_merge = (int)merge;
-    if (!fills.empty()) {
-      const int rcu = upload(h, &h->d_fill_backsub, fills);
-      if (rcu) return rcu;
-    }
-  }
   if (h->n_fill_backsub > 0) hipLaunchKernelGGL(fill_chunks_kernel, dim3(h->n_fill_backsub), dim3(256), 0, s, (const FillChunk*)h->d_fill_backsub);
   int seg_hi = -1, seg_lo = -1;  // levels of the pending segment (top, bottom)
   auto run_level = [&](const LevelWork& L) {  // one level as a launch of its own
@@ -1532,7 +1551,8 @@ static bool graph_eligible(const lmgpu_handle* h) {
 int do_solve_enqueue(lmgpu_handle* h, double lambda) {
   if (use_pcg(h)) return pcg_solve_enqueue(h, lambda);
   hipStream_t s = h->stream;
-  int rc = ensure_dense_schedules(h);  // (allocates and uploads at the first solve: before anything is queued or captured)
+  int rc = ensure_dense_schedules(h);  // (both allocate and upload at the first solve: before anything is queued or captured)
+  if (!rc) rc = ensure_fill_tables(h);
   if (rc) return rc;
   (void)hipEventRecord(h->ev[1], s);
   if (graph_eligible(h)) {
@@ -2028,6 +2048,8 @@ void assign_owners(lmgpu_handle* h) {
 }  // namespace
 
 // =============================================================================================== C ABI
+#include "launch_tables.hpp"  // the host build of the launch tables (finalize_structure_impl)
+
 extern "C" {
 
 int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
@@ -2147,7 +2169,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
-const char* lmgpu_last_error(const lmgpu_handle* h) { return h ? h->err.c_str() : "null handle"; }
+const char* lmgpu_last_error(const lmgpu_handle* h) { return !h ? "null handle" : (h->finalize_err.empty() ? h->err : h->finalize_err).c_str(); }
 int lmgpu_last_failed_slot(const lmgpu_handle* h) { return h ? h->failed_slot : -1; }
 
 int lmgpu_set_variables(lmgpu_handle* h, int32_t n_vars, const uint64_t* keys, const int32_t* types) {
@@ -2309,20 +2331,61 @@ static int finalize_vectors(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
-static int finalize_structure_impl(lmgpu_handle* h);
-int lmgpu_finalize_structure(lmgpu_handle* h) {
-  if (!h) return LMGPU_INVALID;
-  if (h->finalized) {
-    h->err = "lmgpu_finalize_structure: refused (h->finalized)";
-    return LMGPU_INVALID;
+// Every hipMalloc, upload and hipMemset of finalize: the pool, the launch tables in a fixed order, the vectors every solver needs, then the
+// scratch buffers.  A failure leaves the handle un-finalized (lmgpu_finalize_structure); lmgpu_destroy frees what was allocated.
+static int upload_launch_tables(lmgpu_handle* h, const LaunchTables& T) {
+  const Plan& P = h->plan;
+  int rc;
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipMalloc((void**)&h->pool, h->pool_doubles * sizeof(double)));
+  // once: entries the kernels read but never write (lower triangles inside diagonal tiles, padding columns) must be finite
+  HIPCHECK(hipMemset(h->pool, 0, h->pool_doubles * sizeof(double)));
+  if (h->pcg_structure) {  // Jacobians, factor descriptors, incidence list and vectors only
+    if ((rc = upload(h, &h->d_fd, T.fd))) return rc;
+    return finalize_vectors(h);
   }
-  if (!h->smart) return finalize_structure_impl(h);
-  // smart factors: the hidden points and the internal observation bucket enter the structure first, their device arrays come last
-  int rc = smart_prepare(h);
-  if (rc) return rc;
-  if ((rc = finalize_structure_impl(h))) return rc;
-  return h->device >= 0 ? smart_upload(h) : LMGPU_OK;
+  if (!T.packs.empty()) {  // (no records: d_leafpack stays null and the launches take the general descriptor path)
+    HIPCHECK(hipMalloc((void**)&h->d_leafpack, T.packs.size()));
+    HIPCHECK(hipMemcpy(h->d_leafpack, T.packs.data(), T.packs.size(), hipMemcpyHostToDevice));
+  }
+#define UPLOAD(dst, src) \
+  if ((rc = upload(h, &h->dst, src))) return rc
+  UPLOAD(d_fd, T.fd); UPLOAD(d_fronts, h->h_fronts); UPLOAD(d_ffac, T.ffac); UPLOAD(d_childs, T.childs);
+  UPLOAD(d_cmap, T.cmap); UPLOAD(d_fxoff, T.fxoff); UPLOAD(d_sxoff, T.sxoff); UPLOAD(d_lists, T.lists);
+  UPLOAD(d_bs_parent, T.bs_parent); UPLOAD(d_bs_pos, T.bs_pos);
+  if (h->merge_elim) UPLOAD(d_fill_upper, T.fill_upper);
+  UPLOAD(d_hbm_small, T.small); UPLOAD(d_bsd_table, T.bsd);
+  if (!T.bsd_runs_table.empty()) UPLOAD(d_bsd_run_table, T.bsd_runs_table);
+  UPLOAD(d_med_list, T.med); UPLOAD(d_f_off, h->f_off); UPLOAD(d_f_ld, h->f_ld); UPLOAD(d_row_begin, h->row_begin);
+  UPLOAD(d_med_fronts, T.med_fronts);
+  if (!T.level_tasks.empty()) UPLOAD(d_level_tasks, T.level_tasks);
+  UPLOAD(d_rowptr, T.rowptr); UPLOAD(d_rowsrc, T.rowsrc); UPLOAD(d_gpblk, T.gpblk); UPLOAD(d_gzero, T.gzero);
+  UPLOAD(d_gpent, T.gpent); UPLOAD(d_gvblk, T.gvblk); UPLOAD(d_gvent, T.gvent);
+#undef UPLOAD
+  if ((rc = finalize_vectors(h))) return rc;
+  // ---- scratch
+  const size_t NF = P.fronts.size(), wide_blocks = (size_t)(T.max_nf + BSW_NB - 1) / BSW_NB;
+  // (inverses of the 64 x 64 diagonal blocks in the fallback; the wide form parks M_B there, 128 x 128 per 128-row block)
+  HIPCHECK(hipMalloc((void**)&h->bs_inv, wide_blocks * BSW_NB * BSW_NB * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->inv16, (size_t)((P.max_front_n + NBO - 1) / NBO + 2) * 16 * 256 * sizeof(double)));  // 16 blocks per outer panel
+  h->pflags_panels = (P.max_front_n + NBO - 1) / NBO + 1;
+  HIPCHECK(hipMalloc((void**)&h->d_pflags, (size_t)h->pflags_panels * PDF_FLAG_WORDS * sizeof(unsigned int)));
+  // (x of the dataflow back-substitutions: whole 128-row blocks for the wide form, which covers the 64-row blocks of the others)
+  HIPCHECK(hipMalloc((void**)&h->bs_x, wide_blocks * BSW_NB * sizeof(double)));
+  HIPCHECK(hipMalloc((void**)&h->bs_flags, (size_t)((T.max_nf + NB - 1) / NB + 1) * sizeof(unsigned int)));
+  HIPCHECK(hipMalloc((void**)&h->d_bs_done, (NF + h->levels.size() + 1) * sizeof(unsigned int)));
+  if (h->bsd_x_count > 0) {
+    HIPCHECK(hipMalloc((void**)&h->d_bsd_x, h->bsd_x_count * sizeof(double)));
+    HIPCHECK(hipMalloc((void**)&h->d_bsd_ticket, h->levels.size() * sizeof(unsigned int)));
+  }
+  if (T.max_med > 0) HIPCHECK(hipMalloc((void**)&h->inv16_med, (size_t)T.max_med * 16 * 256 * sizeof(double)));
+  if (!T.level_tasks.empty()) HIPCHECK(hipMalloc((void**)&h->d_level_sync, std::max<size_t>(1, T.med_fronts.size()) * sizeof(LevelSync)));
+  HIPCHECK(hipMalloc((void**)&h->d_gcorner, std::max<size_t>(1, (size_t)T.n_gleaf) * sizeof(double)));
+  return LMGPU_OK;
 }
+
+// The symbolic plan, then the launch tables phase by phase (launch_tables.hpp: host only, on every handle), then -- on a device handle --
+// the one upload.
 static int finalize_structure_impl(lmgpu_handle* h) {
   h->pcg_structure = h->solver == LMGPU_SOLVER_PCG;  // PCG selected before finalize: no symbolic analysis, no fronts
   std::string e = h->plan.build(kLdsLimitN, !h->pcg_structure);
@@ -2330,7 +2393,7 @@ static int finalize_structure_impl(lmgpu_handle* h) {
     h->err = e;
     return LMGPU_INVALID;
   }
-  Plan& P = h->plan;
+  const Plan& P = h->plan;
   const int NFAC = (int)P.factors.size();
   h->ntot = P.xoff[P.n_vars];
   h->nstore = P.voff[P.n_vars];
@@ -2342,712 +2405,39 @@ static int finalize_structure_impl(lmgpu_handle* h) {
   h->graph_index_sorted.resize(NFAC);
   for (int i = 0; i < NFAC; i++) h->graph_index_sorted[i] = P.factors[i].graph_index;
 
-  // ---- ownership: which fronts / factors live on this rank
-  assign_owners(h);
-  const int NF = (int)P.fronts.size(), R = h->cfg.rank;
-  std::vector<char> fac_active(NFAC, 0), fac_counted(NFAC, 0);
-  for (int fi = 0; fi < NF; fi++) {
-    if (!h->front_active[fi]) continue;
-    const bool counted = (h->front_owner[fi] == R) || (h->front_owner[fi] < 0 && R == 0);
-    for (int32_t f : P.fronts[fi].factors) {
-      fac_active[f] = 1;
-      fac_counted[f] = counted;
-    }
-  }
-  if (h->pcg_structure) {  // every factor is local and counted (single rank)
-    std::fill(fac_active.begin(), fac_active.end(), 1);
-    std::fill(fac_counted.begin(), fac_counted.end(), 1);
-  }
-  h->fac_local.assign(NFAC, -1);
-  int nloc = 0;
-  for (int i = 0; i < NFAC; i++)
-    if (fac_active[i] && fac_counted[i]) h->fac_local[i] = nloc++;
-  h->n_counted = nloc;
-  for (int i = 0; i < NFAC; i++)
-    if (fac_active[i] && !fac_counted[i]) h->fac_local[i] = nloc++;
-  h->nfac = nloc;
-  for (Bucket& b : h->buckets) {
-    b.loc_of.assign(b.n, -1);
-    b.n_loc = 0;
-  }
-  for (int i = 0; i < NFAC; i++)  // factors are sorted by graph index; bucket-local order follows it
-    if (fac_active[i]) {
-      Bucket& b = h->buckets[P.factors[i].bucket];
-      b.loc_of[P.factors[i].idx] = 0;  // mark
-    }
-  for (Bucket& b : h->buckets)
-    for (int i = 0; i < b.n; i++)
-      if (b.loc_of[i] == 0) b.loc_of[i] = b.n_loc++;
+  LaunchTables T;
+  build_ownership(h);
+  build_pool_layout(h, T);
+  int rc = build_front_tables(h, T);
+  if (rc) return rc;
+  build_level_lists(h, T);
+  build_leaf_group_bins(h, T);
+  build_elim_segments(h);
+  build_solve_flags(h, T);
+  build_leaf_packs(h, T);
+  build_backsub_tables(h, T);
+  build_fused_levels(h, T);
+#ifdef LMGPU_TEST_HOOKS
+  digest_tables(h, T);
+#endif
+  return h->device >= 0 ? upload_launch_tables(h, T) : LMGPU_OK;  // (a structure-only handle: symbolic analysis and tables, no compute)
+}
 
-  // ---- pool layout: Jacobians | [R S d] + updates of LDS fronts | dense HBM fronts
-  int64_t off = 0;
-  for (Bucket& b : h->buckets) {
-    b.joff = off;
-    off += (int64_t)b.n_loc * b.rows * b.cols;
-    off = (off + 15) & ~int64_t(15);
+int lmgpu_finalize_structure(lmgpu_handle* h) {
+  if (!h) return LMGPU_INVALID;
+  if (h->finalized || !h->finalize_err.empty()) {
+    h->err = h->finalized ? "lmgpu_finalize_structure: refused (h->finalized)" : h->finalize_err;
+    return LMGPU_INVALID;
   }
-  h->h_fronts.assign(NF, FrontDesc{});
-  h->f_off.assign(NF, -1);
-  h->f_ld.assign(NF, 0);
-  h->s_off.assign(NF, -1);
-  std::vector<FacDesc> fd(h->nfac);
-  for (int i = 0; i < NFAC; i++) {
-    if (h->fac_local[i] < 0) continue;
-    const FactorRef& f = P.factors[i];
-    const Bucket& b = h->buckets[f.bucket];
-    FacDesc d{};
-    d.joff = b.joff + (int64_t)b.loc_of[f.idx] * b.rows * b.cols;
-    d.rows = (int16_t)b.rows;
-    d.d0 = (int16_t)P.dims[f.slots[0]];
-    d.d1 = (int16_t)(f.slots[1] >= 0 ? P.dims[f.slots[1]] : 0);
-    d.x0 = P.xoff[f.slots[0]];
-    d.x1 = f.slots[1] >= 0 ? P.xoff[f.slots[1]] : -1;
-    d.d2 = (int16_t)(f.slots[2] >= 0 ? P.dims[f.slots[2]] : 0);
-    d.x2 = f.slots[2] >= 0 ? P.xoff[f.slots[2]] : -1;
-    fd[h->fac_local[i]] = d;
-  }
-  struct GPairTmp {
-    int64_t key;
-    int16_t da, db;
-    GPairEntry ent;
-  };
-  struct GVarTmp {
-    int32_t pv;
-    int16_t dv;
-    bool leaf;  // a leaf entry (the leaf's S_v and d) or a factor entry (the factor's A_v and b)
-    GVarEntry ent;
-  };
-  int n_gleaf = 0;
-  std::vector<GPairTmp> gp_tmp;
-  std::vector<GZeroBlock> gzero;
-  std::vector<GVarTmp> gv_tmp;
-  std::vector<GPairBlock> gpblk;
-  std::vector<GPairEntry> gpent;
-  std::vector<GVarBlock> gvblk;
-  std::vector<GVarEntry> gvent;
-  h->gather.assign(NF, lmgpu_handle::GatherRange());
-  std::vector<FrontFac> ffac;
-  std::vector<int32_t> rowptr;
-  std::vector<RowSrc> rowsrc;
-  h->row_begin.assign(NF, -1);
-  std::vector<ChildRef> childs;
-  std::vector<int32_t> cmap, fxoff, sxoff;
-  std::vector<int32_t> colof(P.n_vars, -1);
-  for (int fi = 0; fi < NF; fi++) {
-    const Front& fr = P.fronts[fi];
-    FrontDesc& F = h->h_fronts[fi];
-    F.n = fr.n;
-    F.nf = fr.nf;
-    F.id = fi;
-    F.pad = 0;
-    if (!h->front_active[fi]) continue;
-    if ((h->cfg.world_size > 1 || (h->cfg.flags & LMGPU_FLAG_SPLIT_ROOT)) && h->front_owner[fi] < 0 && fr.cls == 1)
-      F.pad = (R == 0) ? 1 : 3;  // replicated; own terms on rank 0 only
-    if (fr.cls == 0) {
-      F.ld_rsd = fr.n;
-      F.rsd_off = off;
-      off += (int64_t)fr.nf * fr.n;
-      F.ld_u = fr.n - fr.nf;
-      // an LDS front whose parent lives in HBM hands its update over without an update matrix in HBM:
-      //   leaves (no children): the parent GATHERS -[S d]^T [S d] and the factor terms itself (kernels_schur.hpp), par_ld = -1
-      //   others: write their update matrix like any child; the parent's rows collect it in a fixed order
-      const bool direct = fr.parent >= 0 && P.fronts[fr.parent].cls == 1;
-      if (direct && fr.children.empty()) {
-        bool binary_only = true;  // the Schur gather reads factors of at most two variables
-        for (int32_t f : fr.factors) binary_only = binary_only && P.factors[f].slots[2] < 0;
-        if (!binary_only) {  // such a leaf writes its update matrix like any other child
-          F.u_off = off;
-          off += (int64_t)F.ld_u * F.ld_u;
-        } else {
-          F.par_ld = -1;
-          F.u_off = off;  // gather leaves also keep [S d] transposed ((n - nf) x nf: every variable's block contiguous)
-          off += (int64_t)F.ld_u * fr.nf;
-        }
-      } else {  // (a non-leaf LDS child of an HBM front writes its update matrix too: the parent's rows collect it in a fixed order)
-        F.u_off = off;
-        off += (int64_t)F.ld_u * F.ld_u;
-      }
-    } else {
-      const int ld = (fr.n + 15) & ~15;
-      off = (off + 15) & ~int64_t(15);
-      h->f_off[fi] = off;
-      h->f_ld[fi] = ld;
-      F.ld_rsd = ld;
-      F.rsd_off = off;
-      F.ld_u = ld;
-      F.u_off = off + (int64_t)fr.nf * ld + fr.nf;
-      off += (int64_t)fr.n * ld;
-      // the assembled contributions get a buffer of their own beside the working matrix when they arrive in row chunks while
-      // the factorisation is already running: replicated fronts (chunks all-reduced over the ranks)
-      if (F.pad & 1) {
-        h->s_off[fi] = off;
-        off += (int64_t)fr.n * ld;
-      }
-    }
-    for (size_t k = 0; k < fr.vars.size(); k++) colof[fr.vars[k]] = fr.col_off[k];
-    // factors
-    F.fac_begin = (int)ffac.size();
-    for (int32_t f : fr.factors) {
-      FrontFac ff;
-      ff.fac = h->fac_local[f];
-      ff.c0 = colof[P.factors[f].slots[0]];
-      ff.c1 = P.factors[f].slots[1] >= 0 ? colof[P.factors[f].slots[1]] : 0;
-      ff.c2 = P.factors[f].slots[2] >= 0 ? colof[P.factors[f].slots[2]] : 0;
-      ffac.push_back(ff);
-    }
-    F.fac_count = (int)ffac.size() - F.fac_begin;
-    // children present on this rank: map child's separator scalars (+ rhs) to this front's columns
-    F.child_begin = (int)childs.size();
-    for (int32_t c : fr.children) {
-      if (!h->front_active[c]) continue;
-      // a replicated child of a replicated front is identical on every rank: its update matrix enters the parent's sum over the ranks once
-      if ((F.pad & 1) && (h->h_fronts[c].pad & 1) && R != 0) continue;
-      const Front& ch = P.fronts[c];
-      FrontDesc& CF = h->h_fronts[c];
-      const int map_begin = (int)cmap.size();
-      for (size_t k = ch.n_frontal_vars; k < ch.vars.size(); k++)
-        for (int d = 0; d < P.dims[ch.vars[k]]; d++) cmap.push_back(colof[ch.vars[k]] + d);
-      cmap.push_back(fr.n - 1);
-      if (CF.par_ld < 0) {  // gather-mode leaf: register its S blocks and factors with this (HBM) front
-        cmap.resize(map_begin);
-        lmgpu_handle::GatherRange& G = h->gather[fi];
-        const int li = n_gleaf++;
-        if (G.leaf_count == 0) G.leaf_begin = li;
-        G.leaf_count++;
-        CF.par_map = li;  // index of its corner scalar
-        struct Ent {
-          int pc, lc, d;
-        };
-        std::vector<Ent> ents;
-        for (size_t k = ch.n_frontal_vars; k < ch.vars.size(); k++) ents.push_back({colof[ch.vars[k]], ch.col_off[k], P.dims[ch.vars[k]]});
-        ents.push_back({fr.n - 1, ch.n - 1, 1});
-        // (v, v) and (v, rhs) of a separator variable v come from ONE walk of schur_var_kernel over the leaves that see v: a leaf
-        // entry in v's list; the pair lists keep the blocks pa < pb < rhs  (split-diagonal form: every block is a pair block)
-        if (!h->schur_split_diag)
-          for (size_t x = 0; x + 1 < ents.size(); x++) {
-            if (ents[x].d + 1 > 16) {
-              h->err = "Schur gather: a separator variable of more than 15 dimensions does not fit the 16 x 16 tile of schur_var_kernel";
-              return LMGPU_INVALID;
-            }
-            gv_tmp.push_back(GVarTmp{ents[x].pc, (int16_t)ents[x].d, true,
-                                     GVarEntry{CF.u_off, (int16_t)ch.nf, (int16_t)(ents[x].lc - ch.nf), (int16_t)(ch.n - 1 - ch.nf), 0}});
-          }
-        for (size_t x = 0; x < ents.size(); x++)
-          for (size_t y = x; y < ents.size(); y++) {
-            if (x + 1 == ents.size()) continue;  // (rhs, rhs): the corner is a scalar reduction
-            if (!h->schur_split_diag && (y == x || y + 1 == ents.size())) continue;
-            Ent a = ents[x], b = ents[y];
-            if (a.pc > b.pc) std::swap(a, b);
-            gp_tmp.push_back(GPairTmp{((int64_t)a.pc << 32) | (uint32_t)b.pc, (int16_t)a.d, (int16_t)b.d,
-                                      GPairEntry{CF.u_off, (int16_t)((a.lc - ch.nf) * ch.nf), (int16_t)((b.lc - ch.nf) * ch.nf), (int16_t)ch.nf, 0}});
-          }
-        for (int32_t f : ch.factors)
-          for (int pos = 0; pos < 2; pos++) {
-            const int v = P.factors[f].slots[pos];
-            if (v < 0 || P.front_of_var[v] == c) continue;  // frontal in the leaf: no separator contribution
-            const FacDesc& fdd = fd[h->fac_local[f]];
-            gv_tmp.push_back(GVarTmp{colof[v], (int16_t)P.dims[v], false,
-                                     GVarEntry{fdd.joff, fdd.rows, (int16_t)(pos == 0 ? 0 : fdd.d0), (int16_t)(fdd.d0 + fdd.d1), 0}});
-          }
-        continue;
-      }
-      ChildRef cr{};
-      cr.u_off = CF.u_off;
-      cr.ld = CF.ld_u;
-      cr.m = ch.n - ch.nf;
-      cr.map_begin = map_begin;
-      cr.pad = c + 1;  // the child front (merged launches wait for children of their own launch)
-      childs.push_back(cr);
-    }
-    F.child_count = (int)childs.size() - F.child_begin;
-    if (fr.cls == 1 && (F.child_count > 0 || F.fac_count > 0)) {  // row -> sources, for the deterministic assembly
-      std::vector<std::vector<RowSrc>> rows(fr.n);
-      for (int k = 0; k < F.child_count; k++) {
-        const ChildRef& c = childs[F.child_begin + k];
-        for (int i = 0; i < c.m; i++) rows[cmap[c.map_begin + i]].push_back(RowSrc{F.child_begin + k, i});
-      }
-      for (int k = 0; k < F.fac_count; k++) {
-        const FrontFac& ff = ffac[F.fac_begin + k];
-        const FacDesc& d = fd[ff.fac];
-        const int nc = d.d0 + d.d1 + d.d2 + 1;
-        for (int p = 0; p < nc; p++) {
-          const int gp = (p < d.d0) ? ff.c0 + p : (p < d.d0 + d.d1 ? ff.c1 + (p - d.d0) : (p < d.d0 + d.d1 + d.d2 ? ff.c2 + (p - d.d0 - d.d1) : fr.n - 1));
-          rows[gp].push_back(RowSrc{-(F.fac_begin + k) - 1, p});
-        }
-      }
-      h->row_begin[fi] = (int32_t)rowptr.size();
-      for (int R2 = 0; R2 < fr.n; R2++) {
-        rowptr.push_back((int32_t)rowsrc.size());
-        rowsrc.insert(rowsrc.end(), rows[R2].begin(), rows[R2].end());
-      }
-      rowptr.push_back((int32_t)rowsrc.size());
-    }
-    if (!gp_tmp.empty() || !gv_tmp.empty()) {
-      lmgpu_handle::GatherRange& G = h->gather[fi];
-      std::stable_sort(gp_tmp.begin(), gp_tmp.end(), [](const GPairTmp& a, const GPairTmp& b) { return a.key < b.key; });
-      G.pblk_begin = (int)gpblk.size();
-      std::vector<GPairBlock> longs;
-      for (size_t i = 0; i < gp_tmp.size();) {
-        size_t j = i;
-        while (j < gp_tmp.size() && gp_tmp[j].key == gp_tmp[i].key) j++;
-        const GPairBlock blk{(int32_t)(gp_tmp[i].key >> 32), (int32_t)(gp_tmp[i].key & 0xffffffff), gp_tmp[i].da, gp_tmp[i].db,
-                             (int32_t)gpent.size(), (int32_t)(j - i)};
-        if (j - i <= 32) gpblk.push_back(blk); else longs.push_back(blk);
-        for (size_t e = i; e < j; e++) gpent.push_back(gp_tmp[e].ent);
-        i = j;
-      }
-      G.pblk_short = (int)gpblk.size() - G.pblk_begin;
-      G.pblk_long = (int)longs.size();
-      gpblk.insert(gpblk.end(), longs.begin(), longs.end());
-      std::stable_sort(gv_tmp.begin(), gv_tmp.end(), [](const GVarTmp& a, const GVarTmp& b) { return a.pv < b.pv; });
-      G.vblk_begin = (int)gvblk.size();
-      std::vector<GVarBlock> vlongs;
-      for (size_t i = 0; i < gv_tmp.size();) {
-        size_t j = i;
-        while (j < gv_tmp.size() && gv_tmp[j].pv == gv_tmp[i].pv) j++;
-        // the variable's leaf entries first, then its factor entries, each in leaf (elimination) order
-        int nleaf = 0;
-        for (size_t e = i; e < j; e++)
-          if (gv_tmp[e].leaf) nleaf++;
-        const GVarBlock blk{gv_tmp[i].pv, gv_tmp[i].dv, 0, (int32_t)gvent.size(), (int32_t)(j - i), nleaf};
-        const bool is_short = !h->schur_split_diag && nleaf <= SCHUR_VAR_SHORT && (int)(j - i) - nleaf <= SCHUR_VAR_SHORT;
-        if (is_short || h->schur_split_diag) gvblk.push_back(blk); else vlongs.push_back(blk);
-        for (int pass = 0; pass < 2; pass++)
-          for (size_t e = i; e < j; e++)
-            if (gv_tmp[e].leaf == (pass == 0)) gvent.push_back(gv_tmp[e].ent);
-        i = j;
-      }
-      G.vblk_short = h->schur_split_diag ? 0 : (int)gvblk.size() - G.vblk_begin;
-      gvblk.insert(gvblk.end(), vlongs.begin(), vlongs.end());
-      G.vblk_count = (int)gvblk.size() - G.vblk_begin;
-      if (F.child_count == 0) {  // no child adds to this front before its own level: the gather can be the first writer
-        G.write_ok = true;
-        G.zero_begin = (int)gzero.size();
-        struct VB { int c, d; };
-        std::vector<VB> vb;
-        for (size_t k = 0; k < fr.vars.size(); k++) vb.push_back({fr.col_off[k], P.dims[fr.vars[k]]});
-        vb.push_back({fr.n - 1, 1});
-        size_t gi = 0;  // gpblk of this front is sorted by key among shorts, longs appended: collect the covered keys
-        std::vector<int64_t> covered;
-        covered.reserve(G.pblk_short + G.pblk_long);
-        for (int q = 0; q < G.pblk_short + G.pblk_long; q++)
-          covered.push_back(((int64_t)gpblk[G.pblk_begin + q].pa << 32) | (uint32_t)gpblk[G.pblk_begin + q].pb);
-        if (!h->schur_split_diag) {  // a variable block covers (v, v) and (v, rhs); the corner workgroup covers (rhs, rhs)
-          for (int q = 0; q < G.vblk_count; q++) {
-            const int32_t pv = gvblk[G.vblk_begin + q].pv;
-            covered.push_back(((int64_t)pv << 32) | (uint32_t)pv);
-            covered.push_back(((int64_t)pv << 32) | (uint32_t)(fr.n - 1));
-          }
-          if (G.leaf_count > 0) covered.push_back(((int64_t)(fr.n - 1) << 32) | (uint32_t)(fr.n - 1));
-        }
-        std::sort(covered.begin(), covered.end());
-        (void)gi;
-        for (size_t x = 0; x < vb.size(); x++)
-          for (size_t y = x; y < vb.size(); y++) {
-            const int64_t key = ((int64_t)vb[x].c << 32) | (uint32_t)vb[y].c;
-            if (!std::binary_search(covered.begin(), covered.end(), key))
-              gzero.push_back(GZeroBlock{vb[x].c, vb[y].c, (int16_t)vb[x].d, (int16_t)vb[y].d});
-          }
-        G.zero_count = (int)gzero.size() - G.zero_begin;
-      }
-      std::vector<GPairTmp>().swap(gp_tmp);
-      std::vector<GVarTmp>().swap(gv_tmp);
-    }
-    F.fx_begin = (int)fxoff.size();
-    for (int k = 0; k < fr.n_frontal_vars; k++)
-      for (int d = 0; d < P.dims[fr.vars[k]]; d++) fxoff.push_back(P.xoff[fr.vars[k]] + d);
-    F.sx_begin = (int)sxoff.size();
-    for (size_t k = fr.n_frontal_vars; k < fr.vars.size(); k++)
-      for (int d = 0; d < P.dims[fr.vars[k]]; d++) sxoff.push_back(P.xoff[fr.vars[k]] + d);
-  }
-  h->pool_doubles = (size_t)off + 1024;  // slack: the syrk operand DMA may read up to 127 columns past a row end
-  // ---- level work lists (active fronts only)
-  h->levels.assign(P.n_levels, LevelWork());
-  std::vector<std::vector<std::vector<int>>> byLevelBin(P.n_levels, std::vector<std::vector<int>>(kNumBins));
-  for (int fi = 0; fi < NF; fi++) {
-    if (!h->front_active[fi]) continue;
-    const Front& fr = P.fronts[fi];
-    if (fr.cls == 1) {
-      h->levels[fr.level].hbm.push_back(fi);
-    } else {
-      int b = 0;
-      while (fr.n > kBinN[b]) b++;
-      if (h->h_fronts[fi].par_ld < 0) b += 6;  // gather leaf
-      byLevelBin[fr.level][b].push_back(fi);
-    }
-  }
-  // narrow levels (the upper part of a general clique tree): every launch is bound by one front's latency, so fronts of
-  // different LDS sizes share ONE launch (the largest occupied bin of the group) instead of up to six
-  for (int l = 0; l < P.n_levels; l++)
-    for (int g0 = 0; g0 < kNumBins; g0 += 6) {
-      size_t total = 0;
-      int top = -1;
-      for (int b = g0; b < g0 + 6; b++) {
-        total += byLevelBin[l][b].size();
-        if (!byLevelBin[l][b].empty()) top = b;
-      }
-      if (top < 0 || total > 512) continue;
-      for (int b = g0; b < top; b++) {
-        byLevelBin[l][top].insert(byLevelBin[l][top].end(), byLevelBin[l][b].begin(), byLevelBin[l][b].end());
-        byLevelBin[l][b].clear();
-      }
-    }
-  std::vector<int32_t> lists;
-  for (int l = 0; l < P.n_levels; l++) {
-    LevelWork& L = h->levels[l];
-    L.list_begin = (int)lists.size();
-    int c = 0;
-    for (int b = 0; b < kNumBins; b++) {
-      L.bin_begin[b] = c;
-      L.bin_srows[b] = kBinN[b % 6];
-      if (b >= 6) {
-        int mx = 1;
-        for (int fi : byLevelBin[l][b]) mx = std::max(mx, P.fronts[fi].nf);
-        L.bin_srows[b] = mx;
-      }
-      int jc = 96;
-      for (int fi : byLevelBin[l][b]) {
-        int tot = 0;
-        for (int32_t f : P.fronts[fi].factors) tot += fd[h->fac_local[f]].rows * (fd[h->fac_local[f]].d0 + fd[h->fac_local[f]].d1 + fd[h->fac_local[f]].d2 + 1);
-        jc = std::max(jc, std::min(tot, LDSF_JCAP));
-      }
-      L.bin_jcap[b] = (jc + 7) & ~7;
-      for (int fi : byLevelBin[l][b]) {
-        lists.push_back(fi);
-        L.lds_nf_max = std::max(L.lds_nf_max, (int)P.fronts[fi].nf);
-        L.lds_ns_max = std::max(L.lds_ns_max, (int)P.fronts[fi].n - (int)P.fronts[fi].nf - 1);
-        L.lds_rsd_max = std::max(L.lds_rsd_max, (int)P.fronts[fi].nf * ((int)P.fronts[fi].n | 1));
-      }
-      c += (int)byLevelBin[l][b].size();
-    }
-    L.bin_begin[kNumBins] = c;
-    L.list_count = c;
-  }
-  // ---- gather-leaf bins whose launch takes lds_front_group_kernel: decided here, per bin launch, from the structure alone
-  h->n_leaf_group_launches = 0;
-  if (!dev_switch("LMGPU_NO_LEAF_GROUPS") && !dev_switch("LMGPU_NO_LEAFPACK") && !h->pcg_structure)
-    for (LevelWork& L : h->levels)
-      for (int b = 6; b < kNumBins; b++) {
-        const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
-        int form = cnt > 0 ? 1 : 0;
-        for (int q = 0; q < cnt && form; q++) {
-          const FrontDesc& F = h->h_fronts[lists[L.list_begin + L.bin_begin[b] + q]];
-          const int f = leaf_group_form(F, ffac.data(), fd.data(), L.bin_jcap[b]);
-          form = f ? std::max(form, f) : 0;
-          L.bin_group_out[b] = std::max(L.bin_group_out[b], F.nf * F.n);
-          L.bin_group_maxfac[b] = std::max(L.bin_group_maxfac[b], F.fac_count);
-        }
-        L.bin_group[b] = (uint8_t)form;
-        if (form) h->n_leaf_group_launches++;
-      }
-  // ---- merged elimination launches: runs of consecutive levels, each a handful of LDS fronts, with no dense front between them (only
-  //      the top level of a run may hold dense fronts: they are launched after it and nothing in the run depends on them)
-  {
-    h->elim_segs.clear();
-    h->elim_seg_of.assign(P.n_levels, -1);
-    auto level_class = [&](int l, int* nmax, int* jcap, int* threads) { return level_lds_class(h, l, nmax, jcap, threads); };
-    int l = 0;
-    while (l < P.n_levels) {
-      int nmax, jcap, threads;
-      if (!level_class(l, &nmax, &jcap, &threads)) {
-        l++;
-        continue;
-      }
-      lmgpu_handle::ElimSeg E{l, l, nmax, jcap, threads};
-      while (E.lvl_hi + 1 < P.n_levels && h->levels[E.lvl_hi].hbm.empty()) {
-        int n2, j2, t2;
-        if (!level_class(E.lvl_hi + 1, &n2, &j2, &t2) || (t2 == 1024) != (E.threads == 1024)) break;
-        E.lvl_hi++;
-        E.nmax = std::max(E.nmax, n2);
-        E.jcap = std::max(E.jcap, j2);
-        E.threads = std::max(E.threads, t2);
-      }
-      if (E.lvl_hi > E.lvl_lo) {
-        h->elim_seg_of[E.lvl_lo] = (int)h->elim_segs.size();
-        for (int q = E.lvl_lo + 1; q <= E.lvl_hi; q++) h->elim_seg_of[q] = -2;
-        h->elim_segs.push_back(E);
-      }
-      l = E.lvl_hi + 1;
-    }
-  }
-  h->finalized = true;
-  if (h->device < 0) return LMGPU_OK;  // structure-only handle: symbolic analysis available, no compute
-
-  h->n_hbm_fronts = 0;
-  for (const LevelWork& L : h->levels) h->n_hbm_fronts += (int)L.hbm.size();
-  // deep trees are launch-bound: replay the solve as a graph (LMGPU_GRAPH=0 / 1 overrides the depth rule)
-  h->use_graph = (int)h->levels.size() >= 12;
-  h->merge_backsub = (int)h->levels.size() >= 12;
-  if (const char* e = dev_switch("LMGPU_MERGE_BACKSUB")) h->merge_backsub = atoi(e) != 0;
-  h->merge_elim = (int)h->levels.size() >= 12 && h->cfg.world_size == 1;
-  if (const char* e = dev_switch("LMGPU_MERGE_ELIM")) h->merge_elim = atoi(e) != 0 && h->cfg.world_size == 1;
-  if (h->elim_segs.empty()) h->merge_elim = false;
-  if (const char* e = getenv("LMGPU_GRAPH")) h->use_graph = atoi(e) != 0;
-  // ---- device upload
-  HIPCHECK(hipSetDevice(h->device));
-  HIPCHECK(hipMalloc((void**)&h->pool, h->pool_doubles * sizeof(double)));
-  // once: entries the kernels read but never write (lower triangles inside diagonal tiles, padding columns) must be finite
-  HIPCHECK(hipMemset(h->pool, 0, h->pool_doubles * sizeof(double)));
-  int rc;
-  if (h->pcg_structure) {  // Jacobians, factor descriptors, incidence list and vectors only
-    if ((rc = upload(h, &h->d_fd, fd))) return rc;
-    return finalize_vectors(h);
-  }
-  if (!dev_switch("LMGPU_NO_LEAFPACK")) {  // packed records of the LDS fronts, launch by launch
-    std::vector<char> packs;
-    for (LevelWork& L : h->levels)
-      for (int b = 0; b < kNumBins; b++) {
-        const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
-        if (cnt == 0) continue;
-        int maxfac = 0;
-        for (int q = 0; q < cnt; q++) maxfac = std::max(maxfac, std::min((int)LDSF_MAXB, h->h_fronts[lists[L.list_begin + L.bin_begin[b] + q]].fac_count));
-        const int stride = LEAFPACK_FAC + 32 * std::max(1, maxfac);
-        packs.resize((packs.size() + 127) & ~size_t(127));
-        L.pack_off[b] = (int64_t)packs.size();
-        L.pack_stride[b] = stride;
-        packs.resize(packs.size() + (size_t)cnt * stride, 0);
-        for (int q = 0; q < cnt; q++) {
-          const FrontDesc& F = h->h_fronts[lists[L.list_begin + L.bin_begin[b] + q]];
-          char* rec = packs.data() + L.pack_off[b] + (size_t)q * stride;
-          std::memcpy(rec, &F, sizeof(FrontDesc));
-          int32_t* hdr = (int32_t*)(rec + LEAFPACK_HDR);
-          hdr[0] = hdr[1] = hdr[2] = hdr[3] = 0;
-          if (F.fac_count < 1 || F.fac_count > LDSF_MAXB) continue;
-          LFac* lf = (LFac*)(rec + LEAFPACK_FAC);
-          int o = 0;
-          bool contig = true;
-          for (int k = 0; k < F.fac_count; k++) {
-            const FrontFac& ff = ffac[F.fac_begin + k];
-            const FacDesc& d = fd[ff.fac];
-            lf[k].joff = d.joff;
-            lf[k].c0 = ff.c0;
-            lf[k].c1 = ff.c1;
-            lf[k].c2 = ff.c2;
-            lf[k].rows = d.rows;
-            lf[k].d0 = d.d0;
-            lf[k].d1 = d.d1;
-            lf[k].d2 = d.d2;
-            lf[k].off = (int16_t)o;
-            lf[k].sz = (int16_t)(d.rows * (d.d0 + d.d1 + d.d2 + 1));
-            if (k > 0 && lf[k].joff != lf[0].joff + o) contig = false;
-            o += lf[k].sz;
-          }
-          if (o > L.bin_jcap[b]) continue;  // more than one staging batch: the general path
-          hdr[0] = F.fac_count;
-          hdr[1] = o;
-          hdr[2] = contig ? 1 : 0;
-          if (F.nf <= LEAFPACK_MAXNF) {
-            hdr[3] = 1;
-            int32_t* xo = (int32_t*)(rec + LEAFPACK_XO);
-            for (int i = 0; i < F.nf; i++) xo[i] = fxoff[F.fx_begin + i];
-          }
-        }
-      }
-    if (!packs.empty() && h->device >= 0) {
-      HIPCHECK(hipSetDevice(h->device));
-      HIPCHECK(hipMalloc((void**)&h->d_leafpack, packs.size()));
-      HIPCHECK(hipMemcpy(h->d_leafpack, packs.data(), packs.size(), hipMemcpyHostToDevice));
-    }
-  }
-  if ((rc = upload(h, &h->d_fd, fd))) return rc;
-  if ((rc = upload(h, &h->d_fronts, h->h_fronts))) return rc;
-  if ((rc = upload(h, &h->d_ffac, ffac))) return rc;
-  if ((rc = upload(h, &h->d_childs, childs))) return rc;
-  if ((rc = upload(h, &h->d_cmap, cmap))) return rc;
-  if ((rc = upload(h, &h->d_fxoff, fxoff))) return rc;
-  if ((rc = upload(h, &h->d_sxoff, sxoff))) return rc;
-  if ((rc = upload(h, &h->d_lists, lists))) return rc;
-  {
-    std::vector<int32_t> bs_parent(NF, -1), bs_pos(NF, -1);
-    for (size_t q = 0; q < lists.size(); q++) bs_pos[lists[q]] = (int32_t)q;
-    for (int fi = 0; fi < NF; fi++) {
-      const int par = P.fronts[fi].parent;
-      if (par >= 0 && P.fronts[par].cls == 0) bs_parent[fi] = par;
-    }
-    if ((rc = upload(h, &h->d_bs_parent, bs_parent))) return rc;
-    if ((rc = upload(h, &h->d_bs_pos, bs_pos))) return rc;
-    HIPCHECK(hipMalloc((void**)&h->d_bs_done, (size_t)(NF + h->levels.size() + 1) * sizeof(unsigned int)));
-  }
-  h->n_lds_fronts = (int)lists.size();
-  if (h->merge_elim) {
-    std::vector<FillUpper> fu;
-    for (const lmgpu_handle::ElimSeg& E : h->elim_segs)
-      for (int q = h->levels[E.lvl_lo].list_begin; q < h->levels[E.lvl_hi].list_begin + h->levels[E.lvl_hi].list_count; q++) {
-        const FrontDesc& F = h->h_fronts[lists[q]];
-        fu.push_back(FillUpper{F.u_off, F.n - F.nf, F.ld_u});
-      }
-    h->n_fill_upper = (int)fu.size();
-    if ((rc = upload(h, &h->d_fill_upper, fu))) return rc;
-  }
-  {
-    std::vector<int32_t> small;
-    for (LevelWork& L : h->levels) {
-      L.small_begin = (int)small.size();
-      for (int fi : L.hbm)
-        if (P.fronts[fi].nf <= BSS_MAX_NF) small.push_back(fi);
-      L.small_count = (int)small.size() - L.small_begin;
-    }
-    if ((rc = upload(h, &h->d_hbm_small, small))) return rc;
-    std::vector<BsdBlock> bsd;
-    int32_t xoff = 0;
-    for (LevelWork& L : h->levels) {
-      L.bsd_begin = (int)bsd.size();
-      for (int q = 0; q < L.small_count; q++) {
-        const int fi = small[L.small_begin + q], nblk = (P.fronts[fi].nf + 63) / 64;
-        const FrontDesc& F = h->h_fronts[fi];
-        for (int b = nblk - 1; b >= 0; b--) bsd.push_back(BsdBlock{h->f_off[fi], h->f_ld[fi], F.n, F.nf, F.fx_begin, F.sx_begin, F.id, b, xoff});
-        xoff += 64 * nblk;
-      }
-      L.bsd_count = (int)bsd.size() - L.bsd_begin;
-    }
-    h->bsd_x_count = (size_t)xoff;
-    if ((rc = upload(h, &h->d_bsd_table, bsd))) return rc;
-    {
-      h->bsd_runs.clear();
-      h->bsd_run_of.assign(h->levels.size(), -1);
-      std::vector<BsdBlock> runs;
-      // a level can open a run when every HBM front on it is block-solved; the next level down joins when, in addition, none of its
-      // fronts hangs below an LDS front of the run's levels (those are solved by the merged LDS launch BEHIND the run's launch)
-      auto opens = [&](int l) {
-        const LevelWork& L = h->levels[l];
-        return L.bsd_count > 0 && L.small_count == (int)L.hbm.size();
-      };
-      auto joins = [&](int l, int hi) {
-        if (!opens(l)) return false;
-        for (int fi : h->levels[l].hbm) {
-          const int par = P.fronts[fi].parent;
-          if (par >= 0 && P.fronts[par].cls != 1 && P.fronts[par].level <= hi) return false;
-        }
-        return true;
-      };
-      int l = (int)h->levels.size() - 1;
-      while (l >= 0) {
-        if (!opens(l)) {
-          l--;
-          continue;
-        }
-        int lo = l;
-        while (lo - 1 >= 0 && joins(lo - 1, l)) lo--;
-        if (lo < l) {
-          lmgpu_handle::BsdRun R{l, lo, (int)runs.size(), 0};
-          for (int q = l; q >= lo; q--) runs.insert(runs.end(), bsd.begin() + h->levels[q].bsd_begin, bsd.begin() + h->levels[q].bsd_begin + h->levels[q].bsd_count);
-          R.count = (int)runs.size() - R.begin;
-          h->bsd_run_of[l] = (int)h->bsd_runs.size();
-          for (int q = l - 1; q >= lo; q--) h->bsd_run_of[q] = -2;
-          h->bsd_runs.push_back(R);
-        }
-        l = lo - 1;
-      }
-      if (!runs.empty() && (rc = upload(h, &h->d_bsd_run_table, runs))) return rc;
-    }
-    if (xoff > 0) {
-      HIPCHECK(hipMalloc((void**)&h->d_bsd_x, (size_t)xoff * sizeof(double)));
-      HIPCHECK(hipMalloc((void**)&h->d_bsd_ticket, h->levels.size() * sizeof(unsigned int)));
-    }
-    std::vector<int32_t> med;
-    h->is_med.assign(NF, 0);
-    int max_med = 0;
-    for (LevelWork& L : h->levels) {
-      L.med_begin = (int)med.size();
-      for (int fi : L.hbm) {
-        const Front& fr = P.fronts[fi];
-        const FrontDesc& F = h->h_fronts[fi];
-        const lmgpu_handle::GatherRange& G = h->gather[fi];
-        if (fr.nf > NBO || (F.pad & 1) || G.leaf_count > 0 || G.pblk_short + G.pblk_long + G.vblk_count > 0 || dev_switch("LMGPU_NO_MED")) continue;
-        med.push_back(fi);
-        h->is_med[fi] = 1;
-        L.med_max_fac = std::max(L.med_max_fac, F.fac_count);
-        L.med_max_child = std::max(L.med_max_child, F.child_count);
-        L.med_max_nf = std::max(L.med_max_nf, fr.nf);
-        L.med_max_cols = std::max(L.med_max_cols, fr.n - fr.nf);
-        L.med_max_n = std::max(L.med_max_n, (int)fr.n);
-      }
-      L.med_count = (int)med.size() - L.med_begin;
-      max_med = std::max(max_med, L.med_count);
-    }
-    if ((rc = upload(h, &h->d_med_list, med))) return rc;
-    if (max_med > 0) HIPCHECK(hipMalloc((void**)&h->inv16_med, (size_t)max_med * 16 * 256 * sizeof(double)));
-    if ((rc = upload(h, &h->d_f_off, h->f_off))) return rc;
-    if ((rc = upload(h, &h->d_f_ld, h->f_ld))) return rc;
-  }
-  if ((rc = upload(h, &h->d_row_begin, h->row_begin))) return rc;
-  {
-    std::vector<MedFront> mfs;
-    for (const LevelWork& L : h->levels)
-      for (int fi : L.hbm)
-        if (h->is_med[fi]) mfs.push_back(MedFront{h->h_fronts[fi], h->f_off[fi], h->f_ld[fi], h->row_begin[fi]});
-    if ((rc = upload(h, &h->d_med_fronts, mfs))) return rc;
-    // ---- fused level launches: task lists [LDS fronts | assembly rows | diagonal blocks | panel strips | update quadrants] per level
-    h->fuse_levels = (int)h->levels.size() >= 12 && h->cfg.world_size == 1;
-    if (const char* e = dev_switch("LMGPU_FUSE_LEVELS")) h->fuse_levels = atoi(e) != 0 && h->cfg.world_size == 1;
-    std::vector<LevelTask> tasks;
-    int li = 0;
-    for (LevelWork& L : h->levels) {
-      const int l = li++;
-      L.fuse_task_count = 0;
-      int nmax, jcap, threads;
-      if (!h->fuse_levels || L.med_count == 0 || !(L.med_max_fac > 0 || L.med_max_child > 0)) continue;
-      if (h->merge_elim && h->elim_seg_of[l] != -1) continue;  // its LDS fronts belong to a merged launch
-      if (!level_lds_class(h, l, &nmax, &jcap, &threads)) continue;
-      L.fuse_task_begin = (int)tasks.size();
-      L.fuse_nmax = nmax;
-      L.fuse_jcap = jcap;
-      // four waves per workgroup for every role: with sixteen (what a launch of wide LDS fronts alone takes) the kernel is held to 128 VGPRs and the
-      // register Cholesky of the dense fronts' diagonal blocks spills (sphere2500: 1.93 vs 1.87 ms)
-      L.fuse_threads = 256;
-      if (const char* e = dev_switch("LMGPU_FUSE_THREADS")) L.fuse_threads = atoi(e) == 1024 && threads == 1024 ? 1024 : 256;
-      for (int q = 0; q < L.list_count; q++) tasks.push_back(LevelTask{0, L.list_begin + q, 0, 0});
-      for (int m = 0; m < L.med_count; m++) {
-        const FrontDesc& F = mfs[L.med_begin + m].F;
-        for (int r = 0; r < F.n; r += 4) tasks.push_back(LevelTask{1, m, r, 0});
-      }
-      for (int m = 0; m < L.med_count; m++) tasks.push_back(LevelTask{2, m, 0, 0});
-      for (int m = 0; m < L.med_count; m++) {
-        const FrontDesc& F = mfs[L.med_begin + m].F;
-        for (int st = 0; st * 64 < F.n - F.nf; st++) tasks.push_back(LevelTask{3, m, st, 0});
-      }
-      for (int m = 0; m < L.med_count; m++) {
-        const FrontDesc& F = mfs[L.med_begin + m].F;
-        const int S = (F.n - F.nf + 63) / 64;
-        for (int sj = 0; sj < S; sj++)
-          for (int si = 0; si <= sj; si++)
-            for (int qd = 0; qd < 4; qd++) tasks.push_back(LevelTask{4, m, si | (sj << 8), qd});
-      }
-      L.fuse_task_count = (int)tasks.size() - L.fuse_task_begin;
-    }
-    if (!tasks.empty()) {
-      if ((rc = upload(h, &h->d_level_tasks, tasks))) return rc;
-      h->n_level_sync = (int)mfs.size();
-      HIPCHECK(hipMalloc((void**)&h->d_level_sync, std::max<size_t>(1, mfs.size()) * sizeof(LevelSync)));
-    } else {
-      h->fuse_levels = false;
-    }
-  }
-  if ((rc = upload(h, &h->d_rowptr, rowptr))) return rc;
-  if ((rc = upload(h, &h->d_rowsrc, rowsrc))) return rc;
-  if ((rc = upload(h, &h->d_gpblk, gpblk))) return rc;
-  if ((rc = upload(h, &h->d_gzero, gzero))) return rc;
-  if ((rc = upload(h, &h->d_gpent, gpent))) return rc;
-  if ((rc = upload(h, &h->d_gvblk, gvblk))) return rc;
-  if ((rc = upload(h, &h->d_gvent, gvent))) return rc;
-  HIPCHECK(hipMalloc((void**)&h->d_gcorner, std::max<size_t>(1, (size_t)n_gleaf) * sizeof(double)));
-  if ((rc = finalize_vectors(h))) return rc;
-  {
-    int max_nf = 1;
-    for (int fi = 0; fi < NF; fi++)
-      if (h->front_active[fi] && P.fronts[fi].cls == 1) max_nf = std::max(max_nf, P.fronts[fi].nf);
-    const int max_blk = (max_nf + NB - 1) / NB;
-    // (inverses of the 64 x 64 diagonal blocks in the fallback; the wide form parks M_B there, 128 x 128 per 128-row block)
-    HIPCHECK(hipMalloc((void**)&h->bs_inv, (size_t)((max_nf + BSW_NB - 1) / BSW_NB) * BSW_NB * BSW_NB * sizeof(double)));
-    HIPCHECK(hipMalloc((void**)&h->inv16, (size_t)((P.max_front_n + NBO - 1) / NBO + 2) * 16 * 256 * sizeof(double)));  // 16 blocks per outer panel
-    h->pflags_panels = (P.max_front_n + NBO - 1) / NBO + 1;
-    HIPCHECK(hipMalloc((void**)&h->d_pflags, (size_t)h->pflags_panels * PDF_FLAG_WORDS * sizeof(unsigned int)));
-
-    // (x of the dataflow back-substitutions: whole 128-row blocks for the wide form, which covers the 64-row blocks of the others)
-    HIPCHECK(hipMalloc((void**)&h->bs_x, (size_t)((max_nf + BSW_NB - 1) / BSW_NB) * BSW_NB * sizeof(double)));
-    HIPCHECK(hipMalloc((void**)&h->bs_flags, (size_t)(max_blk + 1) * sizeof(unsigned int)));
-  }
-  return LMGPU_OK;
+  // smart factors: the hidden points and the internal observation bucket enter the structure first, their device arrays come last
+  int rc = h->smart ? smart_prepare(h) : LMGPU_OK;
+  if (!rc) rc = finalize_structure_impl(h);
+  if (!rc && h->smart && h->device >= 0) rc = smart_upload(h);
+  // finalized only once the build and the upload have succeeded; a handle that failed either keeps its error and refuses everything
+  // but lmgpu_destroy, which frees what was allocated
+  if (rc) h->finalize_err = h->err;
+  else h->finalized = true;
+  return rc;
 }
 
 // (the hidden points of smart factors are no part of any packed vector at the boundary: they are the first 3 * n_hidden scalars inside)
@@ -4262,6 +3652,15 @@ int lmgpu_selftest_chain_schedule(int n, int nf, int i0, int nsteps, int far_pct
 }
 
 #ifdef LMGPU_TEST_HOOKS
+int lmgpu_debug_table_digest(lmgpu_handle* h, int32_t max, char* names32, uint64_t* counts, uint64_t* fnv1a) {
+  if (!h || !h->finalized) return -1;
+  for (int i = 0; i < std::min(max, (int32_t)h->table_digest.size()); i++) {
+    std::memcpy(names32 + 32 * i, h->table_digest[i].name, 32);
+    counts[i] = h->table_digest[i].count;
+    fnv1a[i] = h->table_digest[i].fnv1a;
+  }
+  return (int)h->table_digest.size();
+}
 int lmgpu_local_group_destroy(lmgpu_local_group* g) {
   delete g;
   return LMGPU_OK;

@@ -138,11 +138,12 @@ class LevenbergMarquardtOptimizer:
 
     `ordering` (an Ordering = list of keys in elimination order) is a boundary input, as it is for the
     reference's hot loop (computed once at construction, LevenbergMarquardtParams.h:112-117).
-    `device=-1` builds a structure-only handle (symbolic analysis, no compute)."""
+    `device=-1` builds a structure-only handle (symbolic analysis and launch tables, no compute); `finalize_only=True` stops a device
+    handle after lmgpu_finalize_structure as well: no communicator, no values, no LM state."""
 
     def __init__(self, graph: NonlinearFactorGraph, initialValues: Values, ordering=None, params: LevenbergMarquardtParams | None = None,
                  device: int = 0, rank: int = 0, world_size: int = 1, comm_id: bytes | None = None,
-                 local_group=None, split_root: bool = False):
+                 local_group=None, split_root: bool = False, finalize_only: bool = False):
         self.params = params or LevenbergMarquardtParams()
         pcg = _check_linear_solver(self.params)
         ordering = ordering if ordering is not None else self.params.ordering
@@ -196,7 +197,7 @@ class LevenbergMarquardtOptimizer:
         self._voff = np.concatenate([[0], np.cumsum([VAR_STORE_DEV[t] for t in self._types])]).astype(np.int64)
         self._xoff = np.concatenate([[0], np.cumsum([VAR_DIM[t] for t in self._types])]).astype(np.int64)
         self.state = _lib.lmgpu_lm_state()
-        if device >= 0:
+        if device >= 0 and not finalize_only:
             if world_size > 1 or split_root:
                 if local_group is not None:  # in-process communicator (tests): one thread per rank
                     self._check(self.lib.lmgpu_comm_init_local(self._h, local_group))

@@ -802,6 +802,11 @@ typedef struct lmgpu_local_group lmgpu_local_group;
 int lmgpu_local_group_create(int32_t world_size, lmgpu_local_group** out);
 int lmgpu_local_group_destroy(lmgpu_local_group* g);
 int lmgpu_comm_init_local(lmgpu_handle* h, lmgpu_local_group* g);
+/* The launch tables finalize built, as digests: one record per table that is uploaded and per piece of the host launch metadata (the
+ * level work lists in the parts the build phases fill, gather ranges, merged segments, block-solve runs, pool layout, solve-form
+ * flags) -- its name (32 bytes, zero-terminated), its number of entries and the FNV-1a of its fields.  Available on structure-only
+ * handles too.  Writes at most `max` records; returns the number of records the handle has, or -1 before finalize. */
+int lmgpu_debug_table_digest(lmgpu_handle* h, int32_t max, char* names32, uint64_t* counts, uint64_t* fnv1a);
 #endif
 
 /* ---- micro-benchmarks used by bench.py for roofline peaks (device-only, no graph needed) ---- */
