@@ -409,28 +409,33 @@ def ccolamd_csc(n_rows, n_cols, col_ptr, row_idx, cmember):
     return p[:n_cols].copy()
 
 
-def _ccolamd_callback(n_rows, n_cols, col_ptr, row_idx, cmember, perm_out):
-    try:
-        cp = np.ctypeslib.as_array(col_ptr, shape=(n_cols + 1,))
-        ri = np.ctypeslib.as_array(row_idx, shape=(max(1, int(cp[n_cols])),))
-        cm = np.ctypeslib.as_array(cmember, shape=(n_cols,))
-        perm = ccolamd_csc(n_rows, n_cols, cp, ri, cm)
-        out = np.ctypeslib.as_array(perm_out, shape=(n_cols,))
-        out[:] = perm
-        return 1
-    except Exception:  # noqa: BLE001 -- a Python exception must not unwind through the C caller
-        import traceback
-        traceback.print_exc()
-        return 0
+def _callback_of(order):
+    """the C callback around order(n_rows, n_cols, col_ptr, row_idx, cmember) -> permutation"""
+    def callback(n_rows, n_cols, col_ptr, row_idx, cmember, perm_out):
+        try:
+            cp = np.ctypeslib.as_array(col_ptr, shape=(n_cols + 1,))
+            ri = np.ctypeslib.as_array(row_idx, shape=(max(1, int(cp[n_cols])),))
+            cm = np.ctypeslib.as_array(cmember, shape=(n_cols,))
+            perm = order(n_rows, n_cols, cp, ri, cm)
+            out = np.ctypeslib.as_array(perm_out, shape=(n_cols,))
+            out[:] = perm
+            return 1
+        except Exception:  # noqa: BLE001 -- a Python exception must not unwind through the C caller
+            import traceback
+            traceback.print_exc()
+            return 0
+    return callback
 
 
-CCOLAMD_CALLBACK = CCOLAMD_FN(_ccolamd_callback)
+CCOLAMD_CALLBACK = CCOLAMD_FN(_callback_of(lambda *a: ccolamd_csc(*a)))
 
 
 class OracleISAM2:
     """ISAM2 (gtsam/nonlinear/ISAM2.h) restated on the CPU; Gauss-Newton optimisation params, Cholesky, COLAMD"""
 
-    def __init__(self, relinearizeThreshold=0.1, relinearizeSkip=10, enableRelinearization=True, wildfireThreshold=0.001):
+    def __init__(self, relinearizeThreshold=0.1, relinearizeSkip=10, enableRelinearization=True, wildfireThreshold=0.001, ccolamd=None):
+        """ccolamd: (n_rows, n_cols, col_ptr, row_idx, cmember) -> column permutation, as ISAM2(ccolamd=...) takes it; None: the
+        reference's CCOLAMD (oracle/_ref)"""
         self.L = lib()
         L = self.L
         L.orc_isam2_create.restype = ct.c_void_p
@@ -464,8 +469,9 @@ class OracleISAM2:
         L.orc_isam2_marginal_factor.argtypes = [ct.c_void_p, ct.c_int, _U, _I, _D]
         L.orc_isam2_fixed_variables.argtypes = [ct.c_void_p, _U]
         L.orc_isam2_graph_hessian.argtypes = [ct.c_void_p, _D]
+        self._cb = CCOLAMD_CALLBACK if ccolamd is None else CCOLAMD_FN(_callback_of(ccolamd))  # (kept alive: the oracle calls it in every update)
         self.h = ct.c_void_p(L.orc_isam2_create(relinearizeThreshold, relinearizeSkip, int(enableRelinearization), wildfireThreshold,
-                                                CCOLAMD_CALLBACK))
+                                                self._cb))
 
     def __del__(self):
         try:
