@@ -128,6 +128,11 @@ class lmgpu_smart_stats(ct.Structure):
                 ("linearize_ms", ct.c_double)]
 
 
+class lmgpu_marginals_stats(ct.Structure):
+    _fields_ = [("launches", ct.c_int64), ("chunks", ct.c_int64), ("factorizations", ct.c_int64), ("vars_lds", ct.c_int64),
+                ("vars_scratch", ct.c_int64), ("scratch_bytes", ct.c_int64), ("longest_path", ct.c_int32), ("lds_capacity", ct.c_int32)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -208,6 +213,12 @@ SYMBOLS = {
     "lmgpu_comm_init": (ct.c_int, [_H, ct.c_char_p]),
     "lmgpu_marginal_covariance": (ct.c_int, [_H, ct.c_int32, _D]),
     "lmgpu_joint_marginal_covariance": (ct.c_int, [_H, ct.c_int32, _I, _D]),
+    "lmgpu_marginals_factor": (ct.c_int, [_H]),
+    "lmgpu_marginal_covariances": (ct.c_int, [_H, ct.c_int32, _I, _D]),
+    "lmgpu_marginals_path": (ct.c_int, [_H, ct.c_int32, _I, ct.c_int32]),
+    "lmgpu_marginals_front_offsets": (ct.c_int, [_H, ct.c_int32, _I, _I, ct.c_int32]),
+    "lmgpu_set_marginals_params": (ct.c_int, [_H, ct.c_int64, ct.c_int32]),
+    "lmgpu_get_marginals_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_marginals_stats)]),
     "lmgpu_selftest_chain_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
     "lmgpu_selftest_dense_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_uint, ct.c_int, _I]),
     "lmgpu_selftest_dogleg_step": (ct.c_int, [ct.c_int, _D, _D]),

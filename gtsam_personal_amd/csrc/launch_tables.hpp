@@ -27,6 +27,7 @@ struct LaunchTables {
   std::vector<LevelTask> level_tasks;
   int max_med = 0;  // most medium fronts on one level (sizes inv16_med)
   int max_nf = 1;   // widest frontal part among the HBM fronts (sizes the back-substitution scratch)
+  std::vector<int32_t> marg_parent;  // per front: its parent (marginal path walks; poff and spos stay on the handle)
 };
 
 // the entries of ONE HBM front's gather lists while its children are walked; sorted and cut into blocks by build_gather_lists
@@ -677,6 +678,38 @@ void build_fused_levels(lmgpu_handle* h, LaunchTables& T) {
   }
   if (tasks.empty()) h->fuse_levels = false;
   else h->n_level_sync = (int)T.med_fronts.size();
+}
+
+// Marginal path walks (kernels_marginals.hpp).  Reads the plan and the sx ranges of h_fronts; fills marg_poff (poff[root] = 0, poff[child] =
+// poff[parent] + nf[parent]: fronts are in post-order, so a parent is placed before its children when the list is walked backwards),
+// marg_depth, marg_vcol (first scalar of every slot inside the front it is frontal in), marg_spos (parallel to T.sxoff: the separator
+// scalar's path position = poff of the ancestor it is frontal in + its column there) and T.marg_parent.
+void build_marginal_tables(lmgpu_handle* h, LaunchTables& T) {
+  const Plan& P = h->plan;
+  const int NF = (int)P.fronts.size();
+  h->marg_poff.assign(NF, 0);
+  h->marg_depth.assign(NF, 0);
+  h->marg_vcol.assign(P.n_vars, 0);
+  h->marg_spos.assign(T.sxoff.size(), -1);
+  T.marg_parent.assign(NF, -1);
+  for (int fi = NF - 1; fi >= 0; fi--) {
+    const Front& fr = P.fronts[fi];
+    T.marg_parent[fi] = fr.parent;
+    if (fr.parent >= 0) {
+      h->marg_poff[fi] = h->marg_poff[fr.parent] + P.fronts[fr.parent].nf;
+      h->marg_depth[fi] = h->marg_depth[fr.parent] + 1;
+    }
+    for (int k = 0; k < fr.n_frontal_vars; k++) h->marg_vcol[fr.vars[k]] = fr.col_off[k];
+  }
+  for (int fi = 0; fi < NF; fi++) {
+    if (!h->front_active[fi]) continue;
+    const Front& fr = P.fronts[fi];
+    int32_t* sp = h->marg_spos.data() + h->h_fronts[fi].sx_begin;
+    for (size_t k = fr.n_frontal_vars; k < fr.vars.size(); k++) {
+      const int32_t v = fr.vars[k];
+      for (int d = 0; d < P.dims[v]; d++) *sp++ = h->marg_poff[P.front_of_var[v]] + h->marg_vcol[v] + d;
+    }
+  }
 }
 
 #ifdef LMGPU_TEST_HOOKS

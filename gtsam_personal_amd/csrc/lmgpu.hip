@@ -41,6 +41,7 @@
 #include "kernels_pcg.hpp"
 #include "kernels_gnc.hpp"
 #include "kernels_ncg.hpp"
+#include "kernels_marginals.hpp"
 #include "plan.hpp"
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
@@ -221,6 +222,8 @@ struct NcgState;  // ncg.hpp
 static void ncg_release(lmgpu_handle* h);
 struct TriState;  // triangulation.hpp
 static void tri_release(lmgpu_handle* h);
+struct MargState;  // marginals.hpp: parameters, statistics and device buffers of the marginal path walks
+static void marg_release(lmgpu_handle* h);
 struct SmartState;  // smart.hpp: the smart projection factors of a handle (hidden points, cache, internal factor bucket)
 static void smart_release(lmgpu_handle* h);
 static int smart_prepare(lmgpu_handle* h);
@@ -388,6 +391,17 @@ struct lmgpu_handle {
   int inv16_owner = -1;  // HBM front whose panels' 16x16 inverses inv16 currently holds
   double* gex = nullptr;         // ntot doubles: extra gradient vector for solves with a prescribed right-hand side (marginals)
   double* gex_active = nullptr;  // == gex while such a solve is being assembled, else nullptr
+
+  // ---- marginal path walks (kernels_marginals.hpp, marginals.hpp).  The tables are built on every handle with fronts (launch_tables.hpp:
+  //      build_marginal_tables); a structure-only handle answers lmgpu_marginals_path from them.
+  std::vector<int32_t> marg_poff;   // per front: path offset (poff[root] = 0, poff[child] = poff[parent] + nf[parent])
+  std::vector<int32_t> marg_depth;  // per front: cliques above it on its path
+  std::vector<int32_t> marg_vcol;   // per slot: its first scalar inside the front it is frontal in
+  std::vector<int32_t> marg_spos;   // parallel to sxoff: path position of each separator scalar
+  int32_t *d_marg_parent = nullptr, *d_marg_poff = nullptr, *d_marg_spos = nullptr;
+  bool marg_valid = false;          // the pool's [R S d] are the undamped factorization at the current values (lmgpu_marginals_factor)
+  bool marg_factoring = false;      // lmgpu_marginals_factor is queueing its solve: always the direct solver
+  MargState* marg = nullptr;
 
   // ---- LM
   lmgpu_lm_state lm{};
@@ -633,6 +647,7 @@ int compute_error(lmgpu_handle* h, int which, double* out) {
 }
 
 int do_linearize(lmgpu_handle* h) {
+  h->marg_valid = false;
   launch_factors<true>(h, h->cur);
   HIPCHECK(hipGetLastError());
   h->linearized = true;
@@ -1513,7 +1528,7 @@ int pcg_solve_finish(lmgpu_handle* h) {
 }
 
 // the solver a solve of this handle takes (the marginal covariances always eliminate: they need the direct path's unit-gradient solves)
-static bool use_pcg(const lmgpu_handle* h) { return h->solver == LMGPU_SOLVER_PCG && !h->gex_active; }
+static bool use_pcg(const lmgpu_handle* h) { return h->solver == LMGPU_SOLVER_PCG && !h->gex_active && !h->marg_factoring; }
 
 // everything of one damped solve that is queued on the stream
 int solve_sequence(lmgpu_handle* h, bool phase_events, double lambda_v, const double* lambda_p) {
@@ -1549,6 +1564,7 @@ static bool graph_eligible(const lmgpu_handle* h) {
 }
 
 int do_solve_enqueue(lmgpu_handle* h, double lambda) {
+  h->marg_valid = false;  // the fronts are about to be overwritten
   if (use_pcg(h)) return pcg_solve_enqueue(h, lambda);
   hipStream_t s = h->stream;
   int rc = ensure_dense_schedules(h);  // (both allocate and upload at the first solve: before anything is queued or captured)
@@ -1611,6 +1627,7 @@ int do_solve(lmgpu_handle* h, double lambda) {
 }
 
 int do_retract(lmgpu_handle* h, int from, int to) {
+  h->marg_valid = false;
   for (int t = 0; t < kNumVarTypes; t++) {
     // the hidden points of smart factors are the first POINT3 variables: never retracted (their value is the cache's, smart.hpp)
     const int skip = t == LMGPU_POINT3 ? h->n_hidden : 0;
@@ -2154,6 +2171,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
     for (hipEvent_t e : h->kt.pool) (void)hipEventDestroy(e);
     fr(h->bs_inv); fr(h->bs_x); fr(h->bs_flags); fr(h->inv16); fr(h->d_pflags); fr(h->d_bs_parent); fr(h->d_bs_pos); fr(h->d_bs_done); fr(h->d_fill_upper); fr(h->d_level_tasks); fr(h->d_level_sync); fr(h->d_bsd_table); fr(h->d_bsd_run_table); fr(h->d_fill_elim); fr(h->d_fill_backsub); fr(h->d_zero_ranges); fr(h->d_bsd_x); fr(h->d_bsd_ticket); fr(h->d_leafpack); fr(h->d_gzero);
     fr(h->d_chain_tasks);
+    fr(h->d_marg_parent); fr(h->d_marg_poff); fr(h->d_marg_spos);
     fr(h->d_gpblk); fr(h->d_gpent); fr(h->d_gvblk); fr(h->d_gvent); fr(h->d_gcorner); fr(h->d_row_begin); fr(h->d_rowptr); fr(h->d_rowsrc);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
@@ -2164,6 +2182,7 @@ int lmgpu_destroy(lmgpu_handle* h) {
     for (hipEvent_t e : h->chunk_ev) (void)hipEventDestroy(e);
   }
   tri_release(h);  // also on a structure-only handle: its index is host memory
+  marg_release(h);
   smart_release(h);
   delete h;
   return LMGPU_OK;
@@ -2361,6 +2380,7 @@ static int upload_launch_tables(lmgpu_handle* h, const LaunchTables& T) {
   if (!T.level_tasks.empty()) UPLOAD(d_level_tasks, T.level_tasks);
   UPLOAD(d_rowptr, T.rowptr); UPLOAD(d_rowsrc, T.rowsrc); UPLOAD(d_gpblk, T.gpblk); UPLOAD(d_gzero, T.gzero);
   UPLOAD(d_gpent, T.gpent); UPLOAD(d_gvblk, T.gvblk); UPLOAD(d_gvent, T.gvent);
+  UPLOAD(d_marg_parent, T.marg_parent); UPLOAD(d_marg_poff, h->marg_poff); UPLOAD(d_marg_spos, h->marg_spos);
 #undef UPLOAD
   if ((rc = finalize_vectors(h))) return rc;
   // ---- scratch
@@ -2417,6 +2437,7 @@ static int finalize_structure_impl(lmgpu_handle* h) {
   build_leaf_packs(h, T);
   build_backsub_tables(h, T);
   build_fused_levels(h, T);
+  build_marginal_tables(h, T);
 #ifdef LMGPU_TEST_HOOKS
   digest_tables(h, T);
 #endif
@@ -2462,6 +2483,7 @@ int lmgpu_set_values(lmgpu_handle* h, const double* packed) {
     HIPCHECK(hipMemcpy(h->vals[h->cur][t], buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   h->have_values = true;
+  h->marg_valid = false;
   return LMGPU_OK;
 }
 
@@ -2512,6 +2534,7 @@ int lmgpu_restore_values(lmgpu_handle* h) {
   }
   int rc = need_device(h);
   if (rc) return rc;
+  h->marg_valid = false;
   for (int t = 0; t < kNumVarTypes; t++) {
     const size_t bytes = std::max<size_t>(1, (size_t)h->plan.type_count[t] * kVarStore[t]) * sizeof(double);
     HIPCHECK(hipMemcpyAsync(h->vals[h->cur][t], h->saved[t], bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -2996,7 +3019,7 @@ int gnc_enqueue_weights(lmgpu_handle* h, int loss, double mu) {
   hipLaunchKernelGGL(gnc_finish_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)h->gnc_part, g, 0, h->gnc_scal);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipMemcpyAsync(h->h_gnc_scal, h->gnc_scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  h->linearized = h->have_jacobians = false;  // the stored [A b] carry the previous weights: no solve and no parity tap reads them
+  h->linearized = h->have_jacobians = h->marg_valid = false;  // the stored [A b] carry the previous weights: no solve and no parity tap reads them
   return LMGPU_OK;
 }
 
@@ -3072,7 +3095,7 @@ int lmgpu_gnc_enable(lmgpu_handle* h, int32_t on, int32_t graph_size) {
   if (!on) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     drop();
-    if (h->gnc_on) h->linearized = h->have_jacobians = false;
+    if (h->gnc_on) h->linearized = h->have_jacobians = h->marg_valid = false;
     h->gnc_on = false;
     return LMGPU_OK;
   }
@@ -3106,7 +3129,7 @@ int lmgpu_gnc_enable(lmgpu_handle* h, int32_t on, int32_t graph_size) {
   if ((rc = gnc_reset_weights(h))) return rc;
   if ((rc = gnc_default_thresholds(h, 0.99))) return rc;  // GncOptimizer.h:104-106
   h->gnc_on = true;
-  h->linearized = h->have_jacobians = false;
+  h->linearized = h->have_jacobians = h->marg_valid = false;
   return LMGPU_OK;
 }
 
@@ -3163,7 +3186,7 @@ int lmgpu_gnc_set_known(lmgpu_handle* h, int32_t n_in, const uint64_t* inliers, 
   h->gnc_n_in = n_in;
   h->gnc_n_out = n_out;
   HIPCHECK(hipMemcpyAsync(h->gnc_fixed, h->gnc_fixed_h.data(), (size_t)std::max(1, h->nfac), hipMemcpyHostToDevice, h->stream));
-  h->linearized = h->have_jacobians = false;
+  h->linearized = h->have_jacobians = h->marg_valid = false;
   return gnc_reset_weights(h);
 }
 
@@ -3175,7 +3198,7 @@ int lmgpu_gnc_set_weights(lmgpu_handle* h, int32_t n, const double* w) {
     h->err = "lmgpu_gnc_set_weights: the number of specified weights does not match the size of the factor graph";
     return LMGPU_INVALID;
   }
-  h->linearized = h->have_jacobians = false;
+  h->linearized = h->have_jacobians = h->marg_valid = false;
   std::vector<double> loc;
   gnc_to_local(h, w, loc);
   return gnc_upload(h, h->gnc_w, loc);
@@ -3865,6 +3888,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 #include "init_pose3.hpp"
 #include "ncg.hpp"
 #include "triangulation.hpp"
+#include "marginals.hpp"
 #include "smart.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py

@@ -199,7 +199,7 @@ int ncg_run(lmgpu_handle* h, const lmgpu_ncg_params* p, bool singleIteration, in
   if ((rc = ncg_enqueue_set_direction(h, s->g[s->cur_g]))) return rc;
   if ((rc = ncg_line_search(h, 1))) return rc;
   h->cur ^= 1;
-  h->linearized = false;
+  h->linearized = h->marg_valid = false;
   double prevError = currentError;
   currentError = s->h_ctl->error;
   do {
@@ -213,7 +213,7 @@ int ncg_run(lmgpu_handle* h, const lmgpu_ncg_params* p, bool singleIteration, in
     }
     if ((rc = ncg_line_search(h, 1))) return rc;  // alpha = lineSearch(...); currentValues = advance(prevValues, alpha, direction) (:260-266)
     h->cur ^= 1;
-    h->linearized = false;
+    h->linearized = h->marg_valid = false;
     prevError = currentError;
     currentError = s->h_ctl->error;
     *err_out = currentError;

@@ -335,6 +335,7 @@ int lmgpu_triangulate_landmarks(lmgpu_handle* h, const lmgpu_triangulation_param
     a.cams[TRI_POSE_K] = h->vals[h->cur][LMGPU_POSE3];
     a.points = s->d_points; a.status = s->d_status; a.iters = s->d_iters;
     a.values = write_values ? h->vals[h->cur][LMGPU_POINT3] : nullptr;
+    if (write_values) h->marg_valid = false;
     HIPCHECK(hipEventRecord(s->ev[0], h->stream));
     tri_launch(s->bins, params->enableEPI != 0, a, tri_params_dev(params), h->stream);
     HIPCHECK(hipGetLastError());

@@ -741,10 +741,16 @@ class Marginals:
     The elimination ordering is a boundary input as for the optimizers (the reference's default here is COLAMD; the result
     does not depend on it).  Raises IndeterminantLinearSystemException-like LmgpuError where the reference throws."""
 
-    def __init__(self, graph: NonlinearFactorGraph, solution: Values, ordering, device: int = 0):
+    def __init__(self, graph: NonlinearFactorGraph, solution: Values, ordering, device: int = 0, path_solves: bool = False):
+        """path_solves: marginalCovariance / marginalInformation answer from ONE cached factorization, each variable along its path to the
+        root of the Bayes tree (lmgpu_marginal_covariances), instead of one elimination + back-substitution per column.
+        marginalCovariances / marginalInformations always take that route."""
         self._opt = LevenbergMarquardtOptimizer(graph, solution, ordering, LevenbergMarquardtParams(), device=device)
+        self._path_solves = bool(path_solves)
 
     def marginalCovariance(self, key) -> np.ndarray:
+        if self._path_solves:
+            return self.marginalCovariances([key])[int(key)]
         o = self._opt
         slot = o._slot[int(key)]
         d = int(o._xoff[slot + 1] - o._xoff[slot])
@@ -754,6 +760,26 @@ class Marginals:
 
     def marginalInformation(self, key) -> np.ndarray:
         return np.linalg.inv(self.marginalCovariance(key))
+
+    def marginalCovariances(self, keys=None) -> dict:
+        """{key: marginalCovariance(key)} for `keys` (all variables when None): one factorization, kept until the values move, and one
+        walk per variable along its path to the root."""
+        o = self._opt
+        keys = sorted(o._slot) if keys is None else [int(k) for k in keys]
+        slots = np.array([o._slot[k] for k in keys], dtype=np.int32)
+        dims = [int(o._xoff[s + 1] - o._xoff[s]) for s in slots]
+        off = np.concatenate([[0], np.cumsum([d * d for d in dims])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        o._check(o.lib.lmgpu_marginal_covariances(o._h, len(slots), _ip(slots), _dp(out)))
+        return {k: out[off[i]:off[i + 1]].reshape(dims[i], dims[i]).copy() for i, k in enumerate(keys)}
+
+    def marginalInformations(self, keys=None) -> dict:
+        return {k: np.linalg.inv(c) for k, c in self.marginalCovariances(keys).items()}
+
+    def marginalsStats(self) -> dict:
+        st = _lib.lmgpu_marginals_stats()
+        self._opt._check(self._opt.lib.lmgpu_get_marginals_stats(self._opt._h, st))
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
 
     def jointMarginalCovariance(self, keys) -> "JointMarginal":
         """Marginals::jointMarginalCovariance (Marginals.cpp:130-137): blocks ordered by Key like JointMarginal::fullMatrix"""

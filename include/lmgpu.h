@@ -497,6 +497,40 @@ int lmgpu_marginal_covariance(lmgpu_handle* h, int32_t slot, double* cov /* dim 
  * (the reference's JointMarginal::fullMatrix orders the blocks by Key; the caller chooses here).  Cost: D unit-gradient solves. */
 int lmgpu_joint_marginal_covariance(lmgpu_handle* h, int32_t nslots, const int32_t* slots, double* cov /* D x D */);
 
+/* ---- marginal covariances of MANY variables from one factorization.  Marginals' constructor factors once and every
+ *      marginalCovariance(key) is answered from the Bayes tree (Marginals.cpp:28-43, :124-127).  lmgpu_marginals_factor linearizes at the
+ *      current values and eliminates undamped (lambda = 0); the fronts' [R S d] stay on the device.  A query then walks, per variable, the
+ *      path from the front it is frontal in to its root -- R^T y = e up the path, R x = y down again -- with one workgroup per variable,
+ *      all of its columns together, one launch and one download per chunk of requests.  The factorization is marked stale by everything
+ *      that overwrites the fronts or moves the values (lmgpu_set_values, lmgpu_retract, lmgpu_restore_values, lmgpu_linearize, lmgpu_solve,
+ *      every *_iterate and *_optimize, the two calls above) and rebuilt by the next query.  After lmgpu_marginals_factor the handle is in
+ *      the state lmgpu_linearize + lmgpu_solve(lambda = 0) leave.  Refused with LMGPU_INVALID like lmgpu_joint_marginal_covariance: smart
+ *      factors, a handle finalized under PCG, world_size > 1.  The two calls above keep their own route (one solve per column). ---- */
+int lmgpu_marginals_factor(lmgpu_handle* h);
+/* the dim x dim blocks (row-major, symmetric) of the n variables in `slots`, back to back in the order of `slots`.  Duplicates are
+ * allowed; n == 0 is LMGPU_OK; a slot out of range is LMGPU_INVALID and nothing is written.  A variable's block is bitwise the same
+ * whatever else the request holds.  LMGPU_INDETERMINATE when a block comes out non-finite (lmgpu_last_failed_slot: the first such
+ * variable) or the factorization fails. */
+int lmgpu_marginal_covariances(lmgpu_handle* h, int32_t n, const int32_t* slots, double* cov_packed);
+/* the fronts of the variable's path, from the front it is frontal in to its root, into fronts_out[0 .. cap); returns the path length
+ * (-1: refused).  Structure only: answers on a device = -1 handle. */
+int lmgpu_marginals_path(const lmgpu_handle* h, int32_t slot, int32_t* fronts_out, int32_t cap);
+/* the path tables of one front: *poff = position of its first frontal scalar in a path's work vector (0 for a root, the parent's
+ * poff + the parent's frontal dimension otherwise), spos[0 .. cap) = the positions of its separator scalars, each inside the frontal
+ * range of an ancestor.  Returns the number of separator scalars (-1: refused).  Structure only. */
+int lmgpu_marginals_front_offsets(const lmgpu_handle* h, int32_t front, int32_t* poff, int32_t* spos, int32_t cap);
+/* scratch_bytes: byte budget of the buffer that holds the work vectors too long for LDS; a request is cut into chunks (one launch each)
+ * so that a chunk's vectors fit it; a single vector that does not is refused (default 64 MiB).  lds_doubles: the longest work vector
+ * (doubles) kept in LDS (default 6144).  0 keeps a value. */
+int lmgpu_set_marginals_params(lmgpu_handle* h, int64_t scratch_bytes, int32_t lds_doubles);
+/* counted over the handle's life: launches and chunks of marginal_path_kernel, factorizations done for it, variables whose work vector
+ * lay in LDS / in scratch, cliques on the longest path walked; lds_capacity (doubles) and scratch_bytes are the parameters in force. */
+typedef struct lmgpu_marginals_stats {
+  int64_t launches, chunks, factorizations, vars_lds, vars_scratch, scratch_bytes;
+  int32_t longest_path, lds_capacity;
+} lmgpu_marginals_stats;
+int lmgpu_get_marginals_stats(lmgpu_handle* h, lmgpu_marginals_stats* out);
+
 /* Host-only self-test (no GPU work): the ticket order the library gives the chained factorisation launch of a dense front
  * with n columns (nf frontal) for the steps i0 .. i0 + nsteps - 1 (tile rows beyond far_pct percent scheduled late; far_pct + 1000: the
  * default schedule, whose update tiles apply two steps per pass) is a permutation of all logical workgroups in which every

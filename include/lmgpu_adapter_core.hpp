@@ -282,6 +282,25 @@ class Problem {
   void ncgIterate(const lmgpu_ncg_params& p, lmgpu_lm_state* inout) { check(lmgpu_ncg_iterate(h_, &p, inout)); }
   void ncgOptimize(const lmgpu_ncg_params& p, lmgpu_lm_state* inout) { check(lmgpu_ncg_optimize(h_, &p, inout)); }
 
+  /// Marginals for many variables from ONE factorization (lmgpu.h, "marginal covariances of MANY variables"): factor at the current
+  /// values; the dim x dim row-major blocks of `slots`, back to back in their order (a stale factorization is rebuilt first)
+  void marginalsFactor() { check(lmgpu_marginals_factor(h_)); }
+  std::vector<double> marginalCovariances(const std::vector<int32_t>& slots) {
+    size_t total = 0;
+    for (int32_t s : slots) {
+      const size_t d = (size_t)varDim(typeOfSlot(s));
+      total += d * d;
+    }
+    std::vector<double> out(total);
+    check(lmgpu_marginal_covariances(h_, (int32_t)slots.size(), slots.data(), out.data()));
+    return out;
+  }
+  lmgpu_marginals_stats marginalsStats() {
+    lmgpu_marginals_stats st{};
+    check(lmgpu_get_marginals_stats(h_, &st));
+    return st;
+  }
+
   /// status -> exception, the mapping the reference-side adapter relies on
   void check(int rc) const {
     if (rc == LMGPU_OK) return;

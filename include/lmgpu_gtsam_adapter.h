@@ -650,6 +650,54 @@ class GpuDoglegOptimizer : public NonlinearOptimizer {
   bool discardLinear_ = false;
 };
 
+/// Marginals(graph, solution, ordering) with the covariances of MANY variables from one factorization (gtsam/nonlinear/Marginals.h:
+/// the constructor linearizes at the solution and eliminates, Marginals.cpp:28-43; marginalCovariance :124-127, marginalInformation
+/// :109-121).  lmgpu_marginals_factor keeps the Bayes tree on the device; each query walks the variable's path to the root
+/// (lmgpu_marginal_covariances).  Cholesky only, like the reference's default; an indeterminate system throws from the constructor as
+/// the reference's does.  Joint marginals are not bound here (lmgpu_joint_marginal_covariance keeps its own route).
+class GpuMarginals {
+ public:
+  GpuMarginals(const NonlinearFactorGraph& graph, const Values& solution, const Ordering& ordering, int device = 0)
+      : dev_(new lmgpu_detail::Device(graph, solution, ordering, device)) {
+    try {
+      dev_->problem().marginalsFactor();
+    } catch (const lmgpu_adapter::Indeterminate& e) {
+      throw IndeterminantLinearSystemException(e.key);
+    }
+  }
+
+  /// Marginals::marginalCovariance(variable)
+  Matrix marginalCovariance(Key variable) const { return marginalCovariances(KeyVector{variable}).front(); }
+  /// Marginals::marginalInformation(variable)
+  Matrix marginalInformation(Key variable) const { return marginalCovariance(variable).inverse(); }
+  /// the covariances of `variables`, in their order: one launch per chunk of requests, one workgroup per variable
+  std::vector<Matrix> marginalCovariances(const KeyVector& variables) const {
+    lmgpu_adapter::Problem& p = dev_->problem();
+    std::vector<int32_t> slots;
+    slots.reserve(variables.size());
+    for (Key k : variables) slots.push_back(p.slotOf(k));
+    std::vector<double> packed;
+    try {
+      packed = p.marginalCovariances(slots);
+    } catch (const lmgpu_adapter::Indeterminate& e) {
+      throw IndeterminantLinearSystemException(e.key);
+    }
+    std::vector<Matrix> out;
+    out.reserve(slots.size());
+    size_t o = 0;
+    for (int32_t s : slots) {
+      const int d = lmgpu_adapter::varDim(p.typeOfSlot(s));
+      out.push_back(Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(packed.data() + o, d, d));
+      o += (size_t)d * d;
+    }
+    return out;
+  }
+  lmgpu_marginals_stats stats() const { return dev_->problem().marginalsStats(); }
+
+ private:
+  std::unique_ptr<lmgpu_detail::Device> dev_;
+};
+
 /// ISAM2 on the device (lmgpu_isam2_*): the same update() / calculateEstimate() calls as gtsam::ISAM2 (gtsam/nonlinear/ISAM2.h:146-260)
 /// for the parameter subset the C ABI binds (Gauss-Newton or Dogleg optimisation params, relinearization threshold as a double or per Symbol
 /// character, partial relinearization check, Cholesky).  Not a
