@@ -130,7 +130,9 @@ class lmgpu_smart_stats(ct.Structure):
 
 class lmgpu_marginals_stats(ct.Structure):
     _fields_ = [("launches", ct.c_int64), ("chunks", ct.c_int64), ("factorizations", ct.c_int64), ("vars_lds", ct.c_int64),
-                ("vars_scratch", ct.c_int64), ("scratch_bytes", ct.c_int64), ("longest_path", ct.c_int32), ("lds_capacity", ct.c_int32)]
+                ("vars_scratch", ct.c_int64), ("scratch_bytes", ct.c_int64), ("longest_path", ct.c_int32), ("lds_capacity", ct.c_int32),
+                ("cross_launches", ct.c_int64), ("cross_chunks", ct.c_int64), ("cross_walks", ct.c_int64), ("cross_targets", ct.c_int64),
+                ("cross_lds", ct.c_int64), ("cross_scratch", ct.c_int64), ("longest_union", ct.c_int32), ("cross_cap", ct.c_int32)]
 
 
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
@@ -219,6 +221,10 @@ SYMBOLS = {
     "lmgpu_marginals_front_offsets": (ct.c_int, [_H, ct.c_int32, _I, _I, ct.c_int32]),
     "lmgpu_set_marginals_params": (ct.c_int, [_H, ct.c_int64, ct.c_int32]),
     "lmgpu_get_marginals_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_marginals_stats)]),
+    "lmgpu_marginal_cross_covariances": (ct.c_int, [_H, ct.c_int32, _I, _I, _D]),
+    "lmgpu_joint_marginal_covariances": (ct.c_int, [_H, ct.c_int32, _I, _I, _D]),
+    "lmgpu_marginals_junction": (ct.c_int, [_H, ct.c_int32, ct.c_int32]),
+    "lmgpu_set_marginals_cross_cap": (ct.c_int, [_H, ct.c_int32]),
     "lmgpu_selftest_chain_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
     "lmgpu_selftest_dense_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_uint, ct.c_int, _I]),
     "lmgpu_selftest_dogleg_step": (ct.c_int, [ct.c_int, _D, _D]),

@@ -743,8 +743,9 @@ class Marginals:
 
     def __init__(self, graph: NonlinearFactorGraph, solution: Values, ordering, device: int = 0, path_solves: bool = False):
         """path_solves: marginalCovariance / marginalInformation answer from ONE cached factorization, each variable along its path to the
-        root of the Bayes tree (lmgpu_marginal_covariances), instead of one elimination + back-substitution per column.
-        marginalCovariances / marginalInformations always take that route."""
+        root of the Bayes tree (lmgpu_marginal_covariances), instead of one elimination + back-substitution per column, and
+        jointMarginalCovariance / jointMarginalInformation from the same factorization (lmgpu_joint_marginal_covariances).
+        marginalCovariances / marginalInformations, crossCovariances and jointMarginalCovariances always take that route."""
         self._opt = LevenbergMarquardtOptimizer(graph, solution, ordering, LevenbergMarquardtParams(), device=device)
         self._path_solves = bool(path_solves)
 
@@ -781,8 +782,37 @@ class Marginals:
         self._opt._check(self._opt.lib.lmgpu_get_marginals_stats(self._opt._h, st))
         return {name: int(getattr(st, name)) for name, _ in st._fields_}
 
+    def crossCovariances(self, pairs) -> dict:
+        """{(ki, kj): Sigma[ki, kj]} (dim_i x dim_j) for the (ki, kj) of `pairs`: kj is the source whose path is walked, pairs with one
+        kj share the walk, each ki costs the descent of its branch below the junction of the two paths."""
+        o = self._opt
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        si = np.array([o._slot[a] for a, _ in pairs], dtype=np.int32)
+        sj = np.array([o._slot[b] for _, b in pairs], dtype=np.int32)
+        dim = lambda s: int(o._xoff[s + 1] - o._xoff[s])
+        shape = [(dim(a), dim(b)) for a, b in zip(si, sj)]
+        off = np.concatenate([[0], np.cumsum([r * c for r, c in shape])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        o._check(o.lib.lmgpu_marginal_cross_covariances(o._h, len(pairs), _ip(si), _ip(sj), _dp(out)))
+        return {pr: out[off[q]:off[q + 1]].reshape(shape[q]).copy() for q, pr in enumerate(pairs)}
+
+    def jointMarginalCovariances(self, list_of_key_lists) -> list:
+        """[jointMarginalCovariance(keys) for keys in list_of_key_lists] in one request: every block from the one factorization, blocks
+        ordered by Key like JointMarginal::fullMatrix, each matrix exactly symmetric (DESIGN section 18)."""
+        o = self._opt
+        sets = [sorted(int(k) for k in keys) for keys in list_of_key_lists]
+        begin = np.concatenate([[0], np.cumsum([len(ks) for ks in sets])]).astype(np.int32)
+        slots = np.array([o._slot[k] for ks in sets for k in ks], dtype=np.int32)
+        dims = [[int(o._xoff[o._slot[k] + 1] - o._xoff[o._slot[k]]) for k in ks] for ks in sets]
+        off = np.concatenate([[0], np.cumsum([sum(d) ** 2 for d in dims])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        o._check(o.lib.lmgpu_joint_marginal_covariances(o._h, len(sets), _ip(begin), _ip(slots), _dp(out)))
+        return [JointMarginal(ks, dims[q], out[off[q]:off[q + 1]].reshape(sum(dims[q]), sum(dims[q])).copy()) for q, ks in enumerate(sets)]
+
     def jointMarginalCovariance(self, keys) -> "JointMarginal":
         """Marginals::jointMarginalCovariance (Marginals.cpp:130-137): blocks ordered by Key like JointMarginal::fullMatrix"""
+        if self._path_solves:
+            return self.jointMarginalCovariances([keys])[0]
         o = self._opt
         keys = sorted(int(k) for k in keys)
         slots = np.array([o._slot[k] for k in keys], dtype=np.int32)

@@ -505,7 +505,8 @@ int lmgpu_joint_marginal_covariance(lmgpu_handle* h, int32_t nslots, const int32
  *      that overwrites the fronts or moves the values (lmgpu_set_values, lmgpu_retract, lmgpu_restore_values, lmgpu_linearize, lmgpu_solve,
  *      every *_iterate and *_optimize, the two calls above) and rebuilt by the next query.  After lmgpu_marginals_factor the handle is in
  *      the state lmgpu_linearize + lmgpu_solve(lambda = 0) leave.  Refused with LMGPU_INVALID like lmgpu_joint_marginal_covariance: smart
- *      factors, a handle finalized under PCG, world_size > 1.  The two calls above keep their own route (one solve per column). ---- */
+ *      factors, a handle finalized under PCG, world_size > 1.  The two calls above keep their own route (one solve per column); joint
+ *      marginals from this factorization: lmgpu_joint_marginal_covariances below. ---- */
 int lmgpu_marginals_factor(lmgpu_handle* h);
 /* the dim x dim blocks (row-major, symmetric) of the n variables in `slots`, back to back in the order of `slots`.  Duplicates are
  * allowed; n == 0 is LMGPU_OK; a slot out of range is LMGPU_INVALID and nothing is written.  A variable's block is bitwise the same
@@ -525,11 +526,42 @@ int lmgpu_marginals_front_offsets(const lmgpu_handle* h, int32_t front, int32_t*
 int lmgpu_set_marginals_params(lmgpu_handle* h, int64_t scratch_bytes, int32_t lds_doubles);
 /* counted over the handle's life: launches and chunks of marginal_path_kernel, factorizations done for it, variables whose work vector
  * lay in LDS / in scratch, cliques on the longest path walked; lds_capacity (doubles) and scratch_bytes are the parameters in force. */
+/* cross walks (below): launches and chunks of marginal_cross_kernel, cross_walks = workgroups = walks of a source's path,
+ * cross_targets = blocks written, workgroups whose work vector lay in LDS / in scratch, longest_union = cliques on the longest source
+ * path + branch walked by one workgroup, cross_cap = targets per workgroup in force. */
 typedef struct lmgpu_marginals_stats {
   int64_t launches, chunks, factorizations, vars_lds, vars_scratch, scratch_bytes;
   int32_t longest_path, lds_capacity;
+  int64_t cross_launches, cross_chunks, cross_walks, cross_targets, cross_lds, cross_scratch;
+  int32_t longest_union, cross_cap;
 } lmgpu_marginals_stats;
 int lmgpu_get_marginals_stats(lmgpu_handle* h, lmgpu_marginals_stats* out);
+
+/* ---- cross-covariances and joint marginals from the same factorization (Marginals::jointMarginalCovariance,
+ *      Marginals.cpp:130-137, answered from the Bayes tree).  Sigma[:, j] is x with R^T y = e_j, R x = y: y lives on j's path, and x at a
+ *      variable i needs only the fronts of i's path, which it shares with j's from their junction (the deepest front on both) to the root.
+ *      One workgroup walks the path of a SOURCE j up and down, then, per TARGET i, descends i's branch below the junction and writes the
+ *      dim_i x dim_j block.  One launch and one download per chunk.  Refusals, staleness and the LDS / scratch rules are those of
+ *      lmgpu_marginal_covariances; lmgpu_set_marginals_params applies.  A block's bits depend on the pair (i, j) and the factorization
+ *      alone; the block of (i, i) is bitwise lmgpu_marginal_covariances' block of i. ---- */
+/* block q = Sigma[slots_i[q], slots_j[q]], dim_i x dim_j row-major (the columns are those of j, the source), back to back in the order
+ * of the pairs.  Pairs with equal j share a walk wherever they stand in the list.  A pair across two trees of a forest: exact zeros.
+ * n == 0 is LMGPU_OK; a slot out of range is LMGPU_INVALID and nothing is written.  LMGPU_INDETERMINATE when a block comes out non-finite
+ * (lmgpu_last_failed_slot: the source of the first such workgroup) or the factorization fails. */
+int lmgpu_marginal_cross_covariances(lmgpu_handle* h, int32_t n, const int32_t* slots_i, const int32_t* slots_j, double* out_packed);
+/* n_sets joint marginals: set q holds slots[set_begin[q] .. set_begin[q + 1]) (distinct: a slot twice in one set is LMGPU_INVALID) and
+ * gets its D_q x D_q row-major matrix, blocks in the order of its slots as lmgpu_joint_marginal_covariance lays them out, the matrices
+ * back to back.  Exactly symmetric: an off-diagonal block is computed once, from the variable of the pair with the shorter path (fewer
+ * scalars; ties: the smaller slot) as the source, and mirrored; a diagonal block is the (i, i) block above. */
+int lmgpu_joint_marginal_covariances(lmgpu_handle* h, int32_t n_sets, const int32_t* set_begin /* n_sets + 1 */, const int32_t* slots,
+                                     double* cov_packed);
+/* the junction of two variables' paths: the deepest front on both (-1: different trees of a forest, or refused).  Structure only. */
+int lmgpu_marginals_junction(const lmgpu_handle* h, int32_t slot_i, int32_t slot_j);
+/* development switch: targets of one source that one workgroup serves after its walk of the source's path (a source with more is split
+ * over several workgroups, each repeating the walk).  0 restores the built-in rule: one target per workgroup until the request holds
+ * more than 1024 pairs, then pairs / 1024 rounded up, 16 at most (lmgpu_marginals_stats.cross_cap reports that maximum).  Results do
+ * not depend on it. */
+int lmgpu_set_marginals_cross_cap(lmgpu_handle* h, int32_t targets_per_workgroup);
 
 /* Host-only self-test (no GPU work): the ticket order the library gives the chained factorisation launch of a dense front
  * with n columns (nf frontal) for the steps i0 .. i0 + nsteps - 1 (tile rows beyond far_pct percent scheduled late; far_pct + 1000: the

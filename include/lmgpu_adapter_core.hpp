@@ -295,6 +295,25 @@ class Problem {
     check(lmgpu_marginal_covariances(h_, (int32_t)slots.size(), slots.data(), out.data()));
     return out;
   }
+  /// the same factorization, off-diagonal blocks too (lmgpu.h, "cross-covariances and joint marginals"): block q = Sigma[slots_i[q],
+  /// slots_j[q]], dim_i x dim_j row-major, back to back; slots_j[q] is the source whose path is walked
+  std::vector<double> marginalCrossCovariances(const std::vector<int32_t>& slots_i, const std::vector<int32_t>& slots_j) {
+    if (slots_i.size() != slots_j.size()) throw Error(LMGPU_INVALID, "marginalCrossCovariances: slots_i and slots_j differ in length");
+    size_t total = 0;
+    for (size_t q = 0; q < slots_i.size(); q++) total += (size_t)varDim(typeOfSlot(slots_i[q])) * (size_t)varDim(typeOfSlot(slots_j[q]));
+    std::vector<double> out(total);
+    check(lmgpu_marginal_cross_covariances(h_, (int32_t)slots_i.size(), slots_i.data(), slots_j.data(), out.data()));
+    return out;
+  }
+  /// the joint marginal covariance of `slots` (distinct): D x D row-major, blocks in their order, exactly symmetric
+  std::vector<double> jointMarginalCovariance(const std::vector<int32_t>& slots) {
+    size_t D = 0;
+    for (int32_t s : slots) D += (size_t)varDim(typeOfSlot(s));
+    std::vector<double> out(D * D);
+    const int32_t begin[2] = {0, (int32_t)slots.size()};
+    check(lmgpu_joint_marginal_covariances(h_, 1, begin, slots.data(), out.data()));
+    return out;
+  }
   lmgpu_marginals_stats marginalsStats() {
     lmgpu_marginals_stats st{};
     check(lmgpu_get_marginals_stats(h_, &st));

@@ -650,11 +650,40 @@ class GpuDoglegOptimizer : public NonlinearOptimizer {
   bool discardLinear_ = false;
 };
 
+/// What GpuMarginals::jointMarginalCovariance returns: the reference's JointMarginal (Marginals.h:141-191) has a protected constructor
+/// with `friend class Marginals`, so this is a small class of the same shape -- at(i, j), operator()(i, j), fullMatrix() -- with the
+/// blocks ordered by Key as there.
+class GpuJointMarginal {
+ public:
+  GpuJointMarginal(const KeyVector& keys, const std::vector<size_t>& dims, const Matrix& full) : keys_(keys), full_(full) {
+    size_t o = 0;
+    for (size_t q = 0; q < keys.size(); q++) {
+      range_[keys[q]] = std::make_pair(o, dims[q]);
+      o += dims[q];
+    }
+  }
+  /// JointMarginal::at(iVariable, jVariable): the block of the two variables
+  Matrix at(Key iVariable, Key jVariable) const {
+    const std::pair<size_t, size_t>&a = range_.at(iVariable), &b = range_.at(jVariable);
+    return full_.block(a.first, b.first, a.second, b.second);
+  }
+  Matrix operator()(Key iVariable, Key jVariable) const { return at(iVariable, jVariable); }
+  /// JointMarginal::fullMatrix(): all blocks, ordered by Key
+  const Matrix& fullMatrix() const { return full_; }
+  const KeyVector& keys() const { return keys_; }
+
+ private:
+  KeyVector keys_;
+  Matrix full_;
+  std::map<Key, std::pair<size_t, size_t>> range_;  // key -> (first scalar, dimension)
+};
+
 /// Marginals(graph, solution, ordering) with the covariances of MANY variables from one factorization (gtsam/nonlinear/Marginals.h:
 /// the constructor linearizes at the solution and eliminates, Marginals.cpp:28-43; marginalCovariance :124-127, marginalInformation
 /// :109-121).  lmgpu_marginals_factor keeps the Bayes tree on the device; each query walks the variable's path to the root
 /// (lmgpu_marginal_covariances).  Cholesky only, like the reference's default; an indeterminate system throws from the constructor as
-/// the reference's does.  Joint marginals are not bound here (lmgpu_joint_marginal_covariance keeps its own route).
+/// the reference's does.  Joint marginals and single cross-covariances come from the same factorization
+/// (lmgpu_joint_marginal_covariances, lmgpu_marginal_cross_covariances: the source's path, then each target's branch).
 class GpuMarginals {
  public:
   GpuMarginals(const NonlinearFactorGraph& graph, const Values& solution, const Ordering& ordering, int device = 0)
@@ -691,6 +720,47 @@ class GpuMarginals {
       o += (size_t)d * d;
     }
     return out;
+  }
+  /// Marginals::jointMarginalCovariance(variables) (Marginals.cpp:130-137): distinct variables, blocks ordered by Key
+  GpuJointMarginal jointMarginalCovariance(const KeyVector& variables) const {
+    lmgpu_adapter::Problem& p = dev_->problem();
+    KeyVector keys(variables);
+    std::sort(keys.begin(), keys.end());
+    std::vector<int32_t> slots;
+    std::vector<size_t> dims;
+    size_t D = 0;
+    for (Key k : keys) {
+      slots.push_back(p.slotOf(k));
+      dims.push_back((size_t)lmgpu_adapter::varDim(p.typeOfSlot(slots.back())));
+      D += dims.back();
+    }
+    std::vector<double> packed;
+    try {
+      packed = p.jointMarginalCovariance(slots);
+    } catch (const lmgpu_adapter::Indeterminate& e) {
+      throw IndeterminantLinearSystemException(e.key);
+    }
+    return GpuJointMarginal(keys, dims, Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(packed.data(), D, D));
+  }
+  /// Marginals::jointMarginalInformation(variables) (Marginals.cpp:145): here the inverse of the joint covariance
+  GpuJointMarginal jointMarginalInformation(const KeyVector& variables) const {
+    const GpuJointMarginal cov = jointMarginalCovariance(variables);
+    std::vector<size_t> dims;
+    for (Key k : cov.keys()) dims.push_back((size_t)cov.at(k, k).rows());
+    return GpuJointMarginal(cov.keys(), dims, cov.fullMatrix().inverse());
+  }
+  /// Sigma[i, j], dim_i x dim_j: the path of j is walked, then the branch of i below the junction of the two paths
+  Matrix crossCovariance(Key i, Key j) const {
+    lmgpu_adapter::Problem& p = dev_->problem();
+    const int32_t si = p.slotOf(i), sj = p.slotOf(j);
+    std::vector<double> packed;
+    try {
+      packed = p.marginalCrossCovariances(std::vector<int32_t>{si}, std::vector<int32_t>{sj});
+    } catch (const lmgpu_adapter::Indeterminate& e) {
+      throw IndeterminantLinearSystemException(e.key);
+    }
+    return Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(
+        packed.data(), lmgpu_adapter::varDim(p.typeOfSlot(si)), lmgpu_adapter::varDim(p.typeOfSlot(sj)));
   }
   lmgpu_marginals_stats stats() const { return dev_->problem().marginalsStats(); }
 
