@@ -209,7 +209,7 @@ struct lmgpu_isam2 {
   int delta_reads = 0;      // readers of delta since the last update returned
   // LMGPU_ISAM2_TRACE=1: wall time per phase of update(), printed when the handle is destroyed (development aid)
   bool trace = false;
-  double t_phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double t_phase[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_lap = 0;  // (t_lap: when the previous phase ended, is_lap)
   std::vector<int> elim_cid;  // cliques of the elimination whose status word is still on the device (checked when the update ends)
   bool elim_pending = false;
   bool elim_relay_pending = false;  // the elimination's status word has not been handed to the host yet
@@ -411,7 +411,6 @@ int is_flush(lmgpu_isam2* S) {
   }
   const size_t npush = S->pushes.size();
   S->delta_zero_pending = false;
-  bool recs_in_arena = true;
   if (npush) {
     char* hp;
     const int rc = is_stage_raw(S, npush * sizeof(lmgpu_isam2::PushRec), &hp, nullptr);
@@ -420,7 +419,6 @@ int is_flush(lmgpu_isam2* S) {
     d_recs = (const lmgpu_isam2::PushRec*)hp;
     S->pushes.clear();
   }
-  (void)recs_in_arena;
   if (npush) hipLaunchKernelGGL(isam2_scatter_kernel, dim3((unsigned)npush), dim3(256), 0, S->stream, d_recs);
   return LMGPU_OK;
 }
@@ -541,21 +539,27 @@ void is_remove_path(lmgpu_isam2* S, int id, std::vector<int>* bn, std::list<int>
   bn->push_back(id);
 }
 
-// launch the factor kernels of bucket b on the index list sel (device), count entries: Jacobians into the linearization cache
-void is_linearize_sel(lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, const int32_t* d_sel, int count) {
-  if (count <= 0) return;
+// bucket b as the factor kernels see it: n factors (all of them, or the index list sel), their Jacobians into the linearization cache or
+// (errors) their errors into the error buffer
+BucketDev is_bucket_dev(const lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, int n, const int32_t* sel, bool errors) {
   BucketDev d;
   d.type = b.type;
-  d.n = count;
+  d.n = n;
   d.noise_kind = b.noise_kind;
   d.vidx = b.d_vidx;
   d.meas = b.d_meas;
   d.noise = b.d_noise;
-  d.J = S->pool + b.joff;
-  d.epos = nullptr;
+  d.J = errors ? nullptr : S->pool + b.joff;
+  d.epos = errors ? b.d_epos : nullptr;
   d.robust = b.robust;
   d.rk = b.rk;
-  d.sel = d_sel;
+  d.sel = sel;
+  return d;
+}
+// launch the factor kernels of bucket b on the index list sel (device), count entries: Jacobians into the linearization cache
+void is_linearize_sel(lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, const int32_t* d_sel, int count) {
+  if (count <= 0) return;
+  const BucketDev d = is_bucket_dev(S, b, count, d_sel, false);
   ValuesDev vals;
   for (int t = 0; t < kNumVarTypes; t++) vals.v[t] = S->theta[t];
   const int g256 = (count + 255) / 256, g128 = (count + 127) / 128;
@@ -606,19 +610,7 @@ int is_linearize_jobs(lmgpu_isam2* S, const std::vector<std::pair<int, std::vect
       is_linearize_sel(S, b, d[q], count);
       continue;
     }
-    BucketDev bd;
-    bd.type = b.type;
-    bd.n = count;
-    bd.noise_kind = b.noise_kind;
-    bd.vidx = b.d_vidx;
-    bd.meas = b.d_meas;
-    bd.noise = b.d_noise;
-    bd.J = S->pool + b.joff;
-    bd.epos = nullptr;
-    bd.robust = b.robust;
-    bd.rk = b.rk;
-    bd.sel = d[q];
-    ml.b[ml.nb] = bd;
+    ml.b[ml.nb] = is_bucket_dev(S, b, count, d[q], false);
     ml.first[ml.nb] = blocks;
     blocks += (count + 127) / 128;
     if (++ml.nb == LIN_MULTI_MAX) launch();
@@ -903,7 +895,6 @@ __global__ __launch_bounds__(256) void isam2_wildfire_kernel(long long* __restri
     __syncthreads();
   }
 }
-
 
 // ISAM2::marginalCovariance(key) (gtsam/nonlinear/ISAM2.h:253-257 -> BayesTree::marginalFactor(key)->information().inverse()):
 // column c of Sigma = (R^T R)^-1 restricted to the variable is x with R^T y = e_c, R x = y.  In the Bayes tree both solves only touch the
@@ -1312,6 +1303,9 @@ struct IsGF {
   int32_t id;
   std::vector<int32_t> vids;
 };
+IsGF is_gf_of_clique(const lmgpu_isam2* S, int kind, int id) {  // kind 1 or 2: over the clique's separator
+  return IsGF{kind, id, std::vector<int32_t>(S->clq[id].vars.begin() + S->clq[id].nfv, S->clq[id].vars.end())};
+}
 
 int is_eliminate_fronts(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std::vector<int32_t>& vid_of_slot, const SymbolicFronts& sf, bool attach,
                         std::vector<int>* cid_out);
@@ -1346,51 +1340,107 @@ int is_eliminate(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std::vector
   return is_eliminate_fronts(S, gfs, vid_of_slot, sf, true, nullptr);
 }
 
-// the numeric half: the fronts of `sf` (over slots; vid_of_slot names their variables) as new cliques on the device.
-// attach = false: the cliques stay outside the tree (marginalizeLeaves eliminates ONE front to get a marginal and throws the conditional
-// away, ISAM2.cpp:624-637); their ids come back in *cid_out and the caller releases them.
-int is_eliminate_fronts(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std::vector<int32_t>& vid_of_slot, const SymbolicFronts& sf, bool attach,
-                        std::vector<int>* cid_out) {
-  const int NF = (int)sf.fronts.size();
-  std::vector<int> cid(NF);
-  std::vector<FrontDesc> fds(NF);
+// The numeric half: the fronts of `sf` (over slots; vid_of_slot names their variables) as new cliques on the device.  is_build_front_tables
+// hands the cliques the fronts became and the tables the front kernels read to is_launch_fronts in this struct.
+struct FrontTables {
+  std::vector<int> cid;  // front -> clique id
+  std::vector<FrontDesc> fds;
   std::vector<FrontFac> ffac;
   std::vector<FacDesc> fd;
   std::vector<ChildRef> childs;
   std::vector<int32_t> cmap, fxoff;
-  int max_level = 0;
-  std::map<int32_t, int32_t> colof;  // vid -> column offset inside the current front
-  int rc;
+  std::vector<int32_t> list;              // the LDS fronts, level by level
+  std::vector<std::pair<int, int>> lv;    // per level: (begin, count) in list
+  std::vector<std::vector<int32_t>> wide;  // per level: the fronts of more than 139 columns
+  // wide fronts are assembled by one wave per row walking that row's sources in a fixed order (hbm_assemble_rows_kernel, as in the batch path)
+  std::vector<int32_t> rowptr;
+  std::vector<RowSrc> rowsrc;
+  std::map<int32_t, int32_t> row_begin;  // front -> start of its n + 1 row pointers
+};
+typedef std::map<int32_t, int32_t> ColOf;  // vid -> column offset inside the current front
+
+// front `fr` as a new clique: its variables (their columns into *colof), its shape and its blocks in the pool
+int is_new_front_clique(lmgpu_isam2* S, const SymbolicFronts::F& fr, const std::vector<int32_t>& vid_of_slot, bool attach, ColOf* colof, int* id_out) {
+  const int id = *id_out = is_new_clique(S);
+  if (attach) S->touched.push_back(id);  // its descriptor reaches the device copy of the tree with the next patch
+  lmgpu_isam2::Clq& c = S->clq[id];
+  for (int32_t s : fr.frontals) c.vars.push_back(vid_of_slot[s]);
+  c.nfv = (int)fr.frontals.size();
+  for (int32_t s : fr.sep) c.vars.push_back(vid_of_slot[s]);
+  colof->clear();
+  int off = 0, rc;
+  for (size_t k = 0; k < c.vars.size(); k++) {
+    (*colof)[c.vars[k]] = off;
+    off += kVarDim[S->vars[c.vars[k]].type];
+    if ((int)k == c.nfv - 1) c.nf = off;
+  }
+  c.n = off + 1;
+  if (c.n > kLdsLimitN) {
+    // wider than an LDS front (loop closures of large graphs): one n x ld block, eliminated in place by the dense-front kernels
+    c.ld = (c.n + 15) & ~15;
+    if ((rc = is_pool_alloc(S, (size_t)c.n * c.ld, &c.f_off))) return rc;
+    c.rsd_off = c.f_off;
+    c.u_off = c.f_off + (int64_t)c.nf * c.ld + c.nf;
+  } else {
+    if ((rc = is_pool_alloc(S, (size_t)c.nf * c.n, &c.rsd_off))) return rc;
+    if ((rc = is_pool_alloc(S, (size_t)(c.n - c.nf) * (c.n - c.nf), &c.u_off))) return rc;
+  }
+  if (attach)
+    for (int k = 0; k < c.nfv; k++) S->node_of[c.vars[k]] = id;
+  return LMGPU_OK;
+}
+// an m x m information matrix in the pool (a child's cached factor = its update matrix, or a marginal factor) over the variables
+// vids[0 .. nv) + the right-hand side: extend-added into the front through a column map
+void is_add_child_ref(const lmgpu_isam2* S, FrontTables* T, int64_t u_off, int32_t ld, int32_t m, const int32_t* vids, size_t nv, const ColOf& colof, int rhs_col) {
+  ChildRef cr{};
+  cr.u_off = u_off;
+  cr.ld = ld;
+  cr.m = m;
+  cr.map_begin = (int)T->cmap.size();
+  for (size_t k = 0; k < nv; k++)
+    for (int d = 0; d < kVarDim[S->vars[vids[k]].type]; d++) T->cmap.push_back(colof.at(vids[k]) + d);
+  T->cmap.push_back(rhs_col);
+  T->childs.push_back(cr);
+}
+void is_add_child(const lmgpu_isam2* S, FrontTables* T, const lmgpu_isam2::Clq& ch, const ColOf& colof, int rhs_col) {
+  is_add_child_ref(S, T, ch.u_off, ch.ld > 0 ? ch.ld : ch.n - ch.nf, ch.n - ch.nf, ch.vars.data() + ch.nfv, ch.vars.size() - ch.nfv, colof, rhs_col);
+}
+// the cached Jacobian [A b] of nonlinear factor f as an own factor of the current front
+void is_add_jacobian(const lmgpu_isam2* S, FrontTables* T, const lmgpu_isam2::Fac& f, const ColOf& colof) {
+  const lmgpu_isam2::Bkt& b = S->bkts[f.bucket];
+  FacDesc d{};
+  d.joff = b.joff + (int64_t)f.lidx * b.rows * b.cols;
+  d.rows = (int16_t)b.rows;
+  d.d0 = (int16_t)kVarDim[S->vars[f.v[0]].type];
+  d.d1 = (int16_t)(f.v[1] >= 0 ? kVarDim[S->vars[f.v[1]].type] : 0);
+  d.x0 = S->vars[f.v[0]].xoff;
+  d.x1 = f.v[1] >= 0 ? S->vars[f.v[1]].xoff : -1;
+  d.d2 = (int16_t)(f.v[2] >= 0 ? kVarDim[S->vars[f.v[2]].type] : 0);
+  d.x2 = f.v[2] >= 0 ? S->vars[f.v[2]].xoff : -1;
+  FrontFac ff{};
+  ff.fac = (int32_t)T->fd.size();
+  ff.c0 = colof.at(f.v[0]);
+  ff.c1 = f.v[1] >= 0 ? colof.at(f.v[1]) : 0;
+  ff.c2 = f.v[2] >= 0 ? colof.at(f.v[2]) : 0;
+  T->fd.push_back(d);
+  T->ffac.push_back(ff);
+}
+
+// host: a clique per front (pool blocks, parents / children / roots wired when `attach`) and the tables the front kernels read
+int is_build_front_tables(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std::vector<int32_t>& vid_of_slot, const SymbolicFronts& sf, bool attach,
+                          FrontTables* T) {
+  const int NF = (int)sf.fronts.size();
+  T->cid.resize(NF);
+  T->fds.resize(NF);
+  int max_level = 0, rc;
+  ColOf colof;
   for (int fi = 0; fi < NF; fi++) {
     const SymbolicFronts::F& fr = sf.fronts[fi];
-    const int id = is_new_clique(S);
-    cid[fi] = id;
-    if (attach) S->touched.push_back(id);  // its descriptor reaches the device copy of the tree with the next patch
+    int id;
+    if ((rc = is_new_front_clique(S, fr, vid_of_slot, attach, &colof, &id))) return rc;
+    T->cid[fi] = id;
     lmgpu_isam2::Clq& c = S->clq[id];
-    for (int32_t s : fr.frontals) c.vars.push_back(vid_of_slot[s]);
-    c.nfv = (int)fr.frontals.size();
-    for (int32_t s : fr.sep) c.vars.push_back(vid_of_slot[s]);
-    colof.clear();
-    int off = 0;
-    for (size_t k = 0; k < c.vars.size(); k++) {
-      colof[c.vars[k]] = off;
-      off += kVarDim[S->vars[c.vars[k]].type];
-      if ((int)k == c.nfv - 1) c.nf = off;
-    }
-    c.n = off + 1;
-    if (c.n > kLdsLimitN) {
-      // wider than an LDS front (loop closures of large graphs): one n x ld block, eliminated in place by the dense-front kernels
-      c.ld = (c.n + 15) & ~15;
-      if ((rc = is_pool_alloc(S, (size_t)c.n * c.ld, &c.f_off))) return rc;
-      c.rsd_off = c.f_off;
-      c.u_off = c.f_off + (int64_t)c.nf * c.ld + c.nf;
-    } else {
-      if ((rc = is_pool_alloc(S, (size_t)c.nf * c.n, &c.rsd_off))) return rc;
-      if ((rc = is_pool_alloc(S, (size_t)(c.n - c.nf) * (c.n - c.nf), &c.u_off))) return rc;
-    }
-    if (attach)
-      for (int k = 0; k < c.nfv; k++) S->node_of[c.vars[k]] = id;
-    FrontDesc& F = fds[fi];
+    FrontDesc& F = T->fds[fi];
     F = FrontDesc{};
     F.n = c.n;
     F.nf = c.nf;
@@ -1399,157 +1449,159 @@ int is_eliminate_fronts(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std:
     F.ld_rsd = c.ld > 0 ? c.ld : c.n;
     F.ld_u = c.ld > 0 ? c.ld : c.n - c.nf;
     F.id = fi;
-    F.fac_begin = (int)ffac.size();
-    F.child_begin = (int)childs.size();
-    auto add_child = [&](const lmgpu_isam2::Clq& ch) {  // its cached factor (update matrix) is extend-added through a column map
-      ChildRef cr{};
-      cr.u_off = ch.u_off;
-      cr.ld = ch.ld > 0 ? ch.ld : ch.n - ch.nf;
-      cr.m = ch.n - ch.nf;
-      cr.map_begin = (int)cmap.size();
-      for (size_t k = ch.nfv; k < ch.vars.size(); k++)
-        for (int d = 0; d < kVarDim[S->vars[ch.vars[k]].type]; d++) cmap.push_back(colof.at(ch.vars[k]) + d);
-      cmap.push_back(c.n - 1);
-      childs.push_back(cr);
-    };
+    F.fac_begin = (int)T->ffac.size();
+    F.child_begin = (int)T->childs.size();
     for (int32_t g : fr.factors) {  // own factors in the reference's order: Jacobians, cached boundary factors; orphans become children
       const IsGF& gf = gfs[g];
       if (gf.kind == 0) {
-        const lmgpu_isam2::Fac& f = S->facs[gf.id];
-        const lmgpu_isam2::Bkt& b = S->bkts[f.bucket];
-        FacDesc d{};
-        d.joff = b.joff + (int64_t)f.lidx * b.rows * b.cols;
-        d.rows = (int16_t)b.rows;
-        d.d0 = (int16_t)kVarDim[S->vars[f.v[0]].type];
-        d.d1 = (int16_t)(f.v[1] >= 0 ? kVarDim[S->vars[f.v[1]].type] : 0);
-        d.x0 = S->vars[f.v[0]].xoff;
-        d.x1 = f.v[1] >= 0 ? S->vars[f.v[1]].xoff : -1;
-        d.d2 = (int16_t)(f.v[2] >= 0 ? kVarDim[S->vars[f.v[2]].type] : 0);
-        d.x2 = f.v[2] >= 0 ? S->vars[f.v[2]].xoff : -1;
-        FrontFac ff{};
-        ff.fac = (int32_t)fd.size();
-        ff.c0 = colof.at(f.v[0]);
-        ff.c1 = f.v[1] >= 0 ? colof.at(f.v[1]) : 0;
-        ff.c2 = f.v[2] >= 0 ? colof.at(f.v[2]) : 0;
-        fd.push_back(d);
-        ffac.push_back(ff);
+        is_add_jacobian(S, T, S->facs[gf.id], colof);
       } else if (gf.kind == 1) {
-        add_child(S->clq[gf.id]);
+        is_add_child(S, T, S->clq[gf.id], colof, c.n - 1);
       } else if (gf.kind == 3) {  // a marginal factor: its information matrix through a column map, like a cached boundary factor
         const lmgpu_isam2::Marg& mg = S->margs[S->facs[gf.id].marg];
-        ChildRef cr{};
-        cr.u_off = mg.u_off;
-        cr.ld = mg.ld;
-        cr.m = mg.m;
-        cr.map_begin = (int)cmap.size();
-        for (int32_t v : mg.vids)
-          for (int d = 0; d < kVarDim[S->vars[v].type]; d++) cmap.push_back(colof.at(v) + d);
-        cmap.push_back(c.n - 1);
-        childs.push_back(cr);
+        is_add_child_ref(S, T, mg.u_off, mg.ld, mg.m, mg.vids.data(), mg.vids.size(), colof, c.n - 1);
       }
     }
-    F.fac_count = (int)ffac.size() - F.fac_begin;
+    F.fac_count = (int)T->ffac.size() - F.fac_begin;
     for (int32_t chf : fr.children) {  // junction-tree children first (pre-order visitor), in order
-      add_child(S->clq[cid[chf]]);
-      c.children.push_back(cid[chf]);
-      S->clq[cid[chf]].parent = id;
+      is_add_child(S, T, S->clq[T->cid[chf]], colof, c.n - 1);
+      c.children.push_back(T->cid[chf]);
+      S->clq[T->cid[chf]].parent = id;
     }
     for (int32_t g : fr.factors)  // then the orphan subtrees whose separator this clique eliminates (ClusterTree-inst.h:228-236)
       if (gfs[g].kind == 2) {
         c.children.push_back(gfs[g].id);
         S->clq[gfs[g].id].parent = id;
       }
-    F.child_count = (int)childs.size() - F.child_begin;
-    F.fx_begin = (int)fxoff.size();
+    F.child_count = (int)T->childs.size() - F.child_begin;
+    F.fx_begin = (int)T->fxoff.size();
     for (int k = 0; k < c.nfv; k++)
-      for (int d = 0; d < kVarDim[S->vars[c.vars[k]].type]; d++) fxoff.push_back(S->vars[c.vars[k]].xoff + d);
+      for (int d = 0; d < kVarDim[S->vars[c.vars[k]].type]; d++) T->fxoff.push_back(S->vars[c.vars[k]].xoff + d);
     max_level = std::max(max_level, (int)fr.level);
   }
   if (attach)
-    for (int32_t r : sf.roots) S->roots.push_back(cid[r]);
-  if (cid_out) *cid_out = cid;
-  // ---- device: one lds_front_kernel launch per level of the new cliques
-  FrontDesc* d_fds = nullptr;
-  FrontFac* d_ffac = nullptr;
-  FacDesc* d_fd = nullptr;
-  ChildRef* d_childs = nullptr;
-  int32_t *d_cmap = nullptr, *d_fxoff = nullptr, *d_list = nullptr;
-  std::vector<int32_t> list;
-  std::vector<std::pair<int, int>> lv(max_level + 1, {0, 0});
-  std::vector<std::vector<int32_t>> wide(max_level + 1);  // per level: the fronts of more than 139 columns
+    for (int32_t r : sf.roots) S->roots.push_back(T->cid[r]);
+  T->lv.assign(max_level + 1, {0, 0});
+  T->wide.resize(max_level + 1);
   for (int l = 0; l <= max_level; l++) {
-    lv[l].first = (int)list.size();
+    T->lv[l].first = (int)T->list.size();
     for (int fi = 0; fi < NF; fi++) {
       if (sf.fronts[fi].level != l) continue;
-      if (S->clq[cid[fi]].ld > 0)
-        wide[l].push_back(fi);
+      if (S->clq[T->cid[fi]].ld > 0)
+        T->wide[l].push_back(fi);
       else
-        list.push_back(fi);
+        T->list.push_back(fi);
     }
-    lv[l].second = (int)list.size() - lv[l].first;
+    T->lv[l].second = (int)T->list.size() - T->lv[l].first;
   }
-  // wide fronts are assembled by one wave per row walking that row's sources in a fixed order (hbm_assemble_rows_kernel, as in the batch path)
-  std::vector<int32_t> rowptr;
-  std::vector<RowSrc> rowsrc;
-  std::map<int32_t, int32_t> row_begin;  // front -> start of its n + 1 row pointers
   for (int l = 0; l <= max_level; l++)
-    for (int32_t fi : wide[l]) {
-      const FrontDesc& F = fds[fi];
-      std::vector<std::vector<RowSrc>> rows(F.n);
-      for (int k = 0; k < F.child_count; k++) {
-        const ChildRef& c = childs[F.child_begin + k];
-        for (int i = 0; i < c.m; i++) rows[cmap[c.map_begin + i]].push_back(RowSrc{F.child_begin + k, i});
-      }
-      for (int k = 0; k < F.fac_count; k++) {
-        const FrontFac& ff = ffac[F.fac_begin + k];
-        const FacDesc& d = fd[ff.fac];
-        const int nc = d.d0 + d.d1 + d.d2 + 1;
-        for (int p = 0; p < nc; p++) {
-          const int gp = (p < d.d0) ? ff.c0 + p : (p < d.d0 + d.d1 ? ff.c1 + (p - d.d0) : (p < d.d0 + d.d1 + d.d2 ? ff.c2 + (p - d.d0 - d.d1) : F.n - 1));
-          rows[gp].push_back(RowSrc{-(F.fac_begin + k) - 1, p});
-        }
-      }
-      row_begin[fi] = (int32_t)rowptr.size();
-      for (int r = 0; r < F.n; r++) {
-        rowptr.push_back((int32_t)rowsrc.size());
-        rowsrc.insert(rowsrc.end(), rows[r].begin(), rows[r].end());
-      }
-      rowptr.push_back((int32_t)rowsrc.size());
-    }
-  int32_t* d_rowptr = nullptr;
-  RowSrc* d_rowsrc = nullptr;
-  if (!rowptr.empty()) {
-    if ((rc = is_stage(S, rowptr, &d_rowptr, true)) || (rc = is_stage(S, rowsrc, &d_rowsrc, true))) return rc;
+    for (int32_t fi : T->wide[l]) T->row_begin[fi] = append_row_sources(T->fds[fi], T->childs, T->cmap, T->ffac, T->fd, T->rowptr, T->rowsrc);
+  return LMGPU_OK;
+}
+
+// the front tables in the device arena (the front kernels walk them with chains of dependent reads: one copy for all of them)
+struct FrontTablesDev {
+  FrontDesc* fds = nullptr;
+  FrontFac* ffac = nullptr;
+  FacDesc* fd = nullptr;
+  ChildRef* childs = nullptr;
+  int32_t *cmap = nullptr, *fxoff = nullptr, *list = nullptr, *rowptr = nullptr;
+  RowSrc* rowsrc = nullptr;
+};
+int is_stage_front_tables(lmgpu_isam2* S, const FrontTables& T, FrontTablesDev* D) {
+  int rc;
+  if (!T.rowptr.empty()) {
+    if ((rc = is_stage(S, T.rowptr, &D->rowptr, true)) || (rc = is_stage(S, T.rowsrc, &D->rowsrc, true))) return rc;
     if (!S->inv16) ISCHECK(hipMalloc((void**)&S->inv16, 16 * 256 * sizeof(double)));
   }
-  // (the front kernels walk these tables with chains of dependent reads: they go into the device arena, one copy for all of them)
-  if ((rc = is_stage(S, fds, &d_fds, true)) || (rc = is_stage(S, ffac, &d_ffac, true)) || (rc = is_stage(S, fd, &d_fd, true)) ||
-      (rc = is_stage(S, childs, &d_childs, true)) || (rc = is_stage(S, cmap, &d_cmap, true)) || (rc = is_stage(S, fxoff, &d_fxoff, true)) ||
-      (rc = is_stage(S, list, &d_list, true)))
+  if ((rc = is_stage(S, T.fds, &D->fds, true)) || (rc = is_stage(S, T.ffac, &D->ffac, true)) || (rc = is_stage(S, T.fd, &D->fd, true)) ||
+      (rc = is_stage(S, T.childs, &D->childs, true)) || (rc = is_stage(S, T.cmap, &D->cmap, true)) || (rc = is_stage(S, T.fxoff, &D->fxoff, true)) ||
+      (rc = is_stage(S, T.list, &D->list, true)))
     return rc;
-  {
-    const int32_t fresh = 0x7f7f7f7f;  // the status word is reset by the scatter kernel of this flush
-    if ((rc = is_push(S, S->d_status, &fresh, sizeof(fresh)))) return rc;
+  const int32_t fresh = 0x7f7f7f7f;  // the status word is reset by the scatter kernel of this flush
+  return is_push(S, S->d_status, &fresh, sizeof(fresh));
+}
+// largest front and Jacobian staging (doubles, rounded up to 8) of the LDS fronts list[begin .. begin + count): what sizes their launch
+void is_lds_launch_shape(const FrontTables& T, int begin, int count, int* nmax, int* jcap) {
+  int jc = 96;
+  *nmax = 1;
+  for (int q = begin; q < begin + count; q++) {
+    const FrontDesc& F = T.fds[T.list[q]];
+    *nmax = std::max(*nmax, F.n);
+    jc = std::max(jc, std::min(front_jacobian_doubles(F, T.ffac.data(), T.fd.data()), LDSF_JCAP));
   }
+  *jcap = (jc + 7) & ~7;
+}
+// a front of more than 139 columns: assembled by row in its n x ld block, then right-looking over 256-row outer panels, the two-launch
+// panel form + the trailing update (lmgpu.hip: panel_alone / the unfused step)
+int is_launch_wide_front(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D, int32_t fi) {
+  const FrontDesc& F = T.fds[fi];
+  const lmgpu_isam2::Clq& c = S->clq[T.cid[fi]];
+  const int ld = c.ld, n = c.n;
+  double* A = S->pool + c.f_off;
+  ISCHECK(hipMemsetAsync(A, 0, (size_t)n * ld * sizeof(double), S->stream));
+  hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, S->stream, F, c.f_off, ld, (const int32_t*)(D.rowptr + T.row_begin.at(fi)),
+                     (const RowSrc*)D.rowsrc, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const FrontFac*)D.ffac, (const FacDesc*)D.fd, S->pool, 1);
+  const int np = (F.nf + NBO - 1) / NBO;
+  for (int i = 0; i < np; i++) {
+    const int k0 = i * NBO, kb = std::min(F.nf, (i + 1) * NBO) - k0, r0 = k0 + kb, cols = n - r0, m = n - r0;
+    hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, S->stream, A, ld, F.nf, k0, kb, F.id, S->d_status, S->inv16);
+    if (cols > 0) hipLaunchKernelGGL(panel_trsm_kernel, dim3((cols + 63) / 64), dim3(256), 0, S->stream, A, ld, n, k0, kb, (const double*)S->inv16);
+    if (m > 0 && m <= 1024) {
+      const int Sx = (m + 63) / 64;
+      hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * Sx, Sx), dim3(256), 0, S->stream, A, ld, n, k0, kb, r0);
+    } else if (m > 0) {
+      const int Tm = (m + 127) / 128;
+      hipLaunchKernelGGL(syrk_mfma_kernel, dim3(Tm, Tm), dim3(256), kSyrkLds, S->stream, A, ld, n, k0, kb, r0, n);
+    }
+  }
+  return LMGPU_OK;
+}
+// one lds_front_kernel launch for the LDS fronts of level l
+void is_launch_lds_level(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D, int l) {
+  const int first = T.lv[l].first, count = T.lv[l].second;
+  int nmax, jcap;
+  is_lds_launch_shape(T, first, count, &nmax, &jcap);
+  const bool wg1024 = nmax > 72 && count <= 256;  // a handful of wide cliques: sixteen waves each (the batch path's rule)
+  auto* kernel = wg1024 ? lds_front_kernel<false, 1024> : lds_front_kernel<false>;
+  const int threads = wg1024 ? 1024 : (nmax <= 24 ? 64 : 256);
+  hipLaunchKernelGGL(kernel, dim3(count), dim3(threads), lds_front_bytes(jcap, nmax, nmax), S->stream, (const int32_t*)(D.list + first), (const FrontDesc*)D.fds,
+                     (const FrontFac*)D.ffac, (const FacDesc*)D.fd, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const int32_t*)D.fxoff, S->pool, 0.0,
+                     (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, nmax, (double*)nullptr, jcap, (const double*)nullptr,
+                     (const char*)nullptr, 0);
+}
+// ONE dataflow launch for all the LDS fronts (lds_front_merged_kernel); it relays the status word to the host itself
+void is_launch_merged(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D) {
+  const int count = (int)T.list.size();
+  int nmax, jcap;
+  is_lds_launch_shape(T, 0, count, &nmax, &jcap);
+  const size_t lds = lds_front_bytes(jcap, nmax, nmax);
+  // (four waves unless every clique takes the one-wave register path: the blocked Cholesky of the LDS body needs four -- with two, the 30-40
+  //  pivots of VisualISAM2Example's root clique were taken one by one: 33 of the 100 us its launch took)
+  auto* kernel = nmax > 72 ? lds_front_merged_kernel<1024> : lds_front_merged_kernel<256>;
+  const int threads = nmax > 72 ? 1024 : (nmax <= 16 ? 64 : 256);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(threads), lds, S->stream, (const int32_t*)D.list, 0, count, (const FrontDesc*)D.fds,
+                     (const FrontFac*)D.ffac, (const FacDesc*)D.fd, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const int32_t*)D.fxoff, S->pool, 0.0,
+                     (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, jcap, (const double*)nullptr, S->d_eticket, S->h_status_dev);
+}
+
+// device: the tables into the arena, the status word / tickets / what the next walk needs as pushes, ONE flush, then the merged launch or
+// one lds_front_kernel launch per level of the new cliques (a level's wide fronts in front of it)
+int is_launch_fronts(lmgpu_isam2* S, const FrontTables& T, bool attach) {
+  FrontTablesDev D;
+  int rc;
+  if ((rc = is_stage_front_tables(S, T, &D))) return rc;
   // Several levels of LDS cliques and no wide one: ONE dataflow launch for all of them (lds_front_merged_kernel: tickets bottom-up, update
   // matrices handed from child to parent by value) instead of a launch per level -- an update of VisualISAM2Example is two levels, one of
   // the city10000 loop two to five, each a dependent launch of a few workgroups.
   bool any_wide = false;
-  for (int l = 0; l <= max_level; l++) any_wide = any_wide || !wide[l].empty();
-  const bool merged = !any_wide && list.size() <= 4096 && !dev_switch("LMGPU_ISAM2_NO_MERGE");  // (a single level too: the launch relays the status)
-  int m_nmax = 1, m_jc = 96;
+  for (const std::vector<int32_t>& w : T.wide) any_wide = any_wide || !w.empty();
+  const bool merged = !any_wide && T.list.size() <= 4096 && !dev_switch("LMGPU_ISAM2_NO_MERGE");  // (a single level too: the launch relays the status)
   if (merged) {
-    for (int32_t fi : list) {
+    for (int32_t fi : T.list) {
       // "not published yet" over the clique's update matrix: a fill record of the flush's scatter kernel (LDS cliques: a dense block of its own)
-      const int mm = fds[fi].n - fds[fi].nf;
-      S->pushes.push_back(lmgpu_isam2::PushRec{S->pool + fds[fi].u_off, nullptr, (uint32_t)(2 * mm * mm), 1u});
-      m_nmax = std::max(m_nmax, fds[fi].n);
-      int tot = 0;
-      for (int k = 0; k < fds[fi].fac_count; k++) {
-        const FacDesc& d = fd[ffac[fds[fi].fac_begin + k].fac];
-        tot += d.rows * (d.d0 + d.d1 + d.d2 + 1);
-      }
-      m_jc = std::max(m_jc, std::min(tot, LDSF_JCAP));
+      const int mm = T.fds[fi].n - T.fds[fi].nf;
+      S->pushes.push_back(lmgpu_isam2::PushRec{S->pool + T.fds[fi].u_off, nullptr, (uint32_t)(2 * mm * mm), 1u});
     }
     if (!S->d_eticket) ISCHECK(hipMalloc((void**)&S->d_eticket, 2 * sizeof(unsigned int)));
     const unsigned int zero[2] = {0u, 0u};  // the ticket counter, the count of finished workgroups
@@ -1559,80 +1611,28 @@ int is_eliminate_fronts(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std:
   if (attach && !S->dogleg && !dev_switch("LMGPU_ISAM2_LATE_WALK_PREP") && (rc = is_walk_prepare(S, is_walk_by_value(S)))) return rc;
   *S->h_status = 0x7f7f7f7f;  // (before the launch that may relay the status word)
   if ((rc = is_flush(S))) return rc;  // the tables above, and whatever the update pushed before (new values, factor rows)
-  if (merged) {
-    const int jcap = (m_jc + 7) & ~7;
-    const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - jcap) * 8 + 64 + (size_t)m_nmax * m_nmax * sizeof(double);
-    if (m_nmax > 72)
-      hipLaunchKernelGGL(lds_front_merged_kernel<1024>, dim3((unsigned)list.size()), dim3(1024), lds, S->stream, (const int32_t*)d_list, 0, (int)list.size(),
-                         (const FrontDesc*)d_fds, (const FrontFac*)d_ffac, (const FacDesc*)d_fd, (const ChildRef*)d_childs, (const int32_t*)d_cmap,
-                         (const int32_t*)d_fxoff, S->pool, 0.0, (const double*)nullptr, (const double*)S->ones, S->d_status, m_nmax, jcap,
-                         (const double*)nullptr, S->d_eticket, S->h_status_dev);
-    else
-      // (four waves unless every clique takes the one-wave register path: the blocked Cholesky of the LDS body needs four -- with two, the 30-40
-      //  pivots of VisualISAM2Example's root clique were taken one by one: 33 of the 100 us its launch took)
-      hipLaunchKernelGGL(lds_front_merged_kernel<256>, dim3((unsigned)list.size()), dim3(m_nmax <= 16 ? 64 : 256), lds, S->stream,
-                         (const int32_t*)d_list, 0, (int)list.size(), (const FrontDesc*)d_fds, (const FrontFac*)d_ffac, (const FacDesc*)d_fd,
-                         (const ChildRef*)d_childs, (const int32_t*)d_cmap, (const int32_t*)d_fxoff, S->pool, 0.0, (const double*)nullptr,
-                         (const double*)S->ones, S->d_status, m_nmax, jcap, (const double*)nullptr, S->d_eticket, S->h_status_dev);
-  }
-  for (int l = 0; l <= max_level && !merged; l++) {
-    for (int32_t fi : wide[l]) {  // (the level's LDS fronts and these only depend on the levels below)
-      const FrontDesc& F = fds[fi];
-      const lmgpu_isam2::Clq& c = S->clq[cid[fi]];
-      const int ld = c.ld, n = c.n;
-      double* A = S->pool + c.f_off;
-      ISCHECK(hipMemsetAsync(A, 0, (size_t)n * ld * sizeof(double), S->stream));
-      hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, S->stream, F, c.f_off, ld, (const int32_t*)(d_rowptr + row_begin[fi]),
-                         (const RowSrc*)d_rowsrc, (const ChildRef*)d_childs, (const int32_t*)d_cmap, (const FrontFac*)d_ffac, (const FacDesc*)d_fd, S->pool, 1);
-      // right-looking over 256-row outer panels, the two-launch panel form + the trailing update (lmgpu.hip: panel_alone / the unfused step)
-      const int np = (F.nf + NBO - 1) / NBO;
-      for (int i = 0; i < np; i++) {
-        const int k0 = i * NBO, kb = std::min(F.nf, (i + 1) * NBO) - k0, r0 = k0 + kb, cols = n - r0, m = n - r0;
-        hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, S->stream, A, ld, F.nf, k0, kb, F.id, S->d_status, S->inv16);
-        if (cols > 0) hipLaunchKernelGGL(panel_trsm_kernel, dim3((cols + 63) / 64), dim3(256), 0, S->stream, A, ld, n, k0, kb, (const double*)S->inv16);
-        if (m > 0) {
-          if (m <= 1024) {
-            const int Sx = (m + 63) / 64;
-            hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * Sx, Sx), dim3(256), 0, S->stream, A, ld, n, k0, kb, r0);
-          } else {
-            const int T = (m + 127) / 128;
-            hipLaunchKernelGGL(syrk_mfma_kernel, dim3(T, T), dim3(256), kSyrkLds, S->stream, A, ld, n, k0, kb, r0, n);
-          }
-        }
-      }
-    }
-    if (lv[l].second == 0) continue;
-    int nmax = 1, jc = 96;
-    for (int q = 0; q < lv[l].second; q++) {
-      const int fi = list[lv[l].first + q];
-      nmax = std::max(nmax, fds[fi].n);
-      int tot = 0;
-      for (int k = 0; k < fds[fi].fac_count; k++) {
-        const FacDesc& d = fd[ffac[fds[fi].fac_begin + k].fac];
-        tot += d.rows * (d.d0 + d.d1 + d.d2 + 1);
-      }
-      jc = std::max(jc, std::min(tot, LDSF_JCAP));
-    }
-    const int jcap = (jc + 7) & ~7;
-    const int threads = nmax <= 24 ? 64 : 256;
-    const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - jcap) * 8 + 64 + (size_t)nmax * nmax * sizeof(double);
-    if (nmax > 72 && lv[l].second <= 256)  // a handful of wide cliques: sixteen waves each (the batch path's rule)
-      hipLaunchKernelGGL((lds_front_kernel<false, 1024>), dim3(lv[l].second), dim3(1024), lds, S->stream, (const int32_t*)(d_list + lv[l].first),
-                         (const FrontDesc*)d_fds, (const FrontFac*)d_ffac, (const FacDesc*)d_fd, (const ChildRef*)d_childs, (const int32_t*)d_cmap,
-                         (const int32_t*)d_fxoff, S->pool, 0.0, (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, nmax, (double*)nullptr, jcap,
-                         (const double*)nullptr, (const char*)nullptr, 0);
-    else
-      hipLaunchKernelGGL(lds_front_kernel<false>, dim3(lv[l].second), dim3(threads), lds, S->stream, (const int32_t*)(d_list + lv[l].first),
-                         (const FrontDesc*)d_fds, (const FrontFac*)d_ffac, (const FacDesc*)d_fd, (const ChildRef*)d_childs, (const int32_t*)d_cmap,
-                         (const int32_t*)d_fxoff, S->pool, 0.0, (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, nmax, (double*)nullptr, jcap,
-                         (const double*)nullptr, (const char*)nullptr, 0);
+  if (merged) is_launch_merged(S, T, D);
+  for (size_t l = 0; l < T.lv.size() && !merged; l++) {
+    for (int32_t fi : T.wide[l])  // (the level's LDS fronts and these only depend on the levels below)
+      if ((rc = is_launch_wide_front(S, T, D, fi))) return rc;
+    if (T.lv[l].second > 0) is_launch_lds_level(S, T, D, (int)l);
   }
   // the status word comes back with the one wait that ends the update (is_finish_elimination): the mark kernel, the last launch of an
   // update that eliminated anything, relays it into the host's pinned word
   S->elim_relay_pending = !merged;  // (the merged launch hands the status to the host itself)
-  S->elim_cid = cid;
+  S->elim_cid = T.cid;
   S->elim_pending = true;
   return LMGPU_OK;
+}
+
+// attach = false: the cliques stay outside the tree (marginalizeLeaves eliminates ONE front to get a marginal and throws the conditional
+// away, ISAM2.cpp:624-637); their ids come back in *cid_out and the caller releases them.
+int is_eliminate_fronts(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const std::vector<int32_t>& vid_of_slot, const SymbolicFronts& sf, bool attach,
+                        std::vector<int>* cid_out) {
+  FrontTables T;
+  const int rc = is_build_front_tables(S, gfs, vid_of_slot, sf, attach, &T);
+  if (cid_out) *cid_out = T.cid;
+  return rc ? rc : is_launch_fronts(S, T, attach);
 }
 
 // the wait that ends an update: EliminateCholesky failed -> IndeterminantLinearSystemException(first frontal key), HessianFactor.cpp:475-482
@@ -1655,7 +1655,6 @@ int is_finish_elimination(lmgpu_isam2* S) {
   }
   return LMGPU_OK;
 }
-
 
 // upload an index list and run `fn(device list, count)`
 template <typename Fn>
@@ -1698,18 +1697,7 @@ int is_graph_error(lmgpu_isam2* S, bool at_estimate, double* out) {
   }
   for (const lmgpu_isam2::Bkt& b : S->bkts) {
     if (b.n == 0) continue;
-    BucketDev d;
-    d.type = b.type;
-    d.n = b.n;
-    d.noise_kind = b.noise_kind;
-    d.vidx = b.d_vidx;
-    d.meas = b.d_meas;
-    d.noise = b.d_noise;
-    d.J = nullptr;
-    d.epos = b.d_epos;
-    d.robust = b.robust;
-    d.rk = b.rk;
-    d.sel = nullptr;
+    const BucketDev d = is_bucket_dev(S, b, b.n, nullptr, true);
     const int g256 = (b.n + 255) / 256, g128 = (b.n + 127) / 128;
     double* eb = S->d_ebuf;
     switch (b.type) {
@@ -1916,10 +1904,74 @@ int is_empty_slot(lmgpu_isam2* S, int32_t idx) {
   return is_push(S, S->bkts[f.bucket].d_epos + f.lidx, &dump, sizeof(dump));
 }
 
-// ISAM2::update (gtsam/nonlinear/ISAM2.cpp:419-480)
-int is_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, lmgpu_isam2_result* result) {
-  const bool force_relinearize = up.force_relinearize;
-  // what can be refused is refused before anything changes
+// FactorGraph::add_factors (FactorGraph-inst.h:109-137): the index of the next new factor -- the indices continue the list, or
+// (findUnusedFactorSlots) the new factors fill the empty slots from the front; *slot_scan = where the previous call stopped looking
+size_t is_take_slot(const lmgpu_isam2* S, size_t* slot_scan) {
+  if (!S->find_unused_slots) return S->facs.size();
+  while (*slot_scan < S->facs.size() && !S->facs[*slot_scan].removed) ++*slot_scan;
+  return *slot_scan;
+}
+void is_put_factor(lmgpu_isam2* S, size_t slot, const lmgpu_isam2::Fac& f) {
+  if (slot == S->facs.size()) S->facs.emplace_back();
+  S->facs[slot] = f;
+}
+// a factor leaves the graph (pushBackFactors' removals ISAM2-impl.h:157-172, marginalizeLeaves ISAM2.cpp:672-682): the variable index
+// forgets it, its slot empties
+int is_forget_factor(lmgpu_isam2* S, int32_t idx) {
+  for (int32_t v : is_fac_vids(S, S->facs[idx])) {
+    std::vector<int32_t>& entries = S->vindex[v];
+    entries.erase(std::find(entries.begin(), entries.end(), idx));
+  }
+  return is_empty_slot(S, idx);
+}
+// ISAM2::removeVariables (ISAM2.cpp:385-398): the variable leaves theta / delta / the variable index; its storage is not reused.
+// (A variable update() retires has lost its last factor, so its entry of the variable index is empty already; a marginalized leaf's is not.)
+int is_retire_variable(lmgpu_isam2* S, int32_t v) {
+  S->vars[v].dead = true;
+  S->vindex[v].clear();
+  if (S->dogleg) {  // the vectors of the dog leg are summed over all scalars: a retired variable must not count
+    const size_t o = (size_t)S->vars[v].xoff, nb = (size_t)kVarDim[S->vars[v].type] * sizeof(double);
+    ISCHECK(hipMemsetAsync(S->delta + o, 0, nb, S->stream));
+    ISCHECK(hipMemsetAsync(S->delta_newton + o, 0, nb, S->stream));
+    ISCHECK(hipMemsetAsync(S->rgprod + o, 0, nb, S->stream));
+  }
+  S->replaced[v] = 0;
+  S->node_of[v] = -1;
+  S->fixed.erase(S->vars[v].key);
+  S->vid_of.erase(S->vars[v].key);
+  return LMGPU_OK;
+}
+
+// What flows between the phases of one update: ISAM2::update's locals and UpdateImpl's members (ISAM2-impl.h:113-140)
+struct UpdateWork {
+  std::vector<lmgpu_isam2::NewVar> new_vars;  // the pending input, swapped out of the handle
+  std::vector<lmgpu_isam2::NewFac> new_facs;
+  std::vector<int32_t> new_idx;                       // newFactorsIndices
+  std::map<int, std::vector<int32_t>> new_by_bucket;  // bucket -> local indices of its new factors
+  std::set<uint64_t> markedKeys, keysWithRemoved, unusedKeys;
+  std::vector<int32_t> observed;  // observedKeys = the marked keys that stay in the system, ascending by key (as vids)
+  std::set<int32_t> relin;        // relinKeys as vids
+  bool relinNeeded = false;
+  int relin_ntot = 0;         // scalars of delta the pinned copy holds when relinearization is checked
+  bool reads_before = false;  // somebody read delta since the previous update
+  lmgpu_isam2_result res{};
+};
+
+// LMGPU_ISAM2_TRACE: the wall time since the previous lap goes to phase i
+void is_lap(lmgpu_isam2* S, int i) {
+  if (!S->trace) return;
+  const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  if (i >= 0) {
+    S->t_phase[i] += t - S->t_lap;
+    if (t - S->t_lap > 0.02) std::fprintf(stderr, "isam2 update %d: phase %d took %.1f ms\n", S->update_count, i, 1e3 * (t - S->t_lap));
+  }
+  S->t_lap = t;
+}
+
+// Everything an update can refuse, BEFORE anything changes.  A bad removeFactorIndices / extraReelimKeys entry leaves the pending input
+// queued; a pending input that is wrong in itself is dropped with the refusal, so that the handle stays as it was and the next update
+// starts clean (a refusal in the middle used to leave variables committed, factors half entered and the queues still full).
+int is_check_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up) {
   for (uint64_t idx : up.remove)
     if (idx >= S->facs.size()) {
       S->err = "ISAM2: removeFactorIndices names a factor that does not exist (factors added by the same update cannot be removed by it)";
@@ -1933,215 +1985,183 @@ int is_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, lmgpu_isam2_resul
       return LMGPU_INVALID;
     }
   }
-  {
-    // the pending input is checked as a whole BEFORE anything changes; a refused update drops it, so that the handle stays as it was and the
-    // next update starts clean (a refusal in the middle used to leave variables committed, factors half entered and the queues still full)
-    auto refuse = [&](const char* why) {
-      S->new_vars.clear();
-      S->new_facs.clear();
-      S->err = why;
-      return LMGPU_INVALID;
-    };
-    std::map<uint64_t, int32_t> pending_type;
-    for (const lmgpu_isam2::NewVar& nv : S->new_vars) {
-      if (S->vid_of.count(nv.key) || !pending_type.emplace(nv.key, nv.type).second) return refuse("ISAM2: variable already exists");
-      if (!S->relin_thresholds.empty()) {  // the reference throws when a variable's Symbol character has no vector of its dimension (ISAM2-impl.h:258-262)
-        auto it = S->relin_thresholds.find((unsigned char)(nv.key >> 56));
-        if (it == S->relin_thresholds.end() || (int)it->second.size() != kVarDim[nv.type])
-          return refuse("ISAM2: the relinearization threshold (FastMap<char, Vector>) has no vector of the right dimension for a new variable's Symbol character");
-      }
+  auto refuse = [&](const char* why) {
+    S->new_vars.clear();
+    S->new_facs.clear();
+    S->err = why;
+    return LMGPU_INVALID;
+  };
+  std::map<uint64_t, int32_t> pending_type;
+  for (const lmgpu_isam2::NewVar& nv : S->new_vars) {
+    if (S->vid_of.count(nv.key) || !pending_type.emplace(nv.key, nv.type).second) return refuse("ISAM2: variable already exists");
+    if (!S->relin_thresholds.empty()) {  // the reference throws when a variable's Symbol character has no vector of its dimension (ISAM2-impl.h:258-262)
+      auto it = S->relin_thresholds.find((unsigned char)(nv.key >> 56));
+      if (it == S->relin_thresholds.end() || (int)it->second.size() != kVarDim[nv.type])
+        return refuse("ISAM2: the relinearization threshold (FastMap<char, Vector>) has no vector of the right dimension for a new variable's Symbol character");
     }
-    for (const lmgpu_isam2::NewFac& nf : S->new_facs)
-      for (int k = 0; k < kFactorArity[nf.type]; k++) {
-        int32_t t = -1;
-        auto it = S->vid_of.find(nf.k[k]);
-        if (it != S->vid_of.end()) {
-          t = S->vars[it->second].type;
-        } else {
-          auto pt = pending_type.find(nf.k[k]);
-          if (pt == pending_type.end()) return refuse("ISAM2: a new factor references a variable that has no value");
-          t = pt->second;
-        }
-        if (t != factor_var_type(nf.type, k)) return refuse("factor/variable type mismatch");
-      }
-    if (up.has_constrained)
-      for (auto& kg : up.constrained)
-        if (!S->vid_of.count(kg.first) && !pending_type.count(kg.first)) return refuse("ISAM2: constrainedKeys names a variable that is not in the system");
   }
-  S->update_count += 1;
-  lmgpu_isam2_result res{};
+  for (const lmgpu_isam2::NewFac& nf : S->new_facs)
+    for (int k = 0; k < kFactorArity[nf.type]; k++) {
+      int32_t t = -1;
+      auto it = S->vid_of.find(nf.k[k]);
+      if (it != S->vid_of.end()) {
+        t = S->vars[it->second].type;
+      } else {
+        auto pt = pending_type.find(nf.k[k]);
+        if (pt == pending_type.end()) return refuse("ISAM2: a new factor references a variable that has no value");
+        t = pt->second;
+      }
+      if (t != factor_var_type(nf.type, k)) return refuse("factor/variable type mismatch");
+    }
+  if (up.has_constrained)
+    for (auto& kg : up.constrained)
+      if (!S->vid_of.count(kg.first) && !pending_type.count(kg.first)) return refuse("ISAM2: constrainedKeys names a variable that is not in the system");
+  return LMGPU_OK;
+}
+
+// ISAM2::addVariables (ISAM2.cpp:365-384): the device arrays sized by the number of variables / scalars grow to hold the new ones too,
+// then the host records, the values and delta offsets per type, delta = 0 over the new scalars
+int is_add_variables(lmgpu_isam2* S, const UpdateWork& W) {
+  if (W.new_vars.empty()) return LMGPU_OK;
+  int add[kNumVarTypes] = {}, addtot = 0, rc;
+  for (auto& nv : W.new_vars) {
+    add[nv.type]++;
+    addtot += kVarDim[nv.type];
+  }
+  for (int t = 0; t < kNumVarTypes; t++) {
+    const size_t need = (size_t)(S->type_count[t] + add[t]);
+    if (!add[t] || need <= (size_t)S->type_cap[t]) continue;
+    const size_t ncap = is_next_cap((size_t)S->type_cap[t], need);
+    if ((rc = is_realloc(S, &S->theta[t], ncap * kVarStore[t], (size_t)S->type_count[t] * kVarStore[t]))) return rc;
+    if ((rc = is_realloc(S, &S->est[t], ncap * kVarStore[t], 0))) return rc;
+    if ((rc = is_realloc(S, &S->d_type_xoff[t], ncap, (size_t)S->type_count[t]))) return rc;
+    S->type_cap[t] = (int)ncap;
+  }
+  if (S->ntot + addtot > S->ntot_cap) {
+    const size_t ncap = is_next_cap((size_t)S->ntot_cap, (size_t)(S->ntot + addtot));
+    if ((rc = is_realloc(S, &S->delta, ncap, (size_t)S->ntot))) return rc;
+    if (S->dogleg) {
+      if ((rc = is_realloc(S, &S->delta_newton, ncap, (size_t)S->ntot)) || (rc = is_realloc(S, &S->rgprod, ncap, (size_t)S->ntot)) ||
+          (rc = is_realloc(S, &S->grad, ncap, 0)) || (rc = is_realloc(S, &S->dx_u, ncap, 0)))
+        return rc;
+    }
+    if ((rc = is_realloc(S, &S->ones, ncap, 0))) return rc;
+    if ((rc = is_realloc(S, &S->d_replaced, ncap, (size_t)S->ntot))) return rc;
+    if ((rc = is_realloc(S, &S->d_changed, ncap, 0))) return rc;
+    ISCHECK(hipMemsetAsync(S->d_changed, 0, ncap, S->stream));  // (epochs: a fresh array must not hold the current one)
+    std::vector<double> one(ncap, 1.0);
+    ISCHECK(hipMemcpy(S->ones, one.data(), ncap * sizeof(double), hipMemcpyHostToDevice));
+    ISCHECK(hipMemsetAsync(S->d_replaced + S->ntot, 0, ncap - S->ntot, S->stream));
+    S->ntot_cap = (int)ncap;
+  }
+  // the new variables of a type take consecutive places: one copy per type for the values, one for the delta offsets
+  const int ntot0 = S->ntot;
+  int first_tidx[kNumVarTypes];
+  std::vector<double> vals[kNumVarTypes];
+  std::vector<int32_t> xoffs[kNumVarTypes];
+  for (int t = 0; t < kNumVarTypes; t++) first_tidx[t] = S->type_count[t];
+  for (auto& nv : W.new_vars) {
+    lmgpu_isam2::Var v{nv.key, nv.type, S->type_count[nv.type]++, S->ntot, false};
+    const int vid = (int)S->vars.size();
+    S->vars.push_back(v);
+    S->vid_of[nv.key] = vid;
+    S->vindex.emplace_back();
+    S->node_of.push_back(-1);
+    S->replaced.push_back(0);
+    vals[nv.type].insert(vals[nv.type].end(), nv.v, nv.v + kVarStore[nv.type]);
+    xoffs[nv.type].push_back(v.xoff);
+    S->ntot += kVarDim[nv.type];
+  }
+  for (int t = 0; t < kNumVarTypes; t++) {
+    if (xoffs[t].empty()) continue;
+    if ((rc = is_push(S, S->theta[t] + (size_t)first_tidx[t] * kVarStore[t], vals[t].data(), vals[t].size() * sizeof(double)))) return rc;
+    if ((rc = is_push(S, S->d_type_xoff[t] + first_tidx[t], xoffs[t].data(), xoffs[t].size() * sizeof(int32_t)))) return rc;
+  }
+  // delta_.insert(zeroVectors): a byte-fill record of the next flush (a fill command of its own was one more device operation per update).
+  // (The all-ones fill a walk pushes over the same scalars must not ride the same flush: two records of one scatter launch are not
+  // ordered.  The linearization of the new factors flushes in between; is_walk_prepare flushes itself if it did not.)
+  S->delta_zero_pending = true;
+  S->pushes.push_back(lmgpu_isam2::PushRec{S->delta + ntot0, (const void*)(uintptr_t)0, (uint32_t)((size_t)(S->ntot - ntot0) * sizeof(double)), 2u});
+  if (S->dogleg) {  // deltaNewton_ / RgProd_.insert(zeroVectors) (ISAM2.cpp:373-374)
+    ISCHECK(hipMemsetAsync(S->delta_newton + ntot0, 0, (size_t)(S->ntot - ntot0) * sizeof(double), S->stream));
+    ISCHECK(hipMemsetAsync(S->rgprod + ntot0, 0, (size_t)(S->ntot - ntot0) * sizeof(double), S->stream));
+  }
+  return LMGPU_OK;
+}
+
+// updateDelta in front of the relinearization check (ISAM2.cpp:438-440), with delta brought to the pinned host copy
+int is_delta_for_relin_check(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up) {
+  // delta and the host's mirror of it are current when nothing was re-eliminated since the last walk (the previous update ended with
+  // it): updateDelta would visit the roots and find nothing to do
+  const bool current = !S->dogleg && !S->any_replaced && !up.force_full_solve && S->mirror_ntot > 0 && (size_t)S->ntot <= S->h_delta_cap;
+  if (!current) return is_update_delta(S, up.force_full_solve, true);
+  for (size_t i = S->mirror_ntot; i < (size_t)S->ntot; i++) S->h_delta[i] = 0.0;  // delta_.insert(zeroVectors)
+  S->mirror_ntot = (size_t)S->ntot;
+  return LMGPU_OK;
+}
+
+// the bucket (factor type, noise kind, robust loss) of new factor nf; a new one when it is the first of its kind
+int is_bucket_of(lmgpu_isam2* S, const lmgpu_isam2::NewFac& nf) {
+  int bi = -1;
+  for (size_t b = 0; b < S->bkts.size(); b++)
+    if (S->bkts[b].type == nf.type && S->bkts[b].noise_kind == nf.noise_kind && S->bkts[b].robust == nf.robust && S->bkts[b].rk == nf.rk) bi = (int)b;
+  if (bi >= 0) return bi;
+  lmgpu_isam2::Bkt b;
+  b.type = nf.type;
+  b.noise_kind = nf.noise_kind;
+  b.robust = nf.robust;
+  b.rk = nf.rk;
+  b.rows = kFactorRows[nf.type];
+  b.ar = kFactorArity[nf.type];
+  b.ml = kFactorMeas[nf.type];
+  b.nl = nf.noise_kind == LMGPU_N_DIAG ? b.rows : (nf.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
+  b.cols = 1;
+  for (int k = 0; k < b.ar; k++) b.cols += kVarDim[factor_var_type(nf.type, k)];
+  S->bkts.push_back(b);
+  return (int)S->bkts.size() - 1;
+}
+// grow a full bucket: its descriptor arrays and its Jacobian region in the pool
+int is_grow_bucket(lmgpu_isam2* S, lmgpu_isam2::Bkt& b) {
+  const size_t ncap = std::max<size_t>(64, (size_t)b.cap * 2);
   int rc;
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = S->trace ? now() : 0.0;
-  auto lap = [&](int i) {
-    if (!S->trace) return;
-    const double t = now();
-    S->t_phase[i] += t - t_last;
-    if (t - t_last > 0.02) std::fprintf(stderr, "isam2 update %d: phase %d took %.1f ms\n", S->update_count, i, 1e3 * (t - t_last));
-    t_last = t;
-  };
-  if ((rc = is_stage_begin(S))) return rc;
-  S->elim_pending = false;
-  // ---- addVariables :365-384
-  for (const lmgpu_isam2::NewVar& nv : S->new_vars)
-    if (S->vid_of.count(nv.key)) {
-      S->err = "ISAM2: variable already exists";
-      return LMGPU_INVALID;
-    }
-  std::vector<lmgpu_isam2::NewVar> new_vars;
-  new_vars.swap(S->new_vars);
-  std::vector<lmgpu_isam2::NewFac> new_facs;
-  new_facs.swap(S->new_facs);
-  if (!new_vars.empty()) {
-    int add[kNumVarTypes] = {}, addtot = 0;
-    for (auto& nv : new_vars) {
-      add[nv.type]++;
-      addtot += kVarDim[nv.type];
-    }
-    for (int t = 0; t < kNumVarTypes; t++) {
-      const size_t need = (size_t)(S->type_count[t] + add[t]);
-      if (!add[t] || need <= (size_t)S->type_cap[t]) continue;
-      const size_t ncap = is_next_cap((size_t)S->type_cap[t], need);
-      if ((rc = is_realloc(S, &S->theta[t], ncap * kVarStore[t], (size_t)S->type_count[t] * kVarStore[t]))) return rc;
-      if ((rc = is_realloc(S, &S->est[t], ncap * kVarStore[t], 0))) return rc;
-      if ((rc = is_realloc(S, &S->d_type_xoff[t], ncap, (size_t)S->type_count[t]))) return rc;
-      S->type_cap[t] = (int)ncap;
-    }
-    if (S->ntot + addtot > S->ntot_cap) {
-      const size_t ncap = is_next_cap((size_t)S->ntot_cap, (size_t)(S->ntot + addtot));
-      if ((rc = is_realloc(S, &S->delta, ncap, (size_t)S->ntot))) return rc;
-      if (S->dogleg) {
-        if ((rc = is_realloc(S, &S->delta_newton, ncap, (size_t)S->ntot)) || (rc = is_realloc(S, &S->rgprod, ncap, (size_t)S->ntot)) ||
-            (rc = is_realloc(S, &S->grad, ncap, 0)) || (rc = is_realloc(S, &S->dx_u, ncap, 0)))
-          return rc;
-      }
-      if ((rc = is_realloc(S, &S->ones, ncap, 0))) return rc;
-      if ((rc = is_realloc(S, &S->d_replaced, ncap, (size_t)S->ntot))) return rc;
-      if ((rc = is_realloc(S, &S->d_changed, ncap, 0))) return rc;
-      ISCHECK(hipMemsetAsync(S->d_changed, 0, ncap, S->stream));  // (epochs: a fresh array must not hold the current one)
-      std::vector<double> one(ncap, 1.0);
-      ISCHECK(hipMemcpy(S->ones, one.data(), ncap * sizeof(double), hipMemcpyHostToDevice));
-      ISCHECK(hipMemsetAsync(S->d_replaced + S->ntot, 0, ncap - S->ntot, S->stream));
-      S->ntot_cap = (int)ncap;
-    }
-    // the new variables of a type take consecutive places: one copy per type for the values, one for the delta offsets
-    const int ntot0 = S->ntot;
-    int first_tidx[kNumVarTypes];
-    std::vector<double> vals[kNumVarTypes];
-    std::vector<int32_t> xoffs[kNumVarTypes];
-    for (int t = 0; t < kNumVarTypes; t++) first_tidx[t] = S->type_count[t];
-    for (auto& nv : new_vars) {
-      lmgpu_isam2::Var v{nv.key, nv.type, S->type_count[nv.type]++, S->ntot, false};
-      const int vid = (int)S->vars.size();
-      S->vars.push_back(v);
-      S->vid_of[nv.key] = vid;
-      S->vindex.emplace_back();
-      S->node_of.push_back(-1);
-      S->replaced.push_back(0);
-      vals[nv.type].insert(vals[nv.type].end(), nv.v, nv.v + kVarStore[nv.type]);
-      xoffs[nv.type].push_back(v.xoff);
-      S->ntot += kVarDim[nv.type];
-    }
-    for (int t = 0; t < kNumVarTypes; t++) {
-      if (xoffs[t].empty()) continue;
-      if ((rc = is_push(S, S->theta[t] + (size_t)first_tidx[t] * kVarStore[t], vals[t].data(), vals[t].size() * sizeof(double)))) return rc;
-      if ((rc = is_push(S, S->d_type_xoff[t] + first_tidx[t], xoffs[t].data(), xoffs[t].size() * sizeof(int32_t)))) return rc;
-    }
-    // delta_.insert(zeroVectors): a byte-fill record of the next flush (a fill command of its own was one more device operation per update).
-    // (The all-ones fill a walk pushes over the same scalars must not ride the same flush: two records of one scatter launch are not
-    // ordered.  The linearization of the new factors flushes in between; is_walk_prepare flushes itself if it did not.)
-    S->delta_zero_pending = true;
-    S->pushes.push_back(lmgpu_isam2::PushRec{S->delta + ntot0, (const void*)(uintptr_t)0, (uint32_t)((size_t)(S->ntot - ntot0) * sizeof(double)), 2u});
-    if (S->dogleg) {  // deltaNewton_ / RgProd_.insert(zeroVectors) (ISAM2.cpp:373-374)
-      ISCHECK(hipMemsetAsync(S->delta_newton + ntot0, 0, (size_t)(S->ntot - ntot0) * sizeof(double), S->stream));
-      ISCHECK(hipMemsetAsync(S->rgprod + ntot0, 0, (size_t)(S->ntot - ntot0) * sizeof(double), S->stream));
-    }
+  if ((rc = is_realloc(S, &b.d_vidx, ncap * b.ar, (size_t)b.n * b.ar))) return rc;
+  if ((rc = is_realloc(S, &b.d_epos, ncap, (size_t)b.n))) return rc;
+  if ((rc = is_realloc(S, &b.d_meas, ncap * b.ml, (size_t)b.n * b.ml))) return rc;
+  if ((rc = is_realloc(S, &b.d_noise, ncap * std::max(1, b.nl), (size_t)b.n * b.nl))) return rc;
+  int64_t noff;
+  if ((rc = is_pool_alloc(S, ncap * b.rows * b.cols, &noff))) return rc;
+  if (b.joff >= 0) {
+    ISCHECK(hipMemcpyAsync(S->pool + noff, S->pool + b.joff, (size_t)b.n * b.rows * b.cols * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
+    ISCHECK(hipStreamSynchronize(S->stream));
+    is_pool_free(S, b.joff, (size_t)b.cap * b.rows * b.cols);
   }
-  const bool relinNeeded = force_relinearize || (S->prm.enableRelinearization && S->prm.relinearizeSkip > 0 && S->update_count % S->prm.relinearizeSkip == 0);
-  const bool reads_before = S->delta_reads > 0;
-  S->delta_reads = 0;
-  if (relinNeeded) {
-    // delta and the host's mirror of it are current when nothing was re-eliminated since the last walk (the previous update ended with
-    // it): updateDelta would visit the roots and find nothing to do
-    const bool current = !S->dogleg && !S->any_replaced && !up.force_full_solve && S->mirror_ntot > 0 && (size_t)S->ntot <= S->h_delta_cap;
-    if (current) {
-      for (size_t i = S->mirror_ntot; i < (size_t)S->ntot; i++) S->h_delta[i] = 0.0;  // delta_.insert(zeroVectors)
-      S->mirror_ntot = (size_t)S->ntot;
-    } else if ((rc = is_update_delta(S, up.force_full_solve, true))) {
-      return rc;
-    }
-  }
-  const int relin_ntot = S->ntot;  // scalars of delta the pinned copy holds
-  lap(0);  // new variables + updateDelta (wildfire, one wait)
-  // ---- 1. pushBackFactors (ISAM2-impl.h:145-175): FactorGraph::add_factors (FactorGraph-inst.h:109-137) -- the indices continue the list,
-  //         or (findUnusedFactorSlots) the new factors fill the empty slots from the front
-  std::vector<int32_t> new_idx;
+  b.joff = noff;
+  b.cap = (int)ncap;
+  return LMGPU_OK;
+}
+// the descriptor rows of a bucket's new factors (consecutive local indices), uploaded once all of them are known
+struct NewRows {
+  int first = -1;
+  std::vector<int32_t> vidx, epos;
+  std::vector<double> meas, noise;
+};
+// UpdateImpl::pushBackFactors (ISAM2-impl.h:145-175): the new factors enter the graph in the slots FactorGraph::add_factors gives them
+// (is_take_slot), their keys are marked (:199-228); removeFactorIndices leave it
+int is_push_back_factors(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, UpdateWork& W) {
   size_t slot_scan = 0;
-  std::set<uint64_t> markedKeys;
-  std::map<int, std::vector<int32_t>> new_by_bucket;  // bucket -> new local indices
-  struct NewRows {
-    int first = -1;
-    std::vector<int32_t> vidx, epos;
-    std::vector<double> meas, noise;
-  };
-  std::map<int, NewRows> new_rows;  // bucket -> the descriptor rows of its new factors (consecutive local indices), uploaded after the loop
-  for (const lmgpu_isam2::NewFac& nf : new_facs) {
+  std::map<int, NewRows> new_rows;
+  int rc;
+  for (const lmgpu_isam2::NewFac& nf : W.new_facs) {
     const int ar = kFactorArity[nf.type];
     lmgpu_isam2::Fac f{nf.type, -1, -1, {-1, -1, -1}, false, -1};
-    size_t slot = S->facs.size();
-    if (S->find_unused_slots) {
-      while (slot_scan < S->facs.size() && !S->facs[slot_scan].removed) ++slot_scan;
-      slot = slot_scan;
-    }
+    const size_t slot = is_take_slot(S, &slot_scan);
     for (int k = 0; k < ar; k++) {
-      auto it = S->vid_of.find(nf.k[k]);
-      if (it == S->vid_of.end()) {
-        S->err = "ISAM2: a new factor references a variable that has no value";
-        return LMGPU_INVALID;
-      }
-      const int want = factor_var_type(nf.type, k);
-      if (S->vars[it->second].type != want) {
-        S->err = "factor/variable type mismatch";
-        return LMGPU_INVALID;
-      }
-      f.v[k] = it->second;
-      markedKeys.insert(nf.k[k]);  // 3. markedKeys = keys of the new factors (:199-228)
+      f.v[k] = S->vid_of.at(nf.k[k]);  // (known and of the right type: is_check_update)
+      W.markedKeys.insert(nf.k[k]);
     }
-    int bi = -1;
-    for (size_t b = 0; b < S->bkts.size(); b++)
-      if (S->bkts[b].type == nf.type && S->bkts[b].noise_kind == nf.noise_kind && S->bkts[b].robust == nf.robust && S->bkts[b].rk == nf.rk) bi = (int)b;
-    if (bi < 0) {
-      lmgpu_isam2::Bkt b;
-      b.type = nf.type;
-      b.noise_kind = nf.noise_kind;
-      b.robust = nf.robust;
-      b.rk = nf.rk;
-      b.rows = kFactorRows[nf.type];
-      b.ar = ar;
-      b.ml = kFactorMeas[nf.type];
-      b.nl = nf.noise_kind == LMGPU_N_DIAG ? b.rows : (nf.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
-      b.cols = 1;
-      for (int k = 0; k < ar; k++) b.cols += kVarDim[factor_var_type(nf.type, k)];
-      bi = (int)S->bkts.size();
-      S->bkts.push_back(b);
-    }
+    const int bi = is_bucket_of(S, nf);
     lmgpu_isam2::Bkt& b = S->bkts[bi];
-    if (b.n + 1 > b.cap) {  // grow the bucket: descriptor arrays and its Jacobian region in the pool
-      const size_t ncap = std::max<size_t>(64, (size_t)b.cap * 2);
-      if ((rc = is_realloc(S, &b.d_vidx, ncap * b.ar, (size_t)b.n * b.ar))) return rc;
-      if ((rc = is_realloc(S, &b.d_epos, ncap, (size_t)b.n))) return rc;
-      if ((rc = is_realloc(S, &b.d_meas, ncap * b.ml, (size_t)b.n * b.ml))) return rc;
-      if ((rc = is_realloc(S, &b.d_noise, ncap * std::max(1, b.nl), (size_t)b.n * b.nl))) return rc;
-      int64_t noff;
-      if ((rc = is_pool_alloc(S, ncap * b.rows * b.cols, &noff))) return rc;
-      if (b.joff >= 0) {
-        ISCHECK(hipMemcpyAsync(S->pool + noff, S->pool + b.joff, (size_t)b.n * b.rows * b.cols * sizeof(double), hipMemcpyDeviceToDevice, S->stream));
-        ISCHECK(hipStreamSynchronize(S->stream));
-        is_pool_free(S, b.joff, (size_t)b.cap * b.rows * b.cols);
-      }
-      b.joff = noff;
-      b.cap = (int)ncap;
-    }
+    if (b.n + 1 > b.cap && (rc = is_grow_bucket(S, b))) return rc;
     NewRows& nr = new_rows[bi];
     if (nr.first < 0) nr.first = b.n;
     for (int k = 0; k < ar; k++) nr.vidx.push_back(S->vars[f.v[k]].tidx);
@@ -2150,12 +2170,9 @@ int is_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, lmgpu_isam2_resul
     if (b.nl) nr.noise.insert(nr.noise.end(), nf.noise.begin(), nf.noise.begin() + b.nl);
     f.bucket = bi;
     f.lidx = b.n++;
-    new_by_bucket[bi].push_back(f.lidx);
-    if (slot == S->facs.size())
-      S->facs.push_back(f);
-    else
-      S->facs[slot] = f;
-    new_idx.push_back((int32_t)slot);
+    W.new_by_bucket[bi].push_back(f.lidx);
+    is_put_factor(S, slot, f);
+    W.new_idx.push_back((int32_t)slot);
   }
   for (auto& kv : new_rows) {  // (a bucket that grew in the loop moved its old rows only; the new ones arrive here)
     lmgpu_isam2::Bkt& b = S->bkts[kv.first];
@@ -2165,320 +2182,523 @@ int is_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, lmgpu_isam2_resul
     if ((rc = is_push(S, b.d_meas + (size_t)nr.first * b.ml, nr.meas.data(), nr.meas.size() * sizeof(double)))) return rc;
     if (b.nl && (rc = is_push(S, b.d_noise + (size_t)nr.first * b.nl, nr.noise.data(), nr.noise.size() * sizeof(double)))) return rc;
   }
-  // the removals of pushBackFactors (ISAM2-impl.h:157-172): the slot empties, the variable index forgets the factor
-  std::set<uint64_t> keysWithRemoved, newFactorKeys = markedKeys, unusedKeys;
+  // the removals (:157-172), then computeUnusedKeys (:175-190): keys whose last factor went and which no new factor mentions
   for (uint64_t idx : up.remove) {
-    lmgpu_isam2::Fac& f = S->facs[idx];
-    if (f.removed) continue;
-    for (int32_t v : is_fac_vids(S, f)) {
-      keysWithRemoved.insert(S->vars[v].key);
-      std::vector<int32_t>& entries = S->vindex[v];
-      entries.erase(std::find(entries.begin(), entries.end(), (int32_t)idx));
-    }
-    if ((rc = is_empty_slot(S, (int32_t)idx))) return rc;
+    if (S->facs[idx].removed) continue;
+    for (int32_t v : is_fac_vids(S, S->facs[idx])) W.keysWithRemoved.insert(S->vars[v].key);
+    if ((rc = is_forget_factor(S, (int32_t)idx))) return rc;
   }
-  // computeUnusedKeys (:175-190): keys whose last factor went and which no new factor mentions
-  for (uint64_t k : keysWithRemoved)
-    if (S->vindex[S->vid_of.at(k)].empty() && !newFactorKeys.count(k)) unusedKeys.insert(k);
+  for (uint64_t k : W.keysWithRemoved)
+    if (S->vindex[S->vid_of.at(k)].empty() && !W.markedKeys.count(k)) W.unusedKeys.insert(k);
+  return LMGPU_OK;
+}
+// UpdateImpl::gatherRelinearizeKeys (ISAM2-impl.h:367-399) on the pinned copy of delta (is_delta_for_relin_check brought it to the host;
+// variables added by this update are not in it: delta = 0).  LMGPU_INVALID: a threshold vector is missing or of the wrong dimension.
+int is_gather_relinearize_keys(const lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, const UpdateWork& W, std::set<int32_t>* relin) {
+  const double* hdelta = S->h_delta;
+  // above(): double -> infinity norm >= threshold (:287, 361); FastMap<char, Vector> -> any |delta_i| > threshold_i of the vector
+  // registered for the key's Symbol character (:252-268, 365-377)
+  bool bad_threshold = false;
+  auto above = [&](int32_t v) {
+    const lmgpu_isam2::Var& var = S->vars[v];
+    const int dim = kVarDim[var.type];
+    if (var.xoff >= W.relin_ntot) return false;  // added by this update: delta = 0 (never above a positive threshold; see below for 0)
+    if (up.force_full_solve) return true;
+    if (S->relin_thresholds.empty()) {
+      double m = 0;
+      for (int d = 0; d < dim; d++) m = std::max(m, std::fabs(hdelta[var.xoff + d]));
+      return m >= S->prm.relinearizeThreshold;
+    }
+    auto it = S->relin_thresholds.find((unsigned char)(var.key >> 56));
+    if (it == S->relin_thresholds.end() || (int)it->second.size() != dim) {
+      bad_threshold = true;
+      return false;
+    }
+    for (int d = 0; d < dim; d++)
+      if (std::fabs(hdelta[var.xoff + d]) > it->second[d]) return true;
+    return false;
+  };
+  std::set<int32_t> cand;
+  if (S->partial_relin_check && !up.force_full_solve) {
+    // CheckRelinearizationPartial :246-331: from the roots down, every key of a clique's conditional (frontals and parents) is
+    // checked, the children only when one of them was above its threshold
+    std::vector<int32_t> stack(S->roots.rbegin(), S->roots.rend());
+    while (!stack.empty()) {
+      const lmgpu_isam2::Clq& c = S->clq[stack.back()];
+      stack.pop_back();
+      bool any = false;
+      for (int32_t v : c.vars)
+        if (above(v)) {
+          cand.insert(v);
+          any = true;
+        }
+      if (any)
+        for (auto ch = c.children.rbegin(); ch != c.children.rend(); ++ch) stack.push_back(*ch);
+    }
+  } else {  // CheckRelinearizationFull :353-383
+    for (size_t v = 0; v < S->vars.size(); v++)
+      if (!S->vars[v].dead && above((int32_t)v)) cand.insert((int32_t)v);
+  }
+  if (bad_threshold) return LMGPU_INVALID;
+  const std::set<uint64_t> noRelin(up.no_relin.begin(), up.no_relin.end());
+  for (int32_t v : cand)  // minus the keys whose linearization point is fixed (marginal factors) and the caller's noRelinKeys (ISAM2-impl.h:385-392)
+    if (!noRelin.count(S->vars[v].key) && !S->fixed.count(S->vars[v].key)) relin->insert(v);
+  return LMGPU_OK;
+}
+// UpdateImpl::findFluid (ISAM2-impl.h:431-451): the frontals of the cliques whose separator holds a relinearized variable are marked
+void is_find_fluid(const lmgpu_isam2* S, const std::set<int32_t>& relin, std::set<uint64_t>* markedKeys) {
+  for (const lmgpu_isam2::Clq& c : S->clq) {
+    if (!c.alive) continue;
+    bool found = false;
+    for (size_t k = c.nfv; k < c.vars.size() && !found; k++) found = relin.count(c.vars[k]) > 0;
+    if (found)
+      for (int k = 0; k < c.nfv; k++) markedKeys->insert(S->vars[c.vars[k]].key);
+  }
+}
+// theta_.retractMasked(delta_, relinKeys) (ISAM2.cpp:465) on the device: one launch for all the types
+int is_retract_masked(lmgpu_isam2* S, const UpdateWork& W) {
+  std::vector<int32_t> sel[kNumVarTypes];
+  for (int32_t v : W.relin) sel[S->vars[v].type].push_back(S->vars[v].tidx);
+  RetractMulti rm{};
+  int ne = 0, maxn = 0, rc;
+  for (int t = 0; t < kNumVarTypes; t++) {
+    if (sel[t].empty()) continue;
+    int32_t* d = nullptr;
+    if ((rc = is_stage(S, sel[t], &d))) return rc;
+    rm.type[ne] = t;
+    rm.n[ne] = (int)sel[t].size();
+    rm.cur[ne] = S->theta[t];
+    rm.out[ne] = S->theta[t];
+    rm.xoff[ne] = S->d_type_xoff[t];
+    rm.sel[ne] = d;
+    maxn = std::max(maxn, (int)sel[t].size());
+    ne++;
+  }
+  if (ne == 0) return LMGPU_OK;
+  if ((rc = is_flush(S))) return rc;
+  hipLaunchKernelGGL(retract_multi_kernel, dim3((maxn + 255) / 256, ne), dim3(256), 0, S->stream, rm, (const double*)S->delta);
+  return LMGPU_OK;
+}
+// steps 4-6 of ISAM2::update (ISAM2.cpp:452-466): relinKeys, the fluid cliques' frontals marked too, theta moved on the relinKeys
+int is_relinearize(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, UpdateWork& W) {
+  if (is_gather_relinearize_keys(S, up, W, &W.relin)) {
+    S->err = "ISAM2: relinearization threshold vector missing for a Symbol character or of the wrong dimension (ISAM2-impl.h:258-262)";
+    return LMGPU_INVALID;
+  }
+  for (int32_t v : W.relin) W.markedKeys.insert(S->vars[v].key);
+  if (!W.relin.empty()) {
+    is_find_fluid(S, W.relin, &W.markedKeys);
+    const int rc = is_retract_masked(S, W);
+    if (rc) return rc;
+  }
+  W.res.variablesRelinearized = (int32_t)W.markedKeys.size();
+  return LMGPU_OK;
+}
+// linearizeNewFactors (ISAM2.cpp:454-468) into the linearization cache + augmentVariableIndex
+int is_linearize_new_factors(lmgpu_isam2* S, const UpdateWork& W) {
+  const std::vector<std::pair<int, std::vector<int32_t>>> jobs(W.new_by_bucket.begin(), W.new_by_bucket.end());
+  const int rc = is_linearize_jobs(S, jobs);
+  if (rc) return rc;
+  for (int32_t i : W.new_idx)
+    for (int k = 0; k < kFactorArity[S->facs[i].type]; k++) S->vindex[S->facs[i].v[k]].push_back(i);
+  return LMGPU_OK;
+}
+
+// deltaReplacedMask_ |= affectedKeysSet (ISAM2.cpp:172): byte fills carried by the scatter kernel of the flush in front of the elimination
+void is_push_marks(lmgpu_isam2* S, const std::set<int32_t>& affectedSet, const std::set<uint64_t>& unusedKeys) {
+  for (int32_t v : affectedSet) {
+    if (unusedKeys.count(S->vars[v].key)) continue;  // leaves the system (is_retire_variable)
+    S->replaced[v] = 1;
+    S->pushes.push_back(lmgpu_isam2::PushRec{S->d_replaced + S->vars[v].xoff, (const void*)(uintptr_t)S->epoch, (uint32_t)kVarDim[S->vars[v].type], 2u});
+  }
+}
+// ISAM2::recalculateBatch (ISAM2.cpp:178-247): reorder, relinearize and re-eliminate everything
+int is_recalculate_batch(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, UpdateWork& W) {
+  W.res.batch = 1;
+  for (int id = 0; id < (int)S->clq.size(); id++)
+    if (S->clq[id].alive) is_release_clique(S, id);
+  S->roots.clear();
+  std::fill(S->node_of.begin(), S->node_of.end(), -1);
+  std::vector<int32_t> vids;
+  for (auto& kv : S->vid_of)  // the keys of variableIndex_ (ISAM2.cpp:186-190): a variable that has a value but no factor yet stays out of the tree
+    if (!W.unusedKeys.count(kv.first) && !S->vindex[kv.second].empty()) vids.push_back(kv.second);
+  std::vector<std::vector<int32_t>> cols;
+  for (int32_t v : vids) cols.push_back(S->vindex[v]);
+  std::map<int32_t, int> groups;
+  if (up.has_constrained) {
+    for (auto& kg : up.constrained) {
+      if (W.unusedKeys.count(kg.first)) {  // (that it names a variable at all: is_check_update; that the variable leaves with this update shows here)
+        S->err = "ISAM2: constrainedKeys names a variable that is not in the system";
+        return LMGPU_INVALID;
+      }
+      groups[S->vid_of.at(kg.first)] = kg.second;
+    }
+  } else if (S->vid_of.size() > W.observed.size()) {
+    for (int32_t v : W.observed) groups[v] = 1;
+  }
+  std::vector<int32_t> perm;
+  int rc;
+  is_lap(S, 2);
+  if ((rc = is_colamd(S, vids, cols, (int)S->facs.size(), groups, &perm))) return rc;
+  is_lap(S, 3);
+  std::vector<std::pair<int, std::vector<int32_t>>> jobs;
+  for (size_t b = 0; b < S->bkts.size(); b++) {
+    std::vector<int32_t> all(S->bkts[b].n);
+    for (int i = 0; i < S->bkts[b].n; i++) all[i] = i;
+    jobs.emplace_back((int)b, std::move(all));
+  }
+  if ((rc = is_linearize_jobs(S, jobs))) return rc;
+  std::vector<IsGF> gfs(S->facs.size());
+  for (size_t i = 0; i < S->facs.size(); i++) {
+    gfs[i].kind = 0;
+    gfs[i].id = (int32_t)i;
+    if (S->facs[i].removed) continue;  // an empty slot: an entry without variables, so that positions stay factor indices
+    if (S->facs[i].marg >= 0) gfs[i].kind = 3;
+    gfs[i].vids = is_fac_vids(S, S->facs[i]);
+  }
+  is_lap(S, 1);  // (batch: relinearization of everything counts with the linearize phase)
+  is_push_marks(S, std::set<int32_t>(vids.begin(), vids.end()), W.unusedKeys);
+  if ((rc = is_eliminate(S, gfs, vids, perm, &cols))) return rc;  // (variableIndex_ as it stands: GaussianEliminationTree(*linearized, affectedFactorsVarIndex, order))
+  is_lap(S, 4);
+  W.res.variablesReeliminated = (int32_t)vids.size();
+  W.res.factorsRecalculated = (int32_t)S->facs.size();
+  S->any_replaced = S->any_replaced || !vids.empty();
+  return LMGPU_OK;
+}
+// UpdateImpl::relinearizeAffectedFactors (ISAM2-impl.h:66-114): the factors that only involve the variables `inSet` enter *gfs, with their
+// cached linearization unless a relinKey is among their variables (those are linearized again)
+int is_relinearize_affected_factors(lmgpu_isam2* S, const UpdateWork& W, const std::vector<int32_t>& affectedAndNew, std::vector<IsGF>* gfs) {
+  const std::set<int32_t> inSet(affectedAndNew.begin(), affectedAndNew.end());
+  std::set<int32_t> candidates;
+  for (int32_t v : affectedAndNew)
+    for (int32_t f : S->vindex[v]) candidates.insert(f);
+  std::map<int, std::vector<int32_t>> relin_by_bucket;
+  for (int32_t idx : candidates) {
+    const lmgpu_isam2::Fac& f = S->facs[idx];
+    bool inside = true, useCached = true;
+    IsGF g;
+    g.vids = is_fac_vids(S, f);
+    for (int32_t v : g.vids) {
+      if (!inSet.count(v)) {
+        inside = false;
+        break;
+      }
+      if (W.relin.count(v)) useCached = false;
+    }
+    if (!inside) continue;
+    if (!useCached && f.marg < 0) relin_by_bucket[f.bucket].push_back(f.lidx);  // (a marginal factor linearizes to itself)
+    g.kind = f.marg >= 0 ? 3 : 0;
+    g.id = idx;
+    gfs->push_back(std::move(g));
+  }
+  const std::vector<std::pair<int, std::vector<int32_t>>> jobs(relin_by_bucket.begin(), relin_by_bucket.end());
+  return is_linearize_jobs(S, jobs);
+}
+// ISAM2::recalculateIncremental (ISAM2.cpp:250-362); affected = the frontals of the conditionals removeTop took out, orphans = what hung below
+int is_recalculate_incremental(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, UpdateWork& W, const std::vector<int32_t>& affected,
+                               const std::list<int>& orphans) {
+  std::vector<int32_t> affectedAndNew = affected;
+  affectedAndNew.insert(affectedAndNew.end(), W.observed.begin(), W.observed.end());
+  std::vector<IsGF> gfs;
+  int rc;
+  if ((rc = is_relinearize_affected_factors(S, W, affectedAndNew, &gfs))) return rc;
+  W.res.variablesReeliminated = (int32_t)affectedAndNew.size();
+  W.res.factorsRecalculated = (int32_t)gfs.size();
+  for (int kind = 1; kind <= 2; kind++)  // GetCachedBoundaryFactors (ISAM2-impl.h:499-509), then the orphan wrappers
+    for (int o : orphans) gfs.push_back(is_gf_of_clique(S, kind, o));
+  std::set<int32_t> affectedSet(affected.begin(), affected.end());
+  for (uint64_t k : W.markedKeys) affectedSet.insert(S->vid_of.at(k));
+  // VariableIndex of `gfs`, ascending by key
+  std::map<uint64_t, std::vector<int32_t>> vi;
+  for (size_t i = 0; i < gfs.size(); i++)
+    for (int32_t v : gfs[i].vids) vi[S->vars[v].key].push_back((int32_t)i);
+  std::vector<int32_t> vids;
+  std::vector<std::vector<int32_t>> cols;
+  for (auto& kv : vi) {
+    vids.push_back(S->vid_of.at(kv.first));
+    cols.push_back(kv.second);
+  }
+  std::map<int32_t, int> groups;  // constraint groups, minus unused / unaffected keys (ISAM2.cpp:318-340)
+  if (up.has_constrained) {
+    for (auto& kg : up.constrained) {
+      auto it = S->vid_of.find(kg.first);
+      if (it != S->vid_of.end() && !W.unusedKeys.count(kg.first) && affectedSet.count(it->second)) groups.emplace(it->second, kg.second);
+    }
+  } else {
+    const int group = W.observed.size() < vids.size() ? 1 : 0;
+    for (int32_t v : W.observed)
+      if (affectedSet.count(v)) groups.emplace(v, group);
+  }
+  std::vector<int32_t> perm;
+  is_lap(S, 2);  // removeTop, affected factors, variable index
+  if ((rc = is_colamd(S, vids, cols, (int)gfs.size(), groups, &perm))) return rc;
+  is_lap(S, 3);  // constrained COLAMD callback
+  is_push_marks(S, affectedSet, W.unusedKeys);
+  if ((rc = is_eliminate(S, gfs, vids, perm))) return rc;
+  is_lap(S, 4);  // symbolic elimination, tables, launches
+  S->any_replaced = S->any_replaced || !affectedSet.empty();
+  return LMGPU_OK;
+}
+// ISAM2::recalculate (ISAM2.cpp:117-175): removeTop of the marked keys, then everything again or the affected part
+int is_recalculate(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, UpdateWork& W) {
+  std::vector<int> bn;
+  std::list<int> orphans;
+  for (uint64_t k : W.markedKeys) {  // removeTop
+    const int node = S->node_of[S->vid_of.at(k)];
+    if (node >= 0) is_remove_path(S, node, &bn, &orphans);
+  }
+  std::vector<int32_t> affected;  // affectedKeys: frontals of the removed conditionals
+  for (int id : bn)
+    for (int k = 0; k < S->clq[id].nfv; k++) affected.push_back(S->clq[id].vars[k]);
+  for (int id : bn) is_release_clique(S, id);
+  if ((double)affected.size() >= (double)S->vid_of.size() * 0.65) return is_recalculate_batch(S, up, W);
+  return is_recalculate_incremental(S, up, W, affected, orphans);
+}
+
+// ISAM2::update (gtsam/nonlinear/ISAM2.cpp:419-483).  LMGPU_ISAM2_TRACE phases: 0 new variables + updateDelta (wildfire, one wait),
+// 1 new factors / relinearization check / retract / linearize, 2-4 inside recalculate, 5 marks + clique count, 6 the final wait
+int is_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, lmgpu_isam2_result* result) {
+  int rc;
+  if ((rc = is_check_update(S, up))) return rc;
+  S->update_count += 1;
+  is_lap(S, -1);
+  if ((rc = is_stage_begin(S))) return rc;
+  S->elim_pending = false;
+  UpdateWork W;
+  W.new_vars.swap(S->new_vars);
+  W.new_facs.swap(S->new_facs);
+  if ((rc = is_add_variables(S, W))) return rc;
+  W.relinNeeded = up.force_relinearize || (S->prm.enableRelinearization && S->prm.relinearizeSkip > 0 && S->update_count % S->prm.relinearizeSkip == 0);
+  W.reads_before = S->delta_reads > 0;
+  S->delta_reads = 0;
+  if (W.relinNeeded && (rc = is_delta_for_relin_check(S, up))) return rc;
+  W.relin_ntot = S->ntot;
+  is_lap(S, 0);
+  if ((rc = is_push_back_factors(S, up, W))) return rc;  // 1. + computeUnusedKeys
   // 2. errorBefore (ISAM2.cpp:444-446): the graph with the new factors at calculateEstimate(), which brings delta up to date first
   if (S->evaluate_error) {
     if (S->any_replaced && (rc = is_update_delta(S, false))) return rc;
     if ((rc = is_graph_error(S, true, &S->error_before))) return rc;
   }
-  // gatherInvolvedKeys (:199-226) + updateKeys (:228-244)
-  markedKeys.insert(keysWithRemoved.begin(), keysWithRemoved.end());
-  markedKeys.insert(up.extra_reelim.begin(), up.extra_reelim.end());
-  std::vector<int32_t> observed;  // observedKeys = the marked keys that stay in the system, ascending by key
-  for (uint64_t k : markedKeys)
-    if (!unusedKeys.count(k)) observed.push_back(S->vid_of.at(k));
-  std::set<int32_t> relin;  // relinKeys as vids
-  if (relinNeeded) {
-    // ---- 4. CheckRelinearizationFull (:353-383) on the delta just updated
-    // (is_update_delta above brought delta to the host with its own wait; variables added by this update are not in it: delta = 0)
-    const double* hdelta = S->h_delta;
-    const int ntot_checked = relin_ntot;
-    // gatherRelinearizeKeys :367-399.  above(): double -> infinity norm >= threshold (:287, 361); FastMap<char, Vector> -> any
-    // |delta_i| > threshold_i of the vector registered for the key's Symbol character (:252-268, 365-377)
-    std::set<uint64_t> noRelin(up.no_relin.begin(), up.no_relin.end());
-    bool bad_threshold = false;
-    auto above = [&](int32_t v) {
-      const lmgpu_isam2::Var& var = S->vars[v];
-      const int dim = kVarDim[var.type];
-      if (var.xoff >= ntot_checked) return false;  // added by this update: delta = 0 (never above a positive threshold; see below for 0)
-      if (up.force_full_solve) return true;
-      if (S->relin_thresholds.empty()) {
-        double m = 0;
-        for (int d = 0; d < dim; d++) m = std::max(m, std::fabs(hdelta[var.xoff + d]));
-        return m >= S->prm.relinearizeThreshold;
-      }
-      auto it = S->relin_thresholds.find((unsigned char)(var.key >> 56));
-      if (it == S->relin_thresholds.end() || (int)it->second.size() != dim) {
-        bad_threshold = true;
-        return false;
-      }
-      for (int d = 0; d < dim; d++)
-        if (std::fabs(hdelta[var.xoff + d]) > it->second[d]) return true;
-      return false;
-    };
-    std::set<int32_t> cand;
-    if (S->partial_relin_check && !up.force_full_solve) {
-      // CheckRelinearizationPartial :246-331: from the roots down, every key of a clique's conditional (frontals and parents) is
-      // checked, the children only when one of them was above its threshold
-      std::vector<int32_t> stack(S->roots.rbegin(), S->roots.rend());
-      while (!stack.empty()) {
-        const lmgpu_isam2::Clq& c = S->clq[stack.back()];
-        stack.pop_back();
-        bool any = false;
-        for (int32_t v : c.vars)
-          if (above(v)) {
-            cand.insert(v);
-            any = true;
-          }
-        if (any)
-          for (auto ch = c.children.rbegin(); ch != c.children.rend(); ++ch) stack.push_back(*ch);
-      }
-    } else {
-      for (size_t v = 0; v < S->vars.size(); v++)
-        if (!S->vars[v].dead && above((int32_t)v)) cand.insert((int32_t)v);
-    }
-    if (bad_threshold) {
-      S->err = "ISAM2: relinearization threshold vector missing for a Symbol character or of the wrong dimension (ISAM2-impl.h:258-262)";
-      return LMGPU_INVALID;
-    }
-    for (int32_t v : cand)  // minus the keys whose linearization point is fixed (marginal factors) and the caller's noRelinKeys (ISAM2-impl.h:385-392)
-      if (!noRelin.count(S->vars[v].key) && !S->fixed.count(S->vars[v].key)) {
-        relin.insert(v);
-        markedKeys.insert(S->vars[v].key);
-      }
-    if (!relin.empty()) {
-      // ---- 5. findFluid (:431-451): cliques whose separator holds a relinearized variable
-      for (const lmgpu_isam2::Clq& c : S->clq) {
-        if (!c.alive) continue;
-        bool found = false;
-        for (size_t k = c.nfv; k < c.vars.size() && !found; k++) found = relin.count(c.vars[k]) > 0;
-        if (found)
-          for (int k = 0; k < c.nfv; k++) markedKeys.insert(S->vars[c.vars[k]].key);
-      }
-      // ---- 6. theta_.retractMasked(delta_, relinKeys) on the device
-      std::vector<int32_t> sel[kNumVarTypes];
-      for (int32_t v : relin) sel[S->vars[v].type].push_back(S->vars[v].tidx);
-      {  // one launch for all the types
-        RetractMulti rm{};
-        int ne = 0, maxn = 0;
-        for (int t = 0; t < kNumVarTypes; t++) {
-          if (sel[t].empty()) continue;
-          int32_t* d = nullptr;
-          if ((rc = is_stage(S, sel[t], &d))) return rc;
-          rm.type[ne] = t;
-          rm.n[ne] = (int)sel[t].size();
-          rm.cur[ne] = S->theta[t];
-          rm.out[ne] = S->theta[t];
-          rm.xoff[ne] = S->d_type_xoff[t];
-          rm.sel[ne] = d;
-          maxn = std::max(maxn, (int)sel[t].size());
-          ne++;
-        }
-        if (ne > 0) {
-          if ((rc = is_flush(S))) return rc;
-          hipLaunchKernelGGL(retract_multi_kernel, dim3((maxn + 255) / 256, ne), dim3(256), 0, S->stream, rm, (const double*)S->delta);
-        }
-      }
-    }
-    res.variablesRelinearized = (int32_t)markedKeys.size();
-  }
-  // ---- 7. linearizeNewFactors (:454-468) + augmentVariableIndex
-  {
-    std::vector<std::pair<int, std::vector<int32_t>>> jobs(new_by_bucket.begin(), new_by_bucket.end());
-    if ((rc = is_linearize_jobs(S, jobs))) return rc;
-  }
-  for (int32_t i : new_idx)
-    for (int k = 0; k < kFactorArity[S->facs[i].type]; k++) S->vindex[S->facs[i].v[k]].push_back(i);
-  lap(1);  // new factors, relinearization check, retract, linearize
-  // ---- 8. recalculate (ISAM2.cpp:117-175)
-  if (!markedKeys.empty()) {
-    std::vector<int> bn;
-    std::list<int> orphans;
-    for (uint64_t k : markedKeys) {  // removeTop
-      const int node = S->node_of[S->vid_of.at(k)];
-      if (node >= 0) is_remove_path(S, node, &bn, &orphans);
-    }
-    std::vector<int32_t> affected;  // affectedKeys: frontals of the removed conditionals
-    for (int id : bn)
-      for (int k = 0; k < S->clq[id].nfv; k++) affected.push_back(S->clq[id].vars[k]);
-    for (int id : bn) is_release_clique(S, id);
-
-    std::set<int32_t> affectedSet;
-    // deltaReplacedMask_ |= affectedKeysSet: byte fills carried by the scatter kernel of the flush in front of the elimination
-    auto push_marks = [&]() {
-      for (int32_t v : affectedSet) {
-        if (unusedKeys.count(S->vars[v].key)) continue;  // leaves the system below
-        S->replaced[v] = 1;
-        S->pushes.push_back(lmgpu_isam2::PushRec{S->d_replaced + S->vars[v].xoff, (const void*)(uintptr_t)S->epoch, (uint32_t)kVarDim[S->vars[v].type], 2u});
-      }
-    };
-    if ((double)affected.size() >= (double)S->vid_of.size() * 0.65) {
-      // ---- recalculateBatch :178-247: reorder, relinearize and re-eliminate everything
-      res.batch = 1;
-      for (int id = 0; id < (int)S->clq.size(); id++)
-        if (S->clq[id].alive) is_release_clique(S, id);
-      S->roots.clear();
-      std::fill(S->node_of.begin(), S->node_of.end(), -1);
-      std::vector<int32_t> vids;
-      for (auto& kv : S->vid_of)  // the keys of variableIndex_ (ISAM2.cpp:186-190): a variable that has a value but no factor yet stays out of the tree
-        if (!unusedKeys.count(kv.first) && !S->vindex[kv.second].empty()) vids.push_back(kv.second);
-      std::vector<std::vector<int32_t>> cols;
-      for (int32_t v : vids) cols.push_back(S->vindex[v]);
-      std::map<int32_t, int> groups;
-      if (up.has_constrained) {
-        for (auto& kg : up.constrained) {
-          auto it = S->vid_of.find(kg.first);
-          if (it == S->vid_of.end() || unusedKeys.count(kg.first)) {
-            S->err = "ISAM2: constrainedKeys names a variable that is not in the system";
-            return LMGPU_INVALID;
-          }
-          groups[it->second] = kg.second;
-        }
-      } else if (S->vid_of.size() > observed.size()) {
-        for (int32_t v : observed) groups[v] = 1;
-      }
-      std::vector<int32_t> perm;
-      lap(2);
-      if ((rc = is_colamd(S, vids, cols, (int)S->facs.size(), groups, &perm))) return rc;
-      lap(3);
-      {
-        std::vector<std::pair<int, std::vector<int32_t>>> jobs;
-        for (size_t b = 0; b < S->bkts.size(); b++) {
-          std::vector<int32_t> all(S->bkts[b].n);
-          for (int i = 0; i < S->bkts[b].n; i++) all[i] = i;
-          jobs.emplace_back((int)b, std::move(all));
-        }
-        if ((rc = is_linearize_jobs(S, jobs))) return rc;
-      }
-      std::vector<IsGF> gfs(S->facs.size());
-      for (size_t i = 0; i < S->facs.size(); i++) {
-        gfs[i].kind = 0;
-        gfs[i].id = (int32_t)i;
-        if (S->facs[i].removed) continue;  // an empty slot: an entry without variables, so that positions stay factor indices
-        if (S->facs[i].marg >= 0) gfs[i].kind = 3;
-        gfs[i].vids = is_fac_vids(S, S->facs[i]);
-      }
-      lap(1);  // (batch: relinearization of everything counts with the linearize phase)
-      for (int32_t v : vids) affectedSet.insert(v);
-      push_marks();
-      if ((rc = is_eliminate(S, gfs, vids, perm, &cols))) return rc;  // (variableIndex_ as it stands: GaussianEliminationTree(*linearized, affectedFactorsVarIndex, order))
-      lap(4);
-      res.variablesReeliminated = (int32_t)vids.size();
-      res.factorsRecalculated = (int32_t)S->facs.size();
-    } else {
-      // ---- recalculateIncremental :250-362
-      std::vector<int32_t> affectedAndNew = affected;
-      affectedAndNew.insert(affectedAndNew.end(), observed.begin(), observed.end());
-      const std::set<int32_t> inSet(affectedAndNew.begin(), affectedAndNew.end());
-      std::set<int32_t> candidates;  // relinearizeAffectedFactors :66-114
-      for (int32_t v : affectedAndNew)
-        for (int32_t f : S->vindex[v]) candidates.insert(f);
-      std::vector<IsGF> gfs;
-      std::map<int, std::vector<int32_t>> relin_by_bucket;
-      for (int32_t idx : candidates) {
-        const lmgpu_isam2::Fac& f = S->facs[idx];
-        bool inside = true, useCached = true;
-        IsGF g;
-        g.vids = is_fac_vids(S, f);
-        for (int32_t v : g.vids) {
-          if (!inSet.count(v)) {
-            inside = false;
-            break;
-          }
-          if (relin.count(v)) useCached = false;
-        }
-        if (!inside) continue;
-        if (!useCached && f.marg < 0) relin_by_bucket[f.bucket].push_back(f.lidx);  // (a marginal factor linearizes to itself)
-        g.kind = f.marg >= 0 ? 3 : 0;
-        g.id = idx;
-        gfs.push_back(std::move(g));
-      }
-      {
-        std::vector<std::pair<int, std::vector<int32_t>>> jobs(relin_by_bucket.begin(), relin_by_bucket.end());
-        if ((rc = is_linearize_jobs(S, jobs))) return rc;
-      }
-      res.variablesReeliminated = (int32_t)affectedAndNew.size();
-      res.factorsRecalculated = (int32_t)gfs.size();
-      for (int kind = 1; kind <= 2; kind++)  // GetCachedBoundaryFactors (ISAM2-impl.h:499-509), then the orphan wrappers
-        for (int o : orphans) {
-          IsGF g;
-          g.kind = kind;
-          g.id = o;
-          g.vids.assign(S->clq[o].vars.begin() + S->clq[o].nfv, S->clq[o].vars.end());
-          gfs.push_back(std::move(g));
-        }
-      for (uint64_t k : markedKeys) affectedSet.insert(S->vid_of.at(k));
-      for (int32_t v : affected) affectedSet.insert(v);
-      // VariableIndex of `gfs`, ascending by key
-      std::map<uint64_t, std::vector<int32_t>> vi;
-      for (size_t i = 0; i < gfs.size(); i++)
-        for (int32_t v : gfs[i].vids) vi[S->vars[v].key].push_back((int32_t)i);
-      std::vector<int32_t> vids;
-      std::vector<std::vector<int32_t>> cols;
-      for (auto& kv : vi) {
-        vids.push_back(S->vid_of.at(kv.first));
-        cols.push_back(kv.second);
-      }
-      std::map<int32_t, int> groups;  // constraint groups, minus unused / unaffected keys (ISAM2.cpp:318-340)
-      if (up.has_constrained) {
-        for (auto& kg : up.constrained) {
-          auto it = S->vid_of.find(kg.first);
-          if (it != S->vid_of.end() && !unusedKeys.count(kg.first) && affectedSet.count(it->second)) groups.emplace(it->second, kg.second);
-        }
-      } else {
-        const int group = observed.size() < vids.size() ? 1 : 0;
-        for (int32_t v : observed)
-          if (affectedSet.count(v)) groups.emplace(v, group);
-      }
-      std::vector<int32_t> perm;
-      lap(2);  // removeTop, affected factors, variable index
-      if ((rc = is_colamd(S, vids, cols, (int)gfs.size(), groups, &perm))) return rc;
-      lap(3);  // constrained COLAMD callback
-      push_marks();
-      if ((rc = is_eliminate(S, gfs, vids, perm))) return rc;
-      lap(4);  // symbolic elimination, tables, launches
-    }
-    S->any_replaced = S->any_replaced || !affectedSet.empty();
-  }
-  // ---- removeVariables (ISAM2.cpp:385-398): the variable leaves theta / delta / the variable index; its storage is not reused
-  for (uint64_t k : unusedKeys) {
-    const int32_t v = S->vid_of.at(k);
-    S->vars[v].dead = true;
-    if (S->dogleg) {  // the vectors of the dog leg are summed over all scalars: a retired variable must not count
-      const size_t o = (size_t)S->vars[v].xoff, nb = (size_t)kVarDim[S->vars[v].type] * sizeof(double);
-      ISCHECK(hipMemsetAsync(S->delta + o, 0, nb, S->stream));
-      ISCHECK(hipMemsetAsync(S->delta_newton + o, 0, nb, S->stream));
-      ISCHECK(hipMemsetAsync(S->rgprod + o, 0, nb, S->stream));
-    }
-    S->replaced[v] = 0;
-    S->node_of[v] = -1;
-    S->vid_of.erase(k);
-    S->fixed.erase(k);
-  }
-  S->last_unused.assign(unusedKeys.begin(), unusedKeys.end());
-  res.cliques = S->n_alive;  // (every alive clique hangs in the tree again by now; counting them by a walk was O(cliques) per update)
-  if (result) *result = res;
-  lap(5);
+  // 3. gatherInvolvedKeys (ISAM2-impl.h:199-226) + updateKeys (:228-244)
+  W.markedKeys.insert(W.keysWithRemoved.begin(), W.keysWithRemoved.end());
+  W.markedKeys.insert(up.extra_reelim.begin(), up.extra_reelim.end());
+  for (uint64_t k : W.markedKeys)
+    if (!W.unusedKeys.count(k)) W.observed.push_back(S->vid_of.at(k));
+  if (W.relinNeeded && (rc = is_relinearize(S, up, W))) return rc;  // 4. - 6.
+  if ((rc = is_linearize_new_factors(S, W))) return rc;             // 7.
+  is_lap(S, 1);
+  if (!W.markedKeys.empty() && (rc = is_recalculate(S, up, W))) return rc;  // 8.
+  for (uint64_t k : W.unusedKeys)  // removeVariables
+    if ((rc = is_retire_variable(S, S->vid_of.at(k)))) return rc;
+  S->last_unused.assign(W.unusedKeys.begin(), W.unusedKeys.end());
+  W.res.cliques = S->n_alive;  // (every alive clique hangs in the tree again by now; counting them by a walk was O(cliques) per update)
+  if (result) *result = W.res;
+  is_lap(S, 5);
+  // the update ends with the walk (behind its elimination, under the same wait) when delta is going to be asked for anyway (see delta_reads)
   bool walked = false;
   if (!S->dogleg && S->any_replaced && !dev_switch("LMGPU_ISAM2_NO_PREWALK")) {
     const bool next_relin = S->prm.enableRelinearization && S->prm.relinearizeSkip > 0 && (S->update_count + 1) % S->prm.relinearizeSkip == 0;
-    if (next_relin || reads_before) {
+    if (next_relin || W.reads_before) {
       if ((rc = is_update_delta_enqueue(S, false, next_relin))) return rc;
       walked = true;
     }
   }
   rc = is_finish_elimination(S);  // the one wait of an update
   if (rc == LMGPU_OK && walked) rc = is_update_delta_finish(S);  // (an indeterminate back-substitution is reported one call early)
-  lap(6);
+  is_lap(S, 6);
   if (rc == LMGPU_OK && S->evaluate_error) {  // errorAfter (ISAM2.cpp:481-483), again through calculateEstimate()
     if (S->any_replaced && (rc = is_update_delta(S, false))) return rc;
     rc = is_graph_error(S, true, &S->error_after);
   }
   return rc;
+}
+
+// ---- marginalizeLeaves: the plan (nothing changes), then the pieces of carrying it out
+struct MargAct {
+  bool whole;  // the clique goes with everything below it; else: its leading frontals go
+  int clique;
+  std::vector<int> subtrees;  // partial: the children that hang on a leaving variable
+};
+// The reference's loop (ISAM2.cpp:530-667) without touching anything: the acts, and in goneV every variable they take out of the tree.
+// LMGPU_INVALID: *not_leaf is a variable that cannot go (a variable that stays is eliminated before it).
+int is_plan_marginalize(const lmgpu_isam2* S, const std::set<uint64_t>& leafKeys, const std::set<int32_t>& leafV, std::vector<MargAct>* acts,
+                        std::set<int32_t>* goneV, int32_t* not_leaf) {
+  auto plan_subtree = [&](int root) -> int {  // every frontal below must leave too
+    std::vector<int> q{root};
+    for (size_t i = 0; i < q.size(); i++) {
+      const lmgpu_isam2::Clq& c = S->clq[q[i]];
+      for (int k = 0; k < c.nfv; k++) {
+        *not_leaf = c.vars[k];
+        if (!leafV.count(c.vars[k])) return LMGPU_INVALID;
+        goneV->insert(c.vars[k]);
+      }
+      q.insert(q.end(), c.children.begin(), c.children.end());
+    }
+    return LMGPU_OK;
+  };
+  int rc;
+  for (uint64_t key : leafKeys) {
+    const int32_t v = S->vid_of.at(key);
+    if (goneV->count(v)) continue;
+    int id = S->node_of[v];
+    while (S->clq[id].parent >= 0) {  // up to the root of the marginalized subtree: only the first variable of the parent needs a look
+      const int32_t pf = S->clq[S->clq[id].parent].vars[0];
+      if (leafV.count(pf) && !goneV->count(pf))
+        id = S->clq[id].parent;
+      else
+        break;
+    }
+    const lmgpu_isam2::Clq& c = S->clq[id];
+    int nleaf = 0;
+    for (int k = 0; k < c.nfv; k++) nleaf += leafV.count(c.vars[k]) && !goneV->count(c.vars[k]);
+    MargAct a{nleaf == c.nfv, id, {}};
+    if (a.whole) {
+      if ((rc = plan_subtree(id))) return rc;
+    } else {
+      for (int k = 0; k < c.nfv; k++)  // the leaving frontals lead the clique (:639-642 counts them from the front)
+        if ((k < nleaf) != (leafV.count(c.vars[k]) > 0)) {
+          *not_leaf = c.vars[k < nleaf ? k : nleaf];
+          return LMGPU_INVALID;
+        }
+      for (int ch : c.children) {
+        bool hangs = false;
+        for (size_t k = S->clq[ch].nfv; k < S->clq[ch].vars.size() && !hangs; k++) hangs = leafV.count(S->clq[ch].vars[k]) > 0;
+        if (!hangs) continue;
+        a.subtrees.push_back(ch);
+        if ((rc = plan_subtree(ch))) return rc;
+      }
+      for (int k = 0; k < nleaf; k++) goneV->insert(c.vars[k]);
+    }
+    acts->push_back(std::move(a));
+  }
+  return LMGPU_OK;
+}
+// what carrying the plan out collects
+struct MargWork {
+  std::map<uint64_t, std::vector<lmgpu_isam2::Marg>> marginalFactors;  // front key of a clique -> the marginals passed up to it
+  std::set<int32_t> factorIndicesToRemove;
+  std::vector<int> deferred;  // removed cliques whose update matrices a launch of this call still reads
+};
+// BayesTree::removeSubtree (BayesTree-inst.h:512-547) + the bookkeeping of trackingRemoveSubtree (ISAM2.cpp:506-527); returns the cliques, root first
+std::vector<int> is_remove_subtree(lmgpu_isam2* S, MargWork& W, int root) {
+  lmgpu_isam2::Clq& r = S->clq[root];
+  if (r.parent >= 0) {
+    auto& pc = S->clq[r.parent].children;
+    pc.erase(std::find(pc.begin(), pc.end(), root));
+    S->touched.push_back(r.parent);
+  } else {
+    S->roots.erase(std::find(S->roots.begin(), S->roots.end(), root));
+  }
+  r.parent = -1;
+  std::vector<int> q{root};
+  for (size_t i = 0; i < q.size(); i++) {
+    const lmgpu_isam2::Clq& c = S->clq[q[i]];
+    q.insert(q.end(), c.children.begin(), c.children.end());
+    auto it = W.marginalFactors.find(S->vars[c.vars[0]].key);  // marginals passed up to a clique that goes itself are dropped
+    if (it != W.marginalFactors.end()) {
+      for (lmgpu_isam2::Marg& m : it->second) is_pool_free(S, m.blk_off, m.blk_n);
+      W.marginalFactors.erase(it);
+    }
+    for (int k = 0; k < c.nfv; k++) {
+      S->node_of[c.vars[k]] = -1;
+      W.factorIndicesToRemove.insert(S->vindex[c.vars[k]].begin(), S->vindex[c.vars[k]].end());
+    }
+  }
+  return q;
+}
+// Part of a clique goes: ONE front over its leaving frontals (`leaving`, in clique order) -- the cached factors of the removed children
+// a.subtrees, the factors the leaving variables pull in -- is eliminated; the conditional is thrown away, *m takes the update matrix
+int is_marginal_of_front(lmgpu_isam2* S, MargWork& W, const MargAct& a, std::vector<int32_t> leaving, lmgpu_isam2::Marg* m) {
+  std::vector<IsGF> gfs;
+  for (int ch : a.subtrees) gfs.push_back(is_gf_of_clique(S, 1, ch));  // the child marginals (:583-592)
+  std::set<int32_t> pulled;  // factors the leaving frontals pull in, minus those of the subtrees removed at this step (:600-622)
+  for (int32_t v : leaving) pulled.insert(S->vindex[v].begin(), S->vindex[v].end());
+  for (int ch : a.subtrees)
+    for (int gid : is_remove_subtree(S, W, ch)) {
+      for (int k = 0; k < S->clq[gid].nfv; k++)
+        for (int32_t f : S->vindex[S->clq[gid].vars[k]]) pulled.erase(f);
+      W.deferred.push_back(gid);
+    }
+  for (int32_t f : pulled) {
+    IsGF g;
+    g.kind = S->facs[f].marg >= 0 ? 3 : 0;
+    g.id = f;
+    g.vids = is_fac_vids(S, S->facs[f]);
+    gfs.push_back(std::move(g));
+  }
+  // the front: the leaving frontals ascending by key (Ordering(cliqueFrontalsToEliminate), :627-633), then everything else they touch
+  auto by_key = [&](int32_t x, int32_t y) { return S->vars[x].key < S->vars[y].key; };
+  std::sort(leaving.begin(), leaving.end(), by_key);
+  std::set<int32_t> others;
+  for (const IsGF& g : gfs)
+    for (int32_t v : g.vids)
+      if (!std::count(leaving.begin(), leaving.end(), v)) others.insert(v);
+  std::vector<int32_t> sep(others.begin(), others.end());
+  std::sort(sep.begin(), sep.end(), by_key);
+  std::vector<int32_t> vid_of_slot = leaving;
+  vid_of_slot.insert(vid_of_slot.end(), sep.begin(), sep.end());
+  SymbolicFronts sf;
+  sf.fronts.resize(1);
+  for (size_t i = 0; i < leaving.size(); i++) sf.fronts[0].frontals.push_back((int32_t)i);
+  for (size_t i = 0; i < sep.size(); i++) sf.fronts[0].sep.push_back((int32_t)(leaving.size() + i));
+  for (size_t i = 0; i < gfs.size(); i++) sf.fronts[0].factors.push_back((int32_t)i);
+  sf.roots.push_back(0);
+  std::vector<int> tmp;
+  int rc;
+  if ((rc = is_eliminate_fronts(S, gfs, vid_of_slot, sf, false, &tmp))) return rc;
+  if ((rc = is_finish_elimination(S))) return rc;
+  is_release_clique(S, tmp[0], m);
+  return LMGPU_OK;
+}
+// Split clique id (ISAM2.cpp:639-653): its leading `leaving` frontals go, the conditional on the rest moves into storage of its own shape
+int is_split_clique(lmgpu_isam2* S, int id, const std::vector<int32_t>& leaving) {
+  lmgpu_isam2::Clq& c = S->clq[id];
+  int dimToRemove = 0, rc;
+  for (int32_t v : leaving) dimToRemove += kVarDim[S->vars[v].type];
+  const int n0 = c.n, nf0 = c.nf, n1 = n0 - dimToRemove, nf1 = nf0 - dimToRemove, m1 = n1 - nf1;
+  const int ld0 = c.ld > 0 ? c.ld : n0;
+  const int64_t src = c.rsd_off + (int64_t)dimToRemove * ld0 + dimToRemove;
+  if (n1 > kLdsLimitN) {  // stays a dense-front clique: one n1 x ld1 block
+    const int ld1 = (n1 + 15) & ~15;
+    int64_t f1;
+    if ((rc = is_pool_alloc(S, (size_t)n1 * ld1, &f1))) return rc;
+    ISCHECK(hipMemsetAsync(S->pool + f1, 0, (size_t)n1 * ld1 * sizeof(double), S->stream));
+    ISCHECK(hipMemcpy2DAsync(S->pool + f1, (size_t)ld1 * sizeof(double), S->pool + src, (size_t)ld0 * sizeof(double), (size_t)n1 * sizeof(double), (size_t)n1,
+                             hipMemcpyDeviceToDevice, S->stream));
+    is_pool_free(S, c.f_off, (size_t)n0 * c.ld);
+    c.f_off = f1;
+    c.ld = ld1;
+    c.rsd_off = f1;
+    c.u_off = f1 + (int64_t)nf1 * ld1 + nf1;
+  } else {
+    int64_t r1;
+    if ((rc = is_pool_alloc(S, (size_t)nf1 * n1, &r1))) return rc;
+    ISCHECK(hipMemcpy2DAsync(S->pool + r1, (size_t)n1 * sizeof(double), S->pool + src, (size_t)ld0 * sizeof(double), (size_t)n1 * sizeof(double), (size_t)nf1,
+                             hipMemcpyDeviceToDevice, S->stream));
+    if (c.ld > 0) {  // it now fits an LDS front: [R S d] and the update matrix in dense blocks of their own
+      int64_t u1;
+      if ((rc = is_pool_alloc(S, (size_t)m1 * m1, &u1))) return rc;
+      ISCHECK(hipMemcpy2DAsync(S->pool + u1, (size_t)m1 * sizeof(double), S->pool + c.u_off, (size_t)c.ld * sizeof(double), (size_t)m1 * sizeof(double), (size_t)m1,
+                               hipMemcpyDeviceToDevice, S->stream));
+      is_pool_free(S, c.f_off, (size_t)n0 * c.ld);
+      c.f_off = -1;
+      c.ld = 0;
+      c.u_off = u1;
+    } else {
+      is_pool_free(S, c.rsd_off, (size_t)nf0 * n0);
+    }
+    c.rsd_off = r1;
+  }
+  if (c.xrow_off >= 0) is_pool_free(S, c.xrow_off, (size_t)n0 / 2 + 1);
+  c.xrow_off = -1;
+  for (int32_t v : leaving) S->node_of[v] = -1;
+  c.vars.erase(c.vars.begin(), c.vars.begin() + leaving.size());
+  c.nfv -= (int)leaving.size();
+  c.nf = nf1;
+  c.n = n1;
+  S->touched.push_back(id);
+  return LMGPU_OK;
 }
 
 // ISAM2::marginalizeLeaves (gtsam/nonlinear/ISAM2.cpp:487-720).  The host walks the tree and the variable index exactly as the reference
@@ -2514,266 +2734,67 @@ int is_marginalize_leaves(lmgpu_isam2* S, const std::vector<uint64_t>& leafList)
     leafV.insert(it->second);
   }
   if (leafV.empty()) return LMGPU_OK;
-  // ---- the plan: the reference's loop (:530-667) without touching anything
-  struct Act {
-    bool whole;
-    int clique;
-    std::vector<int> subtrees;  // partial: the children that hang on a leaving variable
-  };
-  std::vector<Act> plan;
+  std::vector<MargAct> plan;
   std::set<int32_t> goneV;
-  auto not_leaf = [&](int32_t v) {
-    S->failed_key = S->vars[v].key;
-    S->err = "ISAM2::marginalizeLeaves: requesting to marginalize variables that are not leaves (a variable that stays is eliminated before this one)";
-    return LMGPU_INVALID;
-  };
-  auto plan_subtree = [&](int root) -> int {  // every frontal below must leave too
-    std::vector<int> q{root};
-    for (size_t i = 0; i < q.size(); i++) {
-      const lmgpu_isam2::Clq& c = S->clq[q[i]];
-      for (int k = 0; k < c.nfv; k++) {
-        if (!leafV.count(c.vars[k])) return not_leaf(c.vars[k]);
-        goneV.insert(c.vars[k]);
-      }
-      q.insert(q.end(), c.children.begin(), c.children.end());
-    }
-    return LMGPU_OK;
-  };
+  int32_t not_leaf = -1;
   int rc;
-  for (uint64_t key : leafKeys) {
-    const int32_t v = S->vid_of.at(key);
-    if (goneV.count(v)) continue;
-    int id = S->node_of[v];
-    while (S->clq[id].parent >= 0) {  // up to the root of the marginalized subtree: only the first variable of the parent needs a look
-      const int32_t pf = S->clq[S->clq[id].parent].vars[0];
-      if (leafV.count(pf) && !goneV.count(pf))
-        id = S->clq[id].parent;
-      else
-        break;
-    }
-    const lmgpu_isam2::Clq& c = S->clq[id];
-    int nleaf = 0;
-    for (int k = 0; k < c.nfv; k++) nleaf += leafV.count(c.vars[k]) && !goneV.count(c.vars[k]);
-    Act a{nleaf == c.nfv, id, {}};
-    if (a.whole) {
-      if ((rc = plan_subtree(id))) return rc;
-    } else {
-      for (int k = 0; k < c.nfv; k++)  // the leaving frontals lead the clique (:639-642 counts them from the front)
-        if ((k < nleaf) != (leafV.count(c.vars[k]) > 0)) return not_leaf(c.vars[k < nleaf ? k : nleaf]);
-      for (int ch : c.children) {
-        bool hangs = false;
-        for (size_t k = S->clq[ch].nfv; k < S->clq[ch].vars.size() && !hangs; k++) hangs = leafV.count(S->clq[ch].vars[k]) > 0;
-        if (!hangs) continue;
-        a.subtrees.push_back(ch);
-        if ((rc = plan_subtree(ch))) return rc;
-      }
-      for (int k = 0; k < nleaf; k++) goneV.insert(c.vars[k]);
-    }
-    plan.push_back(std::move(a));
+  if ((rc = is_plan_marginalize(S, leafKeys, leafV, &plan, &goneV, &not_leaf))) {
+    S->failed_key = S->vars[not_leaf].key;
+    S->err = "ISAM2::marginalizeLeaves: requesting to marginalize variables that are not leaves (a variable that stays is eliminated before this one)";
+    return rc;
   }
   S->failed_key = 0;
   // ---- carry it out
   if ((rc = is_stage_begin(S))) return rc;
   S->elim_pending = false;
-  std::map<uint64_t, std::vector<lmgpu_isam2::Marg>> marginalFactors;  // front key of a clique -> the marginals passed up to it
-  std::set<int32_t> factorIndicesToRemove;
-  std::vector<int> deferred;  // removed cliques whose update matrices a launch of this call still reads
-  auto drop_marginals = [&](uint64_t frontKey) {
-    auto it = marginalFactors.find(frontKey);
-    if (it == marginalFactors.end()) return;
-    for (lmgpu_isam2::Marg& m : it->second) is_pool_free(S, m.blk_off, m.blk_n);
-    marginalFactors.erase(it);
-  };
-  // BayesTree::removeSubtree (BayesTree-inst.h:512-547) + the bookkeeping of trackingRemoveSubtree (:506-527); returns the cliques, root first
-  auto remove_subtree = [&](int root) {
-    lmgpu_isam2::Clq& r = S->clq[root];
-    if (r.parent >= 0) {
-      auto& pc = S->clq[r.parent].children;
-      pc.erase(std::find(pc.begin(), pc.end(), root));
-      S->touched.push_back(r.parent);
-    } else {
-      S->roots.erase(std::find(S->roots.begin(), S->roots.end(), root));
-    }
-    r.parent = -1;
-    std::vector<int> q{root};
-    for (size_t i = 0; i < q.size(); i++) {
-      const lmgpu_isam2::Clq& c = S->clq[q[i]];
-      q.insert(q.end(), c.children.begin(), c.children.end());
-      drop_marginals(S->vars[c.vars[0]].key);
-      for (int k = 0; k < c.nfv; k++) {
-        S->node_of[c.vars[k]] = -1;
-        factorIndicesToRemove.insert(S->vindex[c.vars[k]].begin(), S->vindex[c.vars[k]].end());
-      }
-    }
-    return q;
-  };
-  for (const Act& a : plan) {
+  MargWork W;
+  for (const MargAct& a : plan) {
+    const int id = a.clique;
     if (a.whole) {
-      const int parent = S->clq[a.clique].parent;
+      const int parent = S->clq[id].parent;
       const uint64_t parentFront = parent >= 0 ? S->vars[S->clq[parent].vars[0]].key : 0;
-      const std::vector<int> gone = remove_subtree(a.clique);
-      for (int id : gone) {
-        if (id == a.clique && parent >= 0) {  // its cached factor belongs to the parent from now on; a root's is dropped (:559-568)
+      for (int gone : is_remove_subtree(S, W, id)) {
+        if (gone == id && parent >= 0) {  // its cached factor belongs to the parent from now on; a root's is dropped (:559-568)
           lmgpu_isam2::Marg m;
-          is_release_clique(S, id, &m);
-          marginalFactors[parentFront].push_back(std::move(m));
+          is_release_clique(S, gone, &m);
+          W.marginalFactors[parentFront].push_back(std::move(m));
         } else {
-          is_release_clique(S, id);
+          is_release_clique(S, gone);
         }
       }
       continue;
     }
-    // ---- part of a clique: one front over its leaving frontals
-    const int id = a.clique;
-    std::vector<IsGF> gfs;
-    for (int ch : a.subtrees) {  // the child marginals (:583-592)
-      IsGF g;
-      g.kind = 1;
-      g.id = ch;
-      g.vids.assign(S->clq[ch].vars.begin() + S->clq[ch].nfv, S->clq[ch].vars.end());
-      gfs.push_back(std::move(g));
-    }
-    std::set<int32_t> pulled;  // factors the leaving frontals pull in, minus those of the subtrees removed at this step (:600-622)
-    std::vector<int32_t> leaving;
-    for (int k = 0; k < S->clq[id].nfv && leafV.count(S->clq[id].vars[k]); k++) {
-      leaving.push_back(S->clq[id].vars[k]);
-      pulled.insert(S->vindex[S->clq[id].vars[k]].begin(), S->vindex[S->clq[id].vars[k]].end());
-    }
-    for (int ch : a.subtrees)
-      for (int gid : remove_subtree(ch)) {
-        for (int k = 0; k < S->clq[gid].nfv; k++)
-          for (int32_t f : S->vindex[S->clq[gid].vars[k]]) pulled.erase(f);
-        deferred.push_back(gid);
-      }
-    for (int32_t f : pulled) {
-      IsGF g;
-      g.kind = S->facs[f].marg >= 0 ? 3 : 0;
-      g.id = f;
-      g.vids = is_fac_vids(S, S->facs[f]);
-      gfs.push_back(std::move(g));
-    }
-    // the front: the leaving frontals ascending by key (Ordering(cliqueFrontalsToEliminate), :627-633), then everything else they touch
-    auto by_key = [&](int32_t x, int32_t y) { return S->vars[x].key < S->vars[y].key; };
-    std::sort(leaving.begin(), leaving.end(), by_key);
-    std::set<int32_t> others;
-    for (const IsGF& g : gfs)
-      for (int32_t v : g.vids)
-        if (!std::count(leaving.begin(), leaving.end(), v)) others.insert(v);
-    std::vector<int32_t> sep(others.begin(), others.end());
-    std::sort(sep.begin(), sep.end(), by_key);
-    std::vector<int32_t> vid_of_slot = leaving;
-    vid_of_slot.insert(vid_of_slot.end(), sep.begin(), sep.end());
-    SymbolicFronts sf;
-    sf.fronts.resize(1);
-    for (size_t i = 0; i < leaving.size(); i++) sf.fronts[0].frontals.push_back((int32_t)i);
-    for (size_t i = 0; i < sep.size(); i++) sf.fronts[0].sep.push_back((int32_t)(leaving.size() + i));
-    for (size_t i = 0; i < gfs.size(); i++) sf.fronts[0].factors.push_back((int32_t)i);
-    sf.roots.push_back(0);
+    std::vector<int32_t> leaving;  // its leading frontals
+    for (int k = 0; k < S->clq[id].nfv && leafV.count(S->clq[id].vars[k]); k++) leaving.push_back(S->clq[id].vars[k]);
     const uint64_t frontKey = S->vars[S->clq[id].vars[0]].key;  // (the marginal is filed under the front key the clique has BEFORE the split, :637)
-    std::vector<int> tmp;
-    if ((rc = is_eliminate_fronts(S, gfs, vid_of_slot, sf, false, &tmp))) return rc;
-    if ((rc = is_finish_elimination(S))) return rc;
-    {
-      lmgpu_isam2::Marg m;
-      is_release_clique(S, tmp[0], &m);
-      marginalFactors[frontKey].push_back(std::move(m));
-    }
-    // ---- split the clique (:639-653): the leading `leaving` variables go, the conditional on the rest stays as it is
-    lmgpu_isam2::Clq& c = S->clq[id];
-    int dimToRemove = 0;
-    for (int32_t v : leaving) dimToRemove += kVarDim[S->vars[v].type];
-    const int n0 = c.n, nf0 = c.nf, n1 = n0 - dimToRemove, nf1 = nf0 - dimToRemove, m1 = n1 - nf1;
-    const int ld0 = c.ld > 0 ? c.ld : n0;
-    const int64_t src = c.rsd_off + (int64_t)dimToRemove * ld0 + dimToRemove;
-    if (n1 > kLdsLimitN) {  // stays a dense-front clique: one n1 x ld1 block
-      const int ld1 = (n1 + 15) & ~15;
-      int64_t f1;
-      if ((rc = is_pool_alloc(S, (size_t)n1 * ld1, &f1))) return rc;
-      ISCHECK(hipMemsetAsync(S->pool + f1, 0, (size_t)n1 * ld1 * sizeof(double), S->stream));
-      ISCHECK(hipMemcpy2DAsync(S->pool + f1, (size_t)ld1 * sizeof(double), S->pool + src, (size_t)ld0 * sizeof(double), (size_t)n1 * sizeof(double), (size_t)n1,
-                               hipMemcpyDeviceToDevice, S->stream));
-      is_pool_free(S, c.f_off, (size_t)n0 * c.ld);
-      c.f_off = f1;
-      c.ld = ld1;
-      c.rsd_off = f1;
-      c.u_off = f1 + (int64_t)nf1 * ld1 + nf1;
-    } else {
-      int64_t r1;
-      if ((rc = is_pool_alloc(S, (size_t)nf1 * n1, &r1))) return rc;
-      ISCHECK(hipMemcpy2DAsync(S->pool + r1, (size_t)n1 * sizeof(double), S->pool + src, (size_t)ld0 * sizeof(double), (size_t)n1 * sizeof(double), (size_t)nf1,
-                               hipMemcpyDeviceToDevice, S->stream));
-      if (c.ld > 0) {  // it now fits an LDS front: [R S d] and the update matrix in dense blocks of their own
-        int64_t u1;
-        if ((rc = is_pool_alloc(S, (size_t)m1 * m1, &u1))) return rc;
-        ISCHECK(hipMemcpy2DAsync(S->pool + u1, (size_t)m1 * sizeof(double), S->pool + c.u_off, (size_t)c.ld * sizeof(double), (size_t)m1 * sizeof(double), (size_t)m1,
-                                 hipMemcpyDeviceToDevice, S->stream));
-        is_pool_free(S, c.f_off, (size_t)n0 * c.ld);
-        c.f_off = -1;
-        c.ld = 0;
-        c.u_off = u1;
-      } else {
-        is_pool_free(S, c.rsd_off, (size_t)nf0 * n0);
-      }
-      c.rsd_off = r1;
-    }
-    if (c.xrow_off >= 0) is_pool_free(S, c.xrow_off, (size_t)n0 / 2 + 1);
-    c.xrow_off = -1;
-    for (int32_t v : leaving) {
-      S->node_of[v] = -1;
-      factorIndicesToRemove.insert(S->vindex[v].begin(), S->vindex[v].end());
-    }
-    c.vars.erase(c.vars.begin(), c.vars.begin() + leaving.size());
-    c.nfv -= (int)leaving.size();
-    c.nf = nf1;
-    c.n = n1;
-    S->touched.push_back(id);
+    lmgpu_isam2::Marg m;
+    if ((rc = is_marginal_of_front(S, W, a, leaving, &m))) return rc;
+    W.marginalFactors[frontKey].push_back(std::move(m));
+    for (int32_t v : leaving) W.factorIndicesToRemove.insert(S->vindex[v].begin(), S->vindex[v].end());
+    if ((rc = is_split_clique(S, id, leaving))) return rc;
   }
-  for (int id : deferred) is_release_clique(S, id);
+  for (int id : W.deferred) is_release_clique(S, id);
   // ---- the factors the marginals summarise leave the graph and the variable index (:672-682)
-  for (int32_t idx : factorIndicesToRemove) {
-    for (int32_t v : is_fac_vids(S, S->facs[idx])) {
-      std::vector<int32_t>& entries = S->vindex[v];
-      entries.erase(std::find(entries.begin(), entries.end(), idx));
-    }
-    if ((rc = is_empty_slot(S, idx))) return rc;
-  }
+  for (int32_t idx : W.factorIndicesToRemove)
+    if ((rc = is_forget_factor(S, idx))) return rc;
   // ---- the marginals enter it (:684-709), in the order of the map (ascending front key), slots as FactorGraph::add_factors gives them
   size_t slot_scan = 0;
-  for (auto& kf : marginalFactors)
+  for (auto& kf : W.marginalFactors)
     for (lmgpu_isam2::Marg& m : kf.second) {
-      size_t slot = S->facs.size();
-      if (S->find_unused_slots) {
-        while (slot_scan < S->facs.size() && !S->facs[slot_scan].removed) ++slot_scan;
-        slot = slot_scan;
-      }
+      const size_t slot = is_take_slot(S, &slot_scan);
       lmgpu_isam2::Fac f{-1, -1, -1, {-1, -1, -1}, false, -1};
       for (int32_t v : m.vids) {
         S->fixed.insert(S->vars[v].key);
         S->vindex[v].push_back((int32_t)slot);
       }
       f.marg = is_new_marg(S, m);
-      if (slot == S->facs.size())
-        S->facs.push_back(f);
-      else
-        S->facs[slot] = f;
+      is_put_factor(S, slot, f);
       S->last_marginal_idx.push_back((uint64_t)slot);
     }
-  // ---- removeVariables(leafKeys) (:385-398, 712)
-  for (int32_t v : leafV) {
-    S->vars[v].dead = true;
-    S->vindex[v].clear();
-    if (S->dogleg) {
-      const size_t o = (size_t)S->vars[v].xoff, nb = (size_t)kVarDim[S->vars[v].type] * sizeof(double);
-      ISCHECK(hipMemsetAsync(S->delta + o, 0, nb, S->stream));
-      ISCHECK(hipMemsetAsync(S->delta_newton + o, 0, nb, S->stream));
-      ISCHECK(hipMemsetAsync(S->rgprod + o, 0, nb, S->stream));
-    }
-    S->replaced[v] = 0;
-    S->node_of[v] = -1;
-    S->fixed.erase(S->vars[v].key);
-    S->vid_of.erase(S->vars[v].key);
-  }
-  S->last_deleted_idx.assign(factorIndicesToRemove.begin(), factorIndicesToRemove.end());
+  // ---- removeVariables(leafKeys) (:712)
+  for (int32_t v : leafV)
+    if ((rc = is_retire_variable(S, v))) return rc;
+  S->last_deleted_idx.assign(W.factorIndicesToRemove.begin(), W.factorIndicesToRemove.end());
   return is_finish_elimination(S);
 }
 

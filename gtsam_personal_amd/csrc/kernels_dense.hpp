@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "kernels_front.hpp"
 
@@ -32,6 +33,32 @@ struct RowSrc {
   int32_t idx;  // >= 0: child reference (index into childs[]); < 0: own factor, -(index into ffac[]) - 1
   int32_t i;    // child: row / column index inside its update matrix; factor: local column p of [A b]
 };
+// host: row -> sources of front F, from its slices of childs / cmap / ffac and fd; appends the front's n + 1 row pointers and its sources
+// to rowptr / rowsrc and returns where its row pointers start
+inline int32_t append_row_sources(const FrontDesc& F, const std::vector<ChildRef>& childs, const std::vector<int32_t>& cmap, const std::vector<FrontFac>& ffac,
+                                  const std::vector<FacDesc>& fd, std::vector<int32_t>& rowptr, std::vector<RowSrc>& rowsrc) {
+  std::vector<std::vector<RowSrc>> rows(F.n);
+  for (int k = 0; k < F.child_count; k++) {
+    const ChildRef& c = childs[F.child_begin + k];
+    for (int i = 0; i < c.m; i++) rows[cmap[c.map_begin + i]].push_back(RowSrc{F.child_begin + k, i});
+  }
+  for (int k = 0; k < F.fac_count; k++) {
+    const FrontFac& ff = ffac[F.fac_begin + k];
+    const FacDesc& d = fd[ff.fac];
+    const int nc = d.d0 + d.d1 + d.d2 + 1;
+    for (int p = 0; p < nc; p++) {
+      const int gp = (p < d.d0) ? ff.c0 + p : (p < d.d0 + d.d1 ? ff.c1 + (p - d.d0) : (p < d.d0 + d.d1 + d.d2 ? ff.c2 + (p - d.d0 - d.d1) : F.n - 1));
+      rows[gp].push_back(RowSrc{-(F.fac_begin + k) - 1, p});
+    }
+  }
+  const int32_t begin = (int32_t)rowptr.size();
+  for (int r = 0; r < F.n; r++) {
+    rowptr.push_back((int32_t)rowsrc.size());
+    rowsrc.insert(rowsrc.end(), rows[r].begin(), rows[r].end());
+  }
+  rowptr.push_back((int32_t)rowsrc.size());
+  return begin;
+}
 __device__ __forceinline__ void assemble_row_body(const FrontDesc& F, int64_t f_off, int ld, const int32_t* __restrict__ rowptr, const RowSrc* __restrict__ src,
                                                   const ChildRef* __restrict__ childs, const int32_t* __restrict__ cmap,
                                                   const FrontFac* __restrict__ ffac, const FacDesc* __restrict__ fd, double* __restrict__ pool,

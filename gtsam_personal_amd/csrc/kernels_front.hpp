@@ -113,6 +113,19 @@ __device__ __forceinline__ int fac_col(const FD& d, int c0, int c1, int c2, int 
 static_assert(sizeof(FrontDesc) == LEAFPACK_HDR, "leaf records embed a FrontDesc");
 static_assert(sizeof(LFac) == 32, "leaf records embed LFac entries");
 #define LDSF_EXTRA_BYTES (LDSF_JCAP * 8 + LDSF_MAXB * 32 + 16)
+// host: dynamic LDS bytes of an LDS-front launch that stages jcap doubles of Jacobians and a front of rows x cols doubles
+inline size_t lds_front_bytes(int jcap, int rows, int cols) {
+  return (size_t)LDSF_EXTRA_BYTES - (size_t)(LDSF_JCAP - jcap) * 8 + 64 + (size_t)rows * cols * sizeof(double);
+}
+// host: doubles of [A b] the own factors of front F bring along (what a launch has to stage for it, capped at LDSF_JCAP by the caller)
+inline int front_jacobian_doubles(const FrontDesc& F, const FrontFac* ffac, const FacDesc* fd) {
+  int tot = 0;
+  for (int k = 0; k < F.fac_count; k++) {
+    const FacDesc& d = fd[ffac[F.fac_begin + k].fac];
+    tot += d.rows * (d.d0 + d.d1 + d.d2 + 1);
+  }
+  return tot;
+}
 // development aid (tools/ldsf_phases.py builds a library of its own with it): 100 MHz wall-clock time per phase of the first workgroup of
 // every launch of at most eight fronts (= the upper levels of a clique tree, where a launch lasts as long as its slowest front)
 #ifdef LDSF_STAMPS

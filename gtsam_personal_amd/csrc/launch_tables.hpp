@@ -198,27 +198,7 @@ int add_gather_leaf(lmgpu_handle* h, LaunchTables& T, int fi, int c, const std::
 // Row -> sources of HBM front fi, for the deterministic assembly.  Reads the front's slices of T.childs / T.cmap / T.ffac and T.fd; fills
 // row_begin[fi] and appends the front's n + 1 row pointers and its sources to T.rowptr / T.rowsrc.
 void build_row_sources(lmgpu_handle* h, LaunchTables& T, int fi) {
-  const FrontDesc& F = h->h_fronts[fi];
-  std::vector<std::vector<RowSrc>> rows(F.n);
-  for (int k = 0; k < F.child_count; k++) {
-    const ChildRef& c = T.childs[F.child_begin + k];
-    for (int i = 0; i < c.m; i++) rows[T.cmap[c.map_begin + i]].push_back(RowSrc{F.child_begin + k, i});
-  }
-  for (int k = 0; k < F.fac_count; k++) {
-    const FrontFac& ff = T.ffac[F.fac_begin + k];
-    const FacDesc& d = T.fd[ff.fac];
-    const int nc = d.d0 + d.d1 + d.d2 + 1;
-    for (int p = 0; p < nc; p++) {
-      const int gp = (p < d.d0) ? ff.c0 + p : (p < d.d0 + d.d1 ? ff.c1 + (p - d.d0) : (p < d.d0 + d.d1 + d.d2 ? ff.c2 + (p - d.d0 - d.d1) : F.n - 1));
-      rows[gp].push_back(RowSrc{-(F.fac_begin + k) - 1, p});
-    }
-  }
-  h->row_begin[fi] = (int32_t)T.rowptr.size();
-  for (int r = 0; r < F.n; r++) {
-    T.rowptr.push_back((int32_t)T.rowsrc.size());
-    T.rowsrc.insert(T.rowsrc.end(), rows[r].begin(), rows[r].end());
-  }
-  T.rowptr.push_back((int32_t)T.rowsrc.size());
+  h->row_begin[fi] = append_row_sources(h->h_fronts[fi], T.childs, T.cmap, T.ffac, T.fd, T.rowptr, T.rowsrc);
 }
 
 // Gather lists of ONE HBM front from the entries its gather leaves registered.  Reads gp / gv (consumed), the plan's front and

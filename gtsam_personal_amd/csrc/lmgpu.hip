@@ -907,7 +907,7 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
     if (seg >= 0) {
       const lmgpu_handle::ElimSeg& E = h->elim_segs[seg];
       const int b0 = h->levels[E.lvl_lo].list_begin, e0 = h->levels[E.lvl_hi].list_begin + h->levels[E.lvl_hi].list_count;
-      const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - E.jcap) * 8 + 64 + (size_t)E.nmax * E.nmax * sizeof(double);
+      const size_t lds = lds_front_bytes(E.jcap, E.nmax, E.nmax);
       const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
       unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + E.lvl_hi;
       auto* kernel = E.threads == 1024 ? lds_front_merged_kernel<1024> : lds_front_merged_kernel<256>;
@@ -920,8 +920,7 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
     const bool fused = h->fuse_levels && L.fuse_task_count > 0;
     if (fused) {  // the level's LDS fronts and medium fronts in one grid
       const MedLevel ML{(const MedFront*)(h->d_med_fronts + L.med_begin)};
-      const size_t lds = std::max<size_t>(kLdsFrontExtra - (size_t)(LDSF_JCAP - L.fuse_jcap) * 8 + 64 + (size_t)L.fuse_nmax * L.fuse_nmax * sizeof(double),
-                                          (size_t)DIAG_LDS_BYTES);
+      const size_t lds = std::max<size_t>(lds_front_bytes(L.fuse_jcap, L.fuse_nmax, L.fuse_nmax), (size_t)DIAG_LDS_BYTES);
       unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + li;
       const int kt = h->kt.begin(LMGPU_KT_PANEL, s);
       const bool wide = L.fuse_threads == 1024;
@@ -940,7 +939,7 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       // gather leaves keep only nf rows: one wave per front (barriers become free, ~2.5x more fronts resident per CU)
       const int threads = (b >= 6 || b % 6 == 0) ? 64 : (b % 6 == 1 ? 128 : 256);
       const int jcap = L.bin_jcap[b];
-      const size_t lds = kLdsFrontExtra - (size_t)(LDSF_JCAP - jcap) * 8 + 64 + (size_t)srows * nmax * sizeof(double);
+      const size_t lds = lds_front_bytes(jcap, srows, nmax);
       const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
       if (L.bin_group[b]) {  // every leaf of the bin qualifies (leaf_group_form): four leaves per wave, one lane per factor
         auto* gk = L.bin_group[b] == 1 ? lds_front_group_kernel<2, LEAFGRP_MAXSEP, 3> : lds_front_group_kernel<LEAFGRP_MAXROWS, LEAFGRP_MAXSEP, LEAFGRP_MAXNF>;
@@ -1170,13 +1169,12 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
 static int leaf_group_form(const FrontDesc& F, const FrontFac* ffac, const FacDesc* fd, int jcap) {
   if (F.par_ld != -1 || F.pad != 0 || F.nf < 1 || F.nf > LEAFGRP_MAXNF || F.nf > LEAFPACK_MAXNF || F.ld_rsd != F.n) return 0;
   if (F.fac_count < 1 || F.fac_count > LDSF_MAXB) return 0;
-  int form = F.nf <= 3 ? 1 : 2, tot = 0;
+  int form = F.nf <= 3 ? 1 : 2;
   int32_t seen[LDSF_MAXB];
   int nseen = 0;
   for (int k = 0; k < F.fac_count; k++) {
     const FrontFac& ff = ffac[F.fac_begin + k];
     const FacDesc& d = fd[ff.fac];
-    tot += d.rows * (d.d0 + d.d1 + d.d2 + 1);
     if (d.d2 > 0 || d.rows < 1 || d.rows > LEAFGRP_MAXROWS) return 0;
     if (d.d1 == 0) {  // unary: on frontal columns
       if (ff.c0 + d.d0 > F.nf) return 0;
@@ -1191,7 +1189,7 @@ static int leaf_group_form(const FrontDesc& F, const FrontFac* ffac, const FacDe
     seen[nseen++] = cs;
     if (d.rows > 2) form = 2;
   }
-  if (tot > jcap) return 0;  // no single-batch record
+  if (front_jacobian_doubles(F, ffac, fd) > jcap) return 0;  // no single-batch record
   return form;
 }
 
