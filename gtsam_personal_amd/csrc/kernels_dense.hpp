@@ -106,6 +106,24 @@ __global__ __launch_bounds__(256) void hbm_assemble_rows_kernel(FrontDesc F, int
   assemble_row_body(F, f_off, ld, rowptr, src, childs, cmap, ffac, fd, pool, R, with_factors != 0);
 }
 
+// the same, and the wave of a frontal row then adds the row's damping term lambda dampw (and gex) to its diagonal (rhs) entry: what
+// hbm_damp_kernel adds behind the launch above (each entry receives the same additions in the same order, so the bits are the same)
+__global__ __launch_bounds__(256) void hbm_assemble_rows_damp_kernel(FrontDesc F, int64_t f_off, int ld, const int32_t* __restrict__ rowptr,
+                                                                     const RowSrc* __restrict__ src, const ChildRef* __restrict__ childs,
+                                                                     const int32_t* __restrict__ cmap, const FrontFac* __restrict__ ffac,
+                                                                     const FacDesc* __restrict__ fd, double* __restrict__ pool, int with_factors,
+                                                                     const int32_t* __restrict__ fxoff, double lambda_v, const double* __restrict__ lambda_p,
+                                                                     const double* __restrict__ dampw, const double* __restrict__ gex) {
+  const int R = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (R >= F.n) return;
+  assemble_row_body(F, f_off, ld, rowptr, src, childs, cmap, ffac, fd, pool, R, with_factors != 0);
+  // (assemble_row_body ends every source with the wave's stores drained, so lane 0 sees the row's sums)
+  if (R < F.nf && (threadIdx.x & 63) == 0) {
+    pool[f_off + (size_t)R * ld + R] += (lambda_p ? *lambda_p : lambda_v) * dampw[fxoff[F.fx_begin + R]];
+    if (gex) pool[f_off + (size_t)R * ld + F.n - 1] += gex[fxoff[F.fx_begin + R]];
+  }
+}
+
 __global__ __launch_bounds__(256) void hbm_damp_kernel(FrontDesc F, int64_t f_off, int ld, const int32_t* __restrict__ fxoff,
                                                         double* __restrict__ pool, double lambda_v, const double* __restrict__ lambda_p, const double* __restrict__ dampw,
                                                         const double* __restrict__ gex) {

@@ -388,15 +388,235 @@ __global__ __launch_bounds__(256) void panel_trsm_kernel(double* __restrict__ A,
 // When what is left after an outer panel is small (m = n - r0 <= TAIL_MAX_M columns: the last, partial panel of the frontal part
 // plus the separator and the right-hand side -- BAL's 9001-column root leaves 40 + 1), the remaining three steps
 //   update with panel [p0, p0 + kp)  ->  factor the last nf - r0 frontal columns  ->  update what is right of them
-// are one workgroup: the panel's columns and the trailing block staged in LDS, C -= P^T P, a right-looking partial Cholesky
-// in LDS, everything written back (the rows below the frontal part are the front's update matrix for its parent).  Replaces
-// two update launches and the two-launch panel (five launches with their gaps: ~0.15 ms of a 9 ms step) by ~35 us.
+// are one workgroup of four waves, everything written back (the rows below the frontal part are the front's update matrix for
+// its parent).  Replaces two update launches and the two-launch panel (five launches with their gaps: ~0.15 ms of a 9 ms step).
 // Also leaves the 16x16 inverses of its diagonal tiles (inv16, identity-padded) like diag_potrf_kernel.
+//
+// front_tail_kernel: the m x m block is the <= 6 upper 16x16 tiles of a zero-padded 48 x 48 block in the accumulator layout of
+// v_mfma_f64_16x16x4_f64 (header of this file).
+//   operands   wave w takes rows [64 w, 64 w + 64) of the panel straight from global memory into registers: a load instruction is
+//              16 consecutive columns (one 128-byte segment) of each of four rows, and all 48 loads of a wave are in flight together.  The register that
+//              holds P[k0 + 4 s + kk][16 t + cc] is both the A operand (tile row t) and the B operand (tile column t) of k-step s,
+//              so nothing is staged in LDS and no index is divided.
+//   update     every wave forms its K-quarter of all six tiles (six independent chains of 16 MFMAs: 96 issue slots a wave, what two
+//              whole tiles of 64 would take, but with four waves loading); waves 1..3 hand their quarters over through LDS and
+//              wave 0 adds them in the fixed order C - (((q0 + q1) + q2) + q3).
+//   factor     wave 0, in registers, four pivots at a time like potrf64_wave_g4, no barrier: the group that straddles the end of
+//              the frontal part treats its rows beyond it as unit pivots, which makes the group's solve their Schur update
+//              (W = [[R, R']; [0, I]]^-1), and the rank-4 / rank-16 updates behind it take only the frontal rows.
+//   inverses   from an identity tile carried through each strip's solves (one reciprocal square root per pivot, then multiplies).
+// Measured on C4's root (m = 41, nft = 40, kp = 256): 31 us per launch where the scalar form took 82.
+// The pivot rules are those of front_tail_scalar_kernel below, the form the kernel had
+// before (LDS, scalar FMAs, a barrier pair per pivot), kept in the test library as the cross-check (LMGPU_TAIL_SCALAR=1).
 #define TAIL_MAX_M 48
 #define TAIL_MAX_KP 256
-#define TAIL_LDS_BYTES ((TAIL_MAX_KP * TAIL_MAX_M + TAIL_MAX_M * TAIL_MAX_M + 64 * 65) * 8)
+
+// partial Cholesky of the first nft < 48 columns of the 48 x 48 block T (upper tiles, zero beyond the block's m columns; the
+// entries below the diagonal inside diagonal tiles are don't-cares but finite).  Leaves R in rows < nft, the Schur complement in
+// the rows behind them and E[g] = R_gg^-T of the identity-padded frontal factor (potrf64_wave_g4's INV).  Returns "a pivot was <= 0"
+// (a NaN pivot passes, like Eigen's LLT; the substitute pivot is |p|, or 1 for zero and NaN).
+__device__ __forceinline__ bool potrf48_partial_wave(double4_t (&T)[3][3], double4_t (&E)[3], int nft) {
+  const int lane = threadIdx.x & 63, kk = lane >> 4, cc = lane & 15;
+  bool failed = false;
+#pragma unroll
+  for (int g = 0; g < 3; g++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) E[g][r] = (kk + 4 * r == cc) ? 1.0 : 0.0;
+    if (16 * g >= nft) continue;  // nothing frontal in this strip or behind it
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (16 * g + 4 * q >= nft) continue;
+      const int na = min(4, nft - 16 * g - 4 * q);  // frontal rows of the group (wave-uniform)
+      double m[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = a; b < 4; b++) m[a][b] = readlane_d(T[g][g][q], 16 * a + 4 * q + b);
+      double R[4][4], inv[4];
+#pragma unroll
+      for (int a = 0; a < 4; a++) {
+        const bool act = a < na;
+        double p = m[a][a];
+#pragma unroll
+        for (int k = 0; k < a; k++) p -= R[k][a] * R[k][a];
+        failed |= act && (p <= 0.0);
+        p = (p > 0.0) ? p : ((p == p && p != 0.0) ? fabs(p) : 1.0);
+        p = act ? p : 1.0;  // a row behind the frontal part: unit pivot, nothing right of it (its row only receives the update)
+        const double rs = fast_rsqrt(p);
+        inv[a] = rs;
+        R[a][a] = p * rs;
+#pragma unroll
+        for (int b = a + 1; b < 4; b++) {
+          double v = m[a][b];
+#pragma unroll
+          for (int k = 0; k < a; k++) v -= R[k][a] * R[k][b];
+          R[a][b] = act ? v * rs : 0.0;
+        }
+      }
+      double W[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; a++) {
+        W[a][a] = inv[a];
+#pragma unroll
+        for (int b = a + 1; b < 4; b++) {
+          double v = 0;
+#pragma unroll
+          for (int k = a; k < b; k++) v += W[a][k] * R[k][b];
+          W[a][b] = -v * inv[b];
+        }
+      }
+      double aop = 0.0;  // A[i = cc][k = kk] = W[k][i]
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int i = k; i < 4; i++) aop = (kk == k && cc == i) ? W[k][i] : aop;
+      // the identity-padded factor has zeros where the rows behind the frontal part take their update
+      const double aop_e = (kk != cc && cc >= na) ? 0.0 : aop;
+      double bop = 0.0, bop_e = 0.0;
+      {
+        const double4_t x = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, T[g][g][q], double4_t{0, 0, 0, 0}, 0, 0, 0);
+        T[g][g][q] = x[0];
+        if (q < 3) {  // the rows of the strip below the group, frontal or not, minus the group's frontal rows
+          bop = (cc >= 4 * (q + 1) && kk < na) ? -T[g][g][q] : 0.0;
+          bop_e = (16 * g + cc < nft) ? bop : 0.0;
+          T[g][g] = __builtin_amdgcn_mfma_f64_16x16x4f64(bop, T[g][g][q], T[g][g], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int h = g + 1; h < 3; h++) {
+        const double4_t x = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, T[g][h][q], double4_t{0, 0, 0, 0}, 0, 0, 0);
+        T[g][h][q] = x[0];
+        if (q < 3) T[g][h] = __builtin_amdgcn_mfma_f64_16x16x4f64(bop, T[g][h][q], T[g][h], 0, 0, 0);
+      }
+      {
+        const double4_t x = __builtin_amdgcn_mfma_f64_16x16x4f64(aop_e, E[g][q], double4_t{0, 0, 0, 0}, 0, 0, 0);
+        E[g][q] = x[0];
+        if (q < 3) E[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(bop_e, E[g][q], E[g], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int g2 = g + 1; g2 < 3; g2++)
+#pragma unroll
+      for (int h = g2; h < 3; h++)
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+          const double aneg = (16 * g + 4 * s + kk < nft) ? -T[g][g2][s] : 0.0;  // frontal rows only
+          T[g2][h] = __builtin_amdgcn_mfma_f64_16x16x4f64(aneg, T[g][h][s], T[g2][h], 0, 0, 0);
+        }
+  }
+  return failed;
+}
+
 __global__ __launch_bounds__(256) void front_tail_kernel(double* __restrict__ A, int ld, int n, int nf, int p0, int kp, int front_id,
                                                          int* __restrict__ status, double* __restrict__ inv16) {
+  __shared__ double part[3][24][64];  // the K-quarters of waves 1..3: [tile * 4 + register][lane]
+  const int r0 = p0 + kp, m = n - r0, nft = nf - r0;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kk = lane >> 4, cc = lane & 15;
+  // ---- operands: rows [64 wave, 64 wave + 64) of the panel, zero beyond kp rows / m columns (the address stays inside the panel).
+  // (dense_front_schedule only issues a DENSE_TAIL behind a full panel, kp = 256; the row mask keeps the kernel to its own contract kp <= 256)
+  const double* P = A + (size_t)p0 * ld + r0;
+  double pv[16][3];
+#pragma unroll
+  for (int s = 0; s < 16; s++)
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+      const int row = 64 * wave + 4 * s + kk, col = 16 * t + cc;
+      const double v = P[(size_t)min(row, kp - 1) * ld + min(col, m - 1)];
+      pv[s][t] = (row < kp && col < m) ? v : 0.0;
+    }
+  // the block itself (wave 0 only): upper triangle, zero elsewhere
+  double4_t T[3][3];
+  double* C = A + (size_t)r0 * ld + r0;
+  if (wave == 0) {
+#pragma unroll
+    for (int g = 0; g < 3; g++)
+#pragma unroll
+      for (int h = g; h < 3; h++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int row = 16 * g + kk + 4 * r, col = 16 * h + cc;
+          const double v = C[(size_t)min(row, m - 1) * ld + min(col, m - 1)];
+          T[g][h][r] = (row < m && col < m && col >= row) ? v : 0.0;
+        }
+  }
+  // ---- this wave's K-quarter of P^T P
+  double4_t acc[6];
+#pragma unroll
+  for (int x = 0; x < 6; x++) acc[x] = double4_t{0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < 16; s++) {
+    int x = 0;
+#pragma unroll
+    for (int ti = 0; ti < 3; ti++)
+#pragma unroll
+      for (int tj = ti; tj < 3; tj++, x++) acc[x] = __builtin_amdgcn_mfma_f64_16x16x4f64(pv[s][ti], pv[s][tj], acc[x], 0, 0, 0);
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int x = 0; x < 6; x++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) part[wave - 1][4 * x + r][lane] = acc[x][r];
+  }
+  __syncthreads();
+  if (wave > 0) return;
+  {
+    int x = 0;
+#pragma unroll
+    for (int g = 0; g < 3; g++)
+#pragma unroll
+      for (int h = g; h < 3; h++, x++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          T[g][h][r] -= ((acc[x][r] + part[0][4 * x + r][lane]) + part[1][4 * x + r][lane]) + part[2][4 * x + r][lane];
+  }
+  // ---- factor the nft frontal columns, update what is right of them
+  double4_t E[3];
+  bool failed = potrf48_partial_wave(T, E, nft);
+  // pivot-exponent test, gtsam/base/cholesky.cpp:146-158: R[p][p] is register (p & 15) >> 2 of lane 16 (p & 3) + (p & 15) of tile (p >> 4, p >> 4)
+  {
+    const int p1 = nft - 1, p2 = max(nft - 2, 0);
+    double v1 = 0.0, v2 = 0.0;
+#pragma unroll
+    for (int g = 0; g < 3; g++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        v1 = ((p1 >> 4) == g && ((p1 & 15) >> 2) == r) ? T[g][g][r] : v1;
+        v2 = ((p2 >> 4) == g && ((p2 & 15) >> 2) == r) ? T[g][g][r] : v2;
+      }
+    const double r1 = __shfl(v1, 16 * (p1 & 3) + (p1 & 15), 64);
+    if (nft >= 2) {
+      const double r2 = __shfl(v2, 16 * (p2 & 3) + (p2 & 15), 64);
+      if (!(frexp_exp_d(r2) - frexp_exp_d(r1) < 12)) failed = true;
+    } else if (nf >= 2) {
+      if (!(frexp_exp_d(A[(size_t)(nf - 2) * ld + nf - 2]) - frexp_exp_d(r1) < 12)) failed = true;
+    } else if (!(frexp_exp_d(r1) > -12)) {
+      failed = true;
+    }
+  }
+  if (failed && lane == 0) atomicMin(status, front_id);
+  // ---- R, the update matrix and the inverses (the fourth 16 x 16 block of the 64-row panel is all padding: identity)
+#pragma unroll
+  for (int g = 0; g < 3; g++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = 16 * g + kk + 4 * r;
+#pragma unroll
+      for (int h = g; h < 3; h++) {
+        const int col = 16 * h + cc;
+        if (row < m && col < m && col >= row) C[(size_t)row * ld + col] = T[g][h][r];
+      }
+      inv16[(size_t)g * 256 + cc * 16 + kk + 4 * r] = E[g][r];
+    }
+#pragma unroll
+  for (int r = 0; r < 4; r++) inv16[(size_t)3 * 256 + cc * 16 + kk + 4 * r] = (kk + 4 * r == cc) ? 1.0 : 0.0;
+}
+
+#ifdef LMGPU_TEST_HOOKS
+// the scalar form (test library only, LMGPU_TAIL_SCALAR=1): the panel's columns and the trailing block staged in LDS, C -= P^T P with
+// scalar FMAs, a right-looking partial Cholesky in LDS with two barriers per pivot, the inverses by substitution
+#define TAIL_LDS_BYTES ((TAIL_MAX_KP * TAIL_MAX_M + TAIL_MAX_M * TAIL_MAX_M + 64 * 65) * 8)
+__global__ __launch_bounds__(256) void front_tail_scalar_kernel(double* __restrict__ A, int ld, int n, int nf, int p0, int kp, int front_id,
+                                                                int* __restrict__ status, double* __restrict__ inv16) {
   extern __shared__ double tsm[];
   const int r0 = p0 + kp, m = n - r0, nft = nf - r0, tid = threadIdx.x;
   double* Pl = tsm;                               // [kp][m]
@@ -478,6 +698,7 @@ __global__ __launch_bounds__(256) void front_tail_kernel(double* __restrict__ A,
     for (int i = 0; i < 16; i++) inv16[(size_t)blk * 256 + i * 16 + c] = x[i];
   }
 }
+#endif  // LMGPU_TEST_HOOKS
 
 // ---------------------------------------------------------------- the same outer panel as ONE dataflow launch
 // Workgroup b < nblk owns block column b of the diagonal block (and factors diagonal tile b); the others own 64 columns

@@ -299,11 +299,13 @@ struct lmgpu_handle {
   int wide16_max = 256;                        // launches of at most this many wide LDS fronts take sixteen waves per front (LMGPU_WIDE16_MAX)
   bool bsd_ticket = false;                     // LMGPU_BSD_TICKET=1: the block back-substitution always draws tickets (tests: the path of levels with more blocks than CUs)
   bool no_tail = false;                        // LMGPU_NO_TAIL=1: the end of a front as separate update / panel launches (A/B)
+  bool tail_scalar = false;                    // LMGPU_TAIL_SCALAR=1: front_tail_scalar_kernel, the LDS / scalar-FMA form (cross-check)
   bool no_chain = false;                       // LMGPU_NO_CHAIN=1: one launch per fused step instead of one per run of steps (A/B)
   int chain_forms = 0;                         // test library: CHAIN_FORM_* bits (LMGPU_CHAIN_FENCED_TILES, LMGPU_CHAIN_PREREAD; kernels_step.hpp)
   unsigned int* d_pflags = nullptr;            // hand-off flags of panel_dataflow_kernel, PDF_FLAG_WORDS per outer panel
   int pflags_panels = 0;
   unsigned int* bs_flags = nullptr;
+  bool pflags_prefilled = false, bs_prefilled = false;  // their clears are entries of the elimination's fill table (ensure_fill_tables)
   double* pool = nullptr;
   size_t pool_doubles = 0;
   double* vals[2][kNumVarTypes] = {};
@@ -702,12 +704,22 @@ static void add_fill(std::vector<FillChunk>& t, const void* p, size_t bytes, uin
 
 // own factors and children's update matrices of HBM front fi, assembled at pool offset aoff: one wave per row of the front walks that
 // row's sources in a fixed order (no atomics, bitwise reproducible); with_factors = false on the ranks that leave the own terms to rank 0
-static void launch_assemble_rows(lmgpu_handle* h, int fi, int64_t aoff, bool with_factors) {
+// Returns whether the launch was made.  damp: the wave that owns a frontal row also adds that row's damping term (and gex) behind the
+// row's last source -- what hbm_damp_kernel adds behind this launch, the same additions in the same order, without the launch.
+static bool launch_assemble_rows(lmgpu_handle* h, int fi, int64_t aoff, bool with_factors, bool damp = false, double lambda_v = 0.0,
+                                 const double* lambda_p = nullptr) {
   const FrontDesc& F = h->h_fronts[fi];
-  if (h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))
+  if (!(h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))) return false;
+  if (damp)
+    hipLaunchKernelGGL(hbm_assemble_rows_damp_kernel, dim3((F.n + 3) / 4), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi],
+                       (const int32_t*)(h->d_rowptr + h->row_begin[fi]), (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
+                       (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0, (const int32_t*)h->d_fxoff, lambda_v, lambda_p,
+                       (const double*)h->dampw, (const double*)h->gex_active);
+  else
     hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((F.n + 3) / 4), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi], (const int32_t*)(h->d_rowptr + h->row_begin[fi]),
                        (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const FrontFac*)h->d_ffac,
                        (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0);
+  return true;
 }
 
 static void launch_hbm_damp(lmgpu_handle* h, int fi, int64_t aoff, double lambda_v, const double* lambda_p) {
@@ -838,6 +850,27 @@ static int ensure_fill_tables(lmgpu_handle* h) {
       add_fill(fills, h->d_bs_done, (size_t)(h->h_fronts.size() + h->levels.size() + 1) * sizeof(unsigned int), 0u);
     if (h->fuse_levels) add_fill(fills, h->d_level_sync, (size_t)h->n_level_sync * sizeof(LevelSync), 0u);
     if (regime == HBM_CLEAR_SPAN) add_fill(fills, h->pool + lo, (size_t)(hi - lo) * sizeof(double), 0u);
+    // The hand-off flags of the per-front dense path (d_pflags) and the flags and sentinels of the dataflow back-substitution of a
+    // front of more than BSS_MAX_NF rows (bs_flags, bs_x) are touched by that front's own launches only.  When ONE front of a solve
+    // uses them (a root behind point leaves), their clears ride in this launch instead of a memset command each in front of the
+    // front; with several such fronts every front clears the buffers in front of its own launches, as before.  do_eliminate and
+    // do_backsub only ever run as the pair of solve_sequence (eager or replayed, gex or not), so the head of the elimination is in
+    // front of every use.
+    int n_plan = 0, n_wide = 0, plan_fi = -1, wide_fi = -1;
+    for (const LevelWork& L : h->levels)
+      for (int fi : L.hbm) {
+        if (!h->is_med[fi]) n_plan++, plan_fi = fi;
+        if (h->h_fronts[fi].nf > BSS_MAX_NF) n_wide++, wide_fi = fi;
+      }
+    h->pflags_prefilled = n_plan == 1;
+    h->bs_prefilled = n_wide == 1;
+    if (h->pflags_prefilled)
+      add_fill(fills, h->d_pflags, (size_t)((h->h_fronts[plan_fi].nf + NBO - 1) / NBO + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), 0u);
+    if (h->bs_prefilled) {  // (sized for the 64-row and the 128-row form alike: the flags of the former, the whole blocks of the latter)
+      const int nf = h->h_fronts[wide_fi].nf;
+      add_fill(fills, h->bs_flags, (size_t)((nf + NB - 1) / NB + 1) * sizeof(unsigned int), 0u);
+      add_fill(fills, h->bs_x, (size_t)((nf + BSW_NB - 1) / BSW_NB) * BSW_NB * sizeof(double), 0xffffffffu);  // "not published yet"
+    }
     h->n_fill_elim = (int)fills.size();
     const int rcu = upload(h, &h->d_fill_elim, fills);
     if (rcu) return rcu;
@@ -1016,8 +1049,9 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
       const bool gwrite = gather_writes(h, fi);
       if (gwrite && G.zero_count > 0)
         hipLaunchKernelGGL(zero_blocks_kernel, dim3(G.zero_count), dim3(128), 0, s, (const GZeroBlock*)(h->d_gzero + G.zero_begin), h->pool, aoff, ld);
-      launch_assemble_rows(h, fi, aoff, own_terms && !gwrite);
-      if (!gwrite && own_terms) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
+      // (the damping rides in the row assembly where there is one; a front without sources here keeps hbm_damp_kernel)
+      const bool damp_here = !gwrite && own_terms;
+      if (!launch_assemble_rows(h, fi, aoff, own_terms && !gwrite, damp_here, lambda_v, lambda_p) && damp_here) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
       // leaf children in Schur form: deterministic gather instead of atomics
       const int schur_masked = dev_switch("LMGPU_SCHUR_UNMASKED") ? 0 : 2;  // (operand loads that only the lanes holding an element take part in)
       // (LMGPU_SCHUR_UNMASKED reaches schur_pairs_kernel and the split form's schur_factor_kernel; schur_var_kernel has the masked loads only)
@@ -1055,8 +1089,8 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
                              gwrite ? 1 : 0, (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
       }
       if (gwrite && own_terms) {  // the front's own factors and the damping are added: after the gather has initialised the entries
-        if (F.fac_count > 0) launch_assemble_rows(h, fi, aoff, true);  // (a gather-write front has no update-matrix children: only its factors are added here)
-        launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
+        // (a gather-write front has no update-matrix children: only its factors are added here, the damping behind them in the same launch)
+        if (!(F.fac_count > 0 && launch_assemble_rows(h, fi, aoff, true, true, lambda_v, lambda_p))) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
       }
       h->kt.end(kt, s);
       if (mode == DENSE_SPLIT_EVENTS) {  // RCCL: all chunks queued on the communication stream, one event each
@@ -1089,7 +1123,7 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
         switch (st.kind) {
           case DENSE_PANEL_DATAFLOW:
           case DENSE_PANEL_TWO_LAUNCH: {
-            if (i == 0) HIPCHECK(hipMemsetAsync(h->d_pflags, 0, (size_t)((F.nf + NBO - 1) / NBO + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), s));
+            if (i == 0 && !h->pflags_prefilled) HIPCHECK(hipMemsetAsync(h->d_pflags, 0, (size_t)((F.nf + NBO - 1) / NBO + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), s));
             double* inv16 = h->inv16 + (size_t)i * 4096;
             const int ktp = h->kt.begin(LMGPU_KT_PANEL, s);
             if (st.kind == DENSE_PANEL_DATAFLOW) {
@@ -1141,7 +1175,13 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
           }
           case DENSE_TAIL: {
             const int ktt = h->kt.begin(LMGPU_KT_PANEL, s);
-            hipLaunchKernelGGL(front_tail_kernel, dim3(1), dim3(256), TAIL_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
+#ifdef LMGPU_TEST_HOOKS
+            if (h->tail_scalar)
+              hipLaunchKernelGGL(front_tail_scalar_kernel, dim3(1), dim3(256), TAIL_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
+                                 h->inv16 + (size_t)(i + 1) * 4096);
+            else
+#endif
+            hipLaunchKernelGGL(front_tail_kernel, dim3(1), dim3(256), 0, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
                                h->inv16 + (size_t)(i + 1) * 4096);
             h->kt.end(ktt, s, st.flop);
             break;
@@ -1299,8 +1339,10 @@ int do_backsub(lmgpu_handle* h) {
       const bool reuse = h->inv16_owner == fi && !dev_switch("LMGPU_NO_INV16_REUSE");
       const bool wide = reuse && !dev_switch("LMGPU_BACKSOLVE_HOP64");
       const int bw = wide ? BSW_NB : NB, nblk = (F.nf + bw - 1) / bw;
-      HIPCHECK(hipMemsetAsync(h->bs_flags, 0, (nblk + 1) * sizeof(unsigned int), s));  // flags + ticket
-      HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * bw * sizeof(double), s));  // sentinel: "not published yet"
+      if (!h->bs_prefilled) {  // (else cleared by the fill launch at the head of the elimination: ensure_fill_tables)
+        HIPCHECK(hipMemsetAsync(h->bs_flags, 0, (nblk + 1) * sizeof(unsigned int), s));  // flags + ticket
+        HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * bw * sizeof(double), s));  // sentinel: "not published yet"
+      }
       if (wide) {
         hipLaunchKernelGGL((hbm_backsolve_wide_kernel<false>), dim3(nblk), dim3(512), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
                            (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
@@ -1626,14 +1668,24 @@ int do_solve(lmgpu_handle* h, double lambda) {
 
 int do_retract(lmgpu_handle* h, int from, int to) {
   h->marg_valid = false;
+  static_assert(kNumVarTypes <= 7, "RetractMulti holds seven entries");
+  RetractMulti rm{};  // the variable types present, one launch (blockIdx.y = entry; retract_body is retract_kernel's)
+  int ne = 0, maxn = 0;
   for (int t = 0; t < kNumVarTypes; t++) {
     // the hidden points of smart factors are the first POINT3 variables: never retracted (their value is the cache's, smart.hpp)
     const int skip = t == LMGPU_POINT3 ? h->n_hidden : 0;
     const int n = h->plan.type_count[t] - skip;
     if (n == 0) continue;
-    hipLaunchKernelGGL(retract_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, t, n, (const double*)h->vals[from][t] + 3 * skip,
-                       h->vals[to][t] + 3 * skip, (const int32_t*)h->type_xoff[t] + skip, (const double*)h->delta, (const int32_t*)nullptr);
+    rm.type[ne] = t;
+    rm.n[ne] = n;
+    rm.cur[ne] = (const double*)h->vals[from][t] + 3 * skip;
+    rm.out[ne] = h->vals[to][t] + 3 * skip;
+    rm.xoff[ne] = (const int32_t*)h->type_xoff[t] + skip;
+    rm.sel[ne] = nullptr;
+    maxn = std::max(maxn, n);
+    ne++;
   }
+  if (ne > 0) hipLaunchKernelGGL(retract_multi_kernel, dim3((maxn + 255) / 256, ne), dim3(256), 0, h->stream, rm, (const double*)h->delta);
   HIPCHECK(hipGetLastError());
   return LMGPU_OK;
 }
@@ -2078,6 +2130,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   h->no_chain = dev_switch("LMGPU_NO_CHAIN") != nullptr;
   h->chain_forms = (dev_switch("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (dev_switch("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
   h->no_tail = dev_switch("LMGPU_NO_TAIL") != nullptr;
+  h->tail_scalar = dev_switch("LMGPU_TAIL_SCALAR") != nullptr;
   h->no_wide16 = dev_switch("LMGPU_NO_WIDE16") != nullptr;
   if (const char* e = dev_switch("LMGPU_LEAF_GROUP_THREADS")) h->leaf_group_threads = atoi(e) == 64 ? 64 : (atoi(e) == 128 ? 128 : 256);
   h->no_backsub_groups = dev_switch("LMGPU_NO_BACKSUB_GROUPS") != nullptr;
@@ -2124,7 +2177,9 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
     HIPCHECK(hipFuncSetAttribute((const void*)panel_dataflow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PDF_LDS_BYTES));
     HIPCHECK(hipFuncSetAttribute((const void*)step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS_BYTES));
     HIPCHECK(hipFuncSetAttribute((const void*)chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS_BYTES));
-    HIPCHECK(hipFuncSetAttribute((const void*)front_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_BYTES));
+#ifdef LMGPU_TEST_HOOKS
+    HIPCHECK(hipFuncSetAttribute((const void*)front_tail_scalar_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_BYTES));
+#endif
     HIPCHECK(hipFuncSetAttribute((const void*)med_diag_potrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
   }
   return LMGPU_OK;
@@ -2534,7 +2589,8 @@ int lmgpu_restore_values(lmgpu_handle* h) {
   if (rc) return rc;
   h->marg_valid = false;
   for (int t = 0; t < kNumVarTypes; t++) {
-    const size_t bytes = std::max<size_t>(1, (size_t)h->plan.type_count[t] * kVarStore[t]) * sizeof(double);
+    if (h->plan.type_count[t] == 0) continue;  // (a type the graph does not have: its buffers are one unused double each, nothing to restore)
+    const size_t bytes = (size_t)h->plan.type_count[t] * kVarStore[t] * sizeof(double);
     HIPCHECK(hipMemcpyAsync(h->vals[h->cur][t], h->saved[t], bytes, hipMemcpyDeviceToDevice, h->stream));
   }
   return LMGPU_OK;
