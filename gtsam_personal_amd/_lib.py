@@ -269,6 +269,13 @@ SYMBOLS = {
     "lmgpu_isam2_get_value": (ct.c_int, [_H, ct.c_int32, ct.c_uint64, _I, _D]),
     "lmgpu_isam2_get_delta": (ct.c_int, [_H, _D]),
     "lmgpu_isam2_marginal_covariance": (ct.c_int, [_H, ct.c_uint64, _D]),
+    "lmgpu_isam2_marginal_covariances": (ct.c_int, [_H, ct.c_int32, ct.POINTER(ct.c_uint64), _D]),
+    "lmgpu_isam2_cross_covariances": (ct.c_int, [_H, ct.c_int32, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint64), _D]),
+    "lmgpu_isam2_joint_marginal_covariances": (ct.c_int, [_H, ct.c_int32, _I, ct.POINTER(ct.c_uint64), _D]),
+    "lmgpu_isam2_marginals_path": (ct.c_int, [_H, ct.c_uint64, ct.POINTER(ct.c_uint64), ct.c_int32]),
+    "lmgpu_isam2_marginals_junction": (ct.c_int, [_H, ct.c_uint64, ct.c_uint64, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_isam2_set_marginals_params": (ct.c_int, [_H, ct.c_int64, ct.c_int32, ct.c_int32]),
+    "lmgpu_isam2_get_marginals_stats": (ct.c_int, [_H, ct.POINTER(lmgpu_marginals_stats)]),
     "lmgpu_isam2_num_cliques": (ct.c_int, [_H]),
     "lmgpu_isam2_clique_info": (ct.c_int, [_H, ct.c_int32, _I]),
     "lmgpu_isam2_get_clique": (ct.c_int, [_H, ct.c_int32, ct.POINTER(ct.c_uint64), _D]),

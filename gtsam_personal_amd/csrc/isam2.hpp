@@ -227,6 +227,17 @@ struct lmgpu_isam2 {
   size_t tree_lds = 0;           // largest nf x (n | 1) of a clique: doubles of LDS the wildfire kernel stages
   // taps
   std::vector<int32_t> snap;
+  // marginals of many variables, cross-covariances, joint marginals (isam2_marginals.hpp): parameters, counters and
+  // the two device buffers of a chunk -- the blocks with the workgroups' status words behind them, and the work vectors too long for LDS.
+  // The position tables are built per call from clq[], so nothing here can go stale when the tree changes.
+  struct MargQ {
+    int64_t scratch_bytes = 64ll << 20;
+    int32_t lds_doubles = 6144, cross_cap = 0;  // cross_cap 0: the built-in rule of the batch route
+    lmgpu_marginals_stats stats{};
+    double *d_out = nullptr, *d_scratch = nullptr;
+    size_t out_cap = 0, scratch_cap = 0;
+    bool attr_set = false;
+  } mq;
 };
 
 // the pending pushes of an update: record i = words 4-byte words from the device staging arena to their place in a persistent array
@@ -2856,7 +2867,8 @@ int lmgpu_isam2_destroy(lmgpu_isam2* S) {
     }
     for (void* p : {(void*)S->delta, (void*)S->ones, (void*)S->d_replaced, (void*)S->d_changed, (void*)S->pool, (void*)S->d_status, (void*)S->d_gpart, (void*)S->d_tree,
                     (void*)S->d_tree_fx, (void*)S->d_tree_sx, (void*)S->d_tree_done, (void*)S->d_queue, (void*)S->d_wl, (void*)S->inv16, (void*)S->d_eticket, (void*)S->d_marg, (void*)S->d_ebuf,
-                    (void*)S->d_epart, (void*)S->delta_newton, (void*)S->rgprod, (void*)S->grad, (void*)S->dx_u, (void*)S->d_cerr, (void*)S->d_dlscal})
+                    (void*)S->d_epart, (void*)S->delta_newton, (void*)S->rgprod, (void*)S->grad, (void*)S->dx_u, (void*)S->d_cerr, (void*)S->d_dlscal,
+                    (void*)S->mq.d_out, (void*)S->mq.d_scratch})
       if (p) (void)hipFree(p);
     if (S->h_status) (void)hipHostFree(S->h_status);
     if (S->h_val) (void)hipHostFree(S->h_val);

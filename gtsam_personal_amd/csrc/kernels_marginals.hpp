@@ -33,17 +33,28 @@ struct MargReq {
   int64_t out;      // offset (doubles) of its dim x dim block in the chunk's output
 };
 
+// one front of a walk as the two bodies below see it: [R S] (upper; n1 = scalar columns without the right-hand side, nf of them frontal,
+// row stride ld), p0 = the path position of its first frontal scalar, sp[] = the path positions of its separator scalars.  The batch route
+// reads it from its static tables (mp_front_of), ISAM2 from its device tree and the tables of the request (kernels_isam2_marginals.hpp).
+struct MpFront {
+  int n1, nf, ld, p0;
+  const double* A;
+  const int32_t* sp;
+};
+__device__ __forceinline__ MpFront mp_front_of(const int f, const FrontDesc* __restrict__ fronts, const int32_t* __restrict__ poff,
+                                               const int32_t* __restrict__ spos, const double* __restrict__ pool) {
+  const FrontDesc F = fronts[f];
+  return MpFront{F.n - 1, F.nf, F.ld_rsd, poff[f], pool + F.rsd_off, spos + F.sx_begin};
+}
+
 // one front of the way up: R^T y_F = b_F, b_S -= S^T y_F (shared by the path walk and the cross walk: the same operations in the same
 // order, so a variable's block has the same bits from both)
 template <int DP>
-__device__ __forceinline__ void mp_front_up(const int f, const FrontDesc* __restrict__ fronts, const int32_t* __restrict__ poff,
-                                            const int32_t* __restrict__ spos, const double* __restrict__ pool, double* __restrict__ W,
-                                            double* __restrict__ yb) {
+__device__ __forceinline__ void mp_front_up(const MpFront V, double* __restrict__ W, double* __restrict__ yb) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const FrontDesc F = fronts[f];
-  const int n1 = F.n - 1, nf = F.nf, ld = F.ld_rsd, p0 = poff[f];
-  const double* A = pool + F.rsd_off;
-  const int32_t* sp = spos + F.sx_begin;
+  const int n1 = V.n1, nf = V.nf, ld = V.ld, p0 = V.p0;
+  const double* __restrict__ A = V.A;
+  const int32_t* __restrict__ sp = V.sp;
   for (int r0 = 0; r0 < nf; r0 += MP_BS) {
     const int bs = min(MP_BS, nf - r0);
     if (wave == 0) {
@@ -100,14 +111,11 @@ __device__ __forceinline__ void mp_front_up(const int f, const FrontDesc* __rest
 
 // one front of the way down: x_F = R^-1 (y_F - S x_S)
 template <int DP>
-__device__ __forceinline__ void mp_front_down(const int f, const FrontDesc* __restrict__ fronts, const int32_t* __restrict__ poff,
-                                              const int32_t* __restrict__ spos, const double* __restrict__ pool, double* __restrict__ W,
-                                              double* __restrict__ yb) {
+__device__ __forceinline__ void mp_front_down(const MpFront V, double* __restrict__ W, double* __restrict__ yb) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const FrontDesc F = fronts[f];
-  const int n1 = F.n - 1, nf = F.nf, ld = F.ld_rsd, p0 = poff[f];
-  const double* A = pool + F.rsd_off;
-  const int32_t* sp = spos + F.sx_begin;
+  const int n1 = V.n1, nf = V.nf, ld = V.ld, p0 = V.p0;
+  const double* __restrict__ A = V.A;
+  const int32_t* __restrict__ sp = V.sp;
   for (int r0 = ((nf - 1) / MP_BS) * MP_BS; r0 >= 0; r0 -= MP_BS) {
     const int bs = min(MP_BS, nf - r0);
     // t_i = y_i - sum_{k right of the block} A[r0 + i][k] x_k: a wave per row, lanes along the row
@@ -185,11 +193,11 @@ __device__ __forceinline__ void marginal_path_walk(const MargReq rq, const Front
   int npath = 0;
   for (int f = rq.front; f >= 0; f = parent[f], npath++) {
     if (tid == 0) pathv[npath] = f;
-    mp_front_up<DP>(f, fronts, poff, spos, pool, W, yb);
+    mp_front_up<DP>(mp_front_of(f, fronts, poff, spos, pool), W, yb);
   }
 
   // ---- down: x_F = R^-1 (y_F - S x_S), from the root back to the variable's front
-  for (int q = npath - 1; q >= 0; q--) mp_front_down<DP>(pathv[q], fronts, poff, spos, pool, W, yb);
+  for (int q = npath - 1; q >= 0; q--) mp_front_down<DP>(mp_front_of(pathv[q], fronts, poff, spos, pool), W, yb);
 
   // ---- the variable's block, symmetrised (the two triangles differ by rounding only); a non-finite entry: a singular front on the path
   const int d = rq.dim, pv = poff[rq.front] + rq.col;
@@ -258,9 +266,9 @@ __device__ __forceinline__ void marginal_cross_walk(const CrossReq rq, const Cro
   int npath = 0;
   for (int f = rq.front; f >= 0; f = parent[f], npath++) {
     if (tid == 0) pathv[npath] = f;
-    mp_front_up<DP>(f, fronts, poff, spos, pool, W, yb);
+    mp_front_up<DP>(mp_front_of(f, fronts, poff, spos, pool), W, yb);
   }
-  for (int q = npath - 1; q >= 0; q--) mp_front_down<DP>(pathv[q], fronts, poff, spos, pool, W, yb);
+  for (int q = npath - 1; q >= 0; q--) mp_front_down<DP>(mp_front_of(pathv[q], fronts, poff, spos, pool), W, yb);
 
   // ---- the targets, deepest junction first
   int32_t* branchv = pathv + npath;
@@ -279,7 +287,7 @@ __device__ __forceinline__ void marginal_cross_walk(const CrossReq rq, const Cro
       for (int f = T.front; f >= 0 && f != T.junction; f = parent[f], nb++)
         if (tid == 0) branchv[nb] = f;
       __syncthreads();
-      for (int q = nb - 1; q >= 0; q--) mp_front_down<DP>(branchv[q], fronts, poff, spos, pool, W, yb);
+      for (int q = nb - 1; q >= 0; q--) mp_front_down<DP>(mp_front_of(branchv[q], fronts, poff, spos, pool), W, yb);
     }
     const int pv = poff[T.front] + T.col;
     if (tid < cells) {

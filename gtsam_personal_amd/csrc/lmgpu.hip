@@ -42,6 +42,7 @@
 #include "kernels_gnc.hpp"
 #include "kernels_ncg.hpp"
 #include "kernels_marginals.hpp"
+#include "kernels_isam2_marginals.hpp"
 #include "plan.hpp"
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
@@ -3943,6 +3944,7 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 #include "ncg.hpp"
 #include "triangulation.hpp"
 #include "marginals.hpp"
+#include "isam2_marginals.hpp"  // (after both: ISAM2's handle and staging, the batch route's chunking constants)
 #include "smart.hpp"
 
 #ifdef LDSF_STAMPS  // development aid: tools/ldsf_phases.py

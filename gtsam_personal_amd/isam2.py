@@ -107,6 +107,7 @@ class ISAM2:
             o = p.optimizationParams
             self._check(self.lib.lmgpu_isam2_set_dogleg(self._h, float(o.initialDelta), float(o.wildfireThreshold), int(o.adaptationMode)))
         self._u0v0 = {}  # constant principal points of Cal3Bundler cameras (do not travel, see lmgpu.h CAM_BUNDLER)
+        self._var_dim = {}  # key -> scalars, of every variable ever added (the shapes of the marginal blocks; the library refuses a gone key)
 
     def _check(self, rc):
         if rc == _lib.LMGPU_OK:
@@ -141,6 +142,7 @@ class ISAM2:
             types = np.array([newTheta.type(k) for k in newTheta.keys()], dtype=np.int32)
             packed = np.concatenate([newTheta.at(k)[:VAR_STORE_DEV[newTheta.type(k)]] for k in newTheta.keys()]).astype(np.float64)
             for k in newTheta.keys():
+                self._var_dim[int(k)] = VAR_DIM[newTheta.type(k)]
                 if newTheta.type(k) == 3:
                     self._u0v0[k] = newTheta.at(k)[15:17].copy()
             self._check(self.lib.lmgpu_isam2_add_variables(self._h, len(keys), keys.ctypes.data_as(U64), types.ctypes.data_as(_lib._I),
@@ -197,6 +199,87 @@ class ISAM2:
         cov = np.zeros((d, d))
         self._check(self.lib.lmgpu_isam2_marginal_covariance(self._h, int(key), cov.ctypes.data_as(_lib._D)))
         return cov
+
+    # ---- many marginals, cross-covariances and joint marginals from the present tree, one launch per chunk of requests (lmgpu.h:
+    #      lmgpu_isam2_marginal_covariances ...).  Like marginalCovariance these are blocks of (R^T R)^-1 of the tree
+    #      the last update left: the covariance at the linearization point.
+    def _dims_of(self, keys):
+        try:
+            return [self._var_dim[k] for k in keys]
+        except KeyError as e:
+            raise _lib.LmgpuError(f"ISAM2: key {e.args[0]} was never added to this ISAM2") from None
+
+    def marginalCovariances(self, keys=None) -> dict:
+        """{key: marginalCovariance(key)} for `keys` (every live variable when None), one request"""
+        U64 = ct.POINTER(ct.c_uint64)
+        if keys is None:
+            n = self.lib.lmgpu_isam2_num_variables(self._h)
+            live = np.zeros(max(n, 1), dtype=np.uint64)
+            self._check(self.lib.lmgpu_isam2_get_values(self._h, 2, live.ctypes.data_as(U64), None, None))
+            keys = live[:n].tolist()
+        keys = [int(k) for k in keys]
+        dims = self._dims_of(keys)
+        off = np.concatenate([[0], np.cumsum([d * d for d in dims])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        kk = np.asarray(keys, dtype=np.uint64)
+        self._check(self.lib.lmgpu_isam2_marginal_covariances(self._h, len(keys), kk.ctypes.data_as(U64), out.ctypes.data_as(_lib._D)))
+        return {k: out[off[i]:off[i + 1]].reshape(dims[i], dims[i]).copy() for i, k in enumerate(keys)}
+
+    def crossCovariances(self, pairs) -> dict:
+        """{(ki, kj): Sigma[ki, kj]} (dim_i x dim_j): kj is the source whose path is walked, each ki costs the descent of its branch
+        below the junction of the two paths"""
+        U64 = ct.POINTER(ct.c_uint64)
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        shape = list(zip(self._dims_of([a for a, _ in pairs]), self._dims_of([b for _, b in pairs])))
+        off = np.concatenate([[0], np.cumsum([r * c for r, c in shape])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        ki, kj = np.asarray([a for a, _ in pairs], dtype=np.uint64), np.asarray([b for _, b in pairs], dtype=np.uint64)
+        self._check(self.lib.lmgpu_isam2_cross_covariances(self._h, len(pairs), ki.ctypes.data_as(U64), kj.ctypes.data_as(U64),
+                                                           out.ctypes.data_as(_lib._D)))
+        return {pr: out[off[q]:off[q + 1]].reshape(shape[q]).copy() for q, pr in enumerate(pairs)}
+
+    def jointMarginalCovariances(self, list_of_key_lists) -> list:
+        """[jointMarginalCovariance(keys) for keys in list_of_key_lists] in one request; blocks ordered by Key like
+        JointMarginal::fullMatrix, each matrix exactly symmetric"""
+        from .optimizer import JointMarginal
+        sets = [sorted(int(k) for k in keys) for keys in list_of_key_lists]
+        begin = np.concatenate([[0], np.cumsum([len(ks) for ks in sets])]).astype(np.int32)
+        flat = np.asarray([k for ks in sets for k in ks], dtype=np.uint64)
+        dims = [self._dims_of(ks) for ks in sets]
+        off = np.concatenate([[0], np.cumsum([sum(d) ** 2 for d in dims])]).astype(np.int64)
+        out = np.zeros(max(int(off[-1]), 1))
+        self._check(self.lib.lmgpu_isam2_joint_marginal_covariances(self._h, len(sets), begin.ctypes.data_as(_lib._I),
+                                                                    flat.ctypes.data_as(ct.POINTER(ct.c_uint64)), out.ctypes.data_as(_lib._D)))
+        return [JointMarginal(ks, dims[q], out[off[q]:off[q + 1]].reshape(sum(dims[q]), sum(dims[q])).copy()) for q, ks in enumerate(sets)]
+
+    def jointMarginalCovariance(self, keys):
+        """the JointMarginal of Marginals::jointMarginalCovariance, from ISAM2's tree (BayesTree::joint without refactoring the graph)"""
+        return self.jointMarginalCovariances([keys])[0]
+
+    def marginals_stats(self) -> dict:
+        st = _lib.lmgpu_marginals_stats()
+        self._check(self.lib.lmgpu_isam2_get_marginals_stats(self._h, ct.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+    def set_marginals_params(self, scratch_bytes=0, lds_doubles=0, targets_per_workgroup=0):
+        """byte budget of the scratch buffer, longest work vector (doubles) kept in LDS, targets one workgroup serves after its walk of
+        a source's path; 0 keeps a value.  Results do not depend on them."""
+        self._check(self.lib.lmgpu_isam2_set_marginals_params(self._h, int(scratch_bytes), int(lds_doubles), int(targets_per_workgroup)))
+
+    def marginals_path(self, key):
+        """structure tap: the first frontal keys of the cliques from the one `key` is frontal in to its root; None when refused"""
+        n = self.lib.lmgpu_isam2_marginals_path(self._h, int(key), None, 0)
+        if n < 0:
+            return None
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        self.lib.lmgpu_isam2_marginals_path(self._h, int(key), out.ctypes.data_as(ct.POINTER(ct.c_uint64)), n)
+        return [int(k) for k in out[:n]]
+
+    def marginals_junction(self, key_i, key_j):
+        """structure tap: (1, first frontal key of the deepest clique on both paths), (0, None) for two trees, (-1, None) when refused"""
+        k = ct.c_uint64(0)
+        rc = self.lib.lmgpu_isam2_marginals_junction(self._h, int(key_i), int(key_j), ct.byref(k))
+        return rc, (int(k.value) if rc == 1 else None)
 
     def doglegDelta(self):
         """the current trust-region radius (ISAM2::doglegDelta_) with ISAM2DoglegParams"""

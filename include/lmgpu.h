@@ -853,6 +853,39 @@ int lmgpu_isam2_get_delta(lmgpu_isam2* s, double* packed); /* getDelta (:776-779
  * linearization point's covariance block of the variable, dim x dim): two triangular solves per column, on the device, along the path
  * from the variable's clique to its root.  LMGPU_INVALID for a variable that is not in the tree. */
 int lmgpu_isam2_marginal_covariance(lmgpu_isam2* s, uint64_t key, double* cov);
+/* ---- marginals of MANY variables, cross-covariances and joint marginals from the tree the last update left on the device (DESIGN section
+ *      19; BayesTree::joint, gtsam/inference/BayesTree.h:181-187, without refactoring the graph).  Nothing is re-linearized or re-eliminated:
+ *      the blocks are blocks of (R^T R)^-1 of the PRESENT tree, i.e. the covariance at the LINEARIZATION POINT, which is what
+ *      ISAM2::marginalCovariance gives.  The walk is lmgpu_marginal_covariances' / lmgpu_marginal_cross_covariances' (above): one
+ *      workgroup per source variable, up its path with R^T y = e, down again with R x = y, then down each target's branch below the
+ *      junction; the work vector holds the frontal scalars of the walked path only (LDS, or a slice of the scratch buffer).  One launch,
+ *      one download and one wait per chunk of requests.  Packing is that of the batch entries: row-major blocks back to back in request
+ *      order; a cross block is Sigma[i, j], dim_i x dim_j, the columns those of j, the source; a joint matrix is D_q x D_q with the blocks in
+ *      the order of the set's keys.  Duplicates are allowed in the first two calls, a key twice in one joint set is LMGPU_INVALID; n == 0
+ *      is LMGPU_OK.  LMGPU_INVALID, nothing written, the handle usable afterwards: a key that is not in the Bayes tree (never added, gone
+ *      with its last factor, marginalized), a NULL array that is needed, n < 0, set_begin that decreases or starts below 0, a single work
+ *      vector beyond scratch_bytes.  LMGPU_INDETERMINATE: a non-finite block (lmgpu_isam2_last_failed_key: the source of the first such
+ *      workgroup).  LMGPU_HIP_ERROR for n > 0 on a handle without a device.
+ *      A block's bits depend on its pair and the tree alone -- not on the rest of the request, its order, the chunking, LDS or scratch
+ *      placement, or targets_per_workgroup; the (i, i) cross block is bitwise the marginal_covariances block of i; a joint matrix is exactly
+ *      symmetric (an off-diagonal block is computed once, from the variable of the pair with the shorter path -- fewer scalars; ties: the
+ *      smaller key -- as the source, and mirrored); a pair across two trees of a forest gives exact zeros.
+ *      lmgpu_isam2_marginal_covariance above keeps its own route. ---- */
+int lmgpu_isam2_marginal_covariances(lmgpu_isam2* s, int32_t n, const uint64_t* keys, double* cov_packed);
+int lmgpu_isam2_cross_covariances(lmgpu_isam2* s, int32_t n, const uint64_t* keys_i, const uint64_t* keys_j, double* out_packed);
+int lmgpu_isam2_joint_marginal_covariances(lmgpu_isam2* s, int32_t n_sets, const int32_t* set_begin /* n_sets + 1 */, const uint64_t* keys,
+                                           double* cov_packed);
+/* structure taps (no device needed), cliques named by their first frontal key.  path: the cliques from the one `key` is frontal in to its
+ * root into first_frontal_keys_out[0 .. cap) (may be NULL); returns the path length, -1 refused.  junction: the deepest clique on both
+ * paths; returns 1 (and the clique), 0 when the keys lie in two trees of a forest, -1 refused. */
+int lmgpu_isam2_marginals_path(lmgpu_isam2* s, uint64_t key, uint64_t* first_frontal_keys_out, int32_t cap);
+int lmgpu_isam2_marginals_junction(lmgpu_isam2* s, uint64_t key_i, uint64_t key_j, uint64_t* first_frontal_key_out);
+/* as lmgpu_set_marginals_params + lmgpu_set_marginals_cross_cap (defaults 64 MiB, 6144 doubles, the built-in rule); 0 keeps a value.
+ * Results do not depend on any of the three. */
+int lmgpu_isam2_set_marginals_params(lmgpu_isam2* s, int64_t scratch_bytes, int32_t lds_doubles, int32_t targets_per_workgroup);
+/* lmgpu_marginals_stats over the handle's life: launches / chunks / vars_* / longest_path count lmgpu_isam2_marginal_covariances, the
+ * cross_* fields the other two calls; factorizations stays 0 */
+int lmgpu_isam2_get_marginals_stats(lmgpu_isam2* s, lmgpu_marginals_stats* out);
 /* parity taps: the Bayes tree depth-first from the roots (children in order).  lmgpu_isam2_num_cliques takes the snapshot the
  * other two index; info5: n_keys, n_frontal_keys, nf, n, parent (index in the snapshot, -1 root); RSd column-major nf x n */
 int lmgpu_isam2_num_cliques(lmgpu_isam2* s);

@@ -898,6 +898,54 @@ class GpuISAM2 {
     check(lmgpu_isam2_marginal_covariance(h_, key, cov.data()));
     return cov;
   }
+  /// the covariances of `variables`, in their order, from the present Bayes tree: one launch per chunk of requests, one workgroup per
+  /// variable (lmgpu_isam2_marginal_covariances).  Like marginalCovariance: the covariance at the linearization point.
+  std::vector<Matrix> marginalCovariances(const KeyVector& variables) const {
+    std::vector<uint64_t> keys(variables.begin(), variables.end());
+    size_t total = 0;
+    for (Key k : variables) total += dimOf(k) * dimOf(k);
+    std::vector<double> packed(std::max<size_t>(total, 1));
+    check(lmgpu_isam2_marginal_covariances(h_, (int32_t)keys.size(), keys.data(), packed.data()));
+    std::vector<Matrix> out;
+    out.reserve(keys.size());
+    size_t o = 0;
+    for (Key k : variables) {
+      const size_t d = dimOf(k);
+      out.push_back(Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(packed.data() + o, d, d));
+      o += d * d;
+    }
+    return out;
+  }
+  /// the joint marginal of distinct variables as BayesTree::joint / Marginals::jointMarginalCovariance shape it (blocks ordered by
+  /// Key), without refactoring the graph: every block from the present tree (lmgpu_isam2_joint_marginal_covariances), exactly symmetric
+  GpuJointMarginal jointMarginalCovariance(const KeyVector& variables) const {
+    KeyVector sorted(variables);
+    std::sort(sorted.begin(), sorted.end());
+    std::vector<uint64_t> keys(sorted.begin(), sorted.end());
+    std::vector<size_t> dims;
+    size_t D = 0;
+    for (Key k : sorted) {
+      dims.push_back(dimOf(k));
+      D += dims.back();
+    }
+    const int32_t begin[2] = {0, (int32_t)keys.size()};
+    std::vector<double> packed(std::max<size_t>(D * D, 1));
+    check(lmgpu_isam2_joint_marginal_covariances(h_, 1, begin, keys.data(), packed.data()));
+    return GpuJointMarginal(sorted, dims, Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(packed.data(), D, D));
+  }
+  /// Sigma[i, j], dim_i x dim_j: the path of j is walked, then the branch of i below the junction of the two paths
+  Matrix crossCovariance(Key i, Key j) const {
+    const size_t di = dimOf(i), dj = dimOf(j);
+    const uint64_t ki = i, kj = j;
+    std::vector<double> packed(di * dj);
+    check(lmgpu_isam2_cross_covariances(h_, 1, &ki, &kj, packed.data()));
+    return Eigen::Map<const Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>(packed.data(), di, dj);
+  }
+  lmgpu_marginals_stats marginalsStats() const {
+    lmgpu_marginals_stats st;
+    check(lmgpu_isam2_get_marginals_stats(h_, &st));
+    return st;
+  }
 
   /// ISAM2Result::errorBefore / errorAfter of the last update (with ISAM2Params::evaluateNonlinearError)
   std::pair<double, double> errors() const {
@@ -951,6 +999,11 @@ class GpuISAM2 {
     if (rc == LMGPU_OK) return;
     if (rc == LMGPU_INDETERMINATE) throw IndeterminantLinearSystemException(lmgpu_isam2_last_failed_key(h_));
     throw std::runtime_error(lmgpu_isam2_last_error(h_));
+  }
+  /// scalars of a variable this object was given (the library refuses one that has left the tree since)
+  size_t dimOf(Key key) const {
+    if (!all_.exists(key)) throw std::out_of_range("GpuISAM2: unknown key");
+    return all_.at(key).dim();
   }
   static void packOne(const Values& v, Key k, int32_t t, double* o) {
     switch (t) {
