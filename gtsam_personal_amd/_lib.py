@@ -228,6 +228,8 @@ SYMBOLS = {
     "lmgpu_selftest_chain_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
     "lmgpu_selftest_dense_schedule": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_uint, ct.c_int, _I]),
     "lmgpu_selftest_dogleg_step": (ct.c_int, [ct.c_int, _D, _D]),
+    "lmgpu_selftest_factor_type": (ct.c_int, [ct.c_int32, _I]),
+    "lmgpu_selftest_var_type": (ct.c_int, [ct.c_int32, _I]),
     "lmgpu_bt_products": (ct.c_int, [_H, _D, ct.c_double, _D, _D]),
     "lmgpu_triangulate_batch": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _I, _I, _D, ct.POINTER(lmgpu_triangulation_params),
                                            _D, _I]),

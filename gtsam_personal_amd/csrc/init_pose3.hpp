@@ -133,7 +133,7 @@ int lmgpu_init_pose3_add_factors(lmgpu_init_pose3* ip, int32_t factor_type, int3
     return LMGPU_INVALID;
   }
   const bool prior = factor_type == LMGPU_F_PRIOR_POSE3;
-  const int nl = noise_kind == LMGPU_N_DIAG ? 6 : (noise_kind == LMGPU_N_GAUSS ? 36 : 0);
+  const int nl = factor_noise_doubles(factor_type, noise_kind);
   for (int i = 0; i < n; i++) {
     lmgpu_init_pose3::Fac f{};
     f.graph_index = graph_index[i];
@@ -243,7 +243,7 @@ int lmgpu_init_pose3_finalize(lmgpu_init_pose3* ip, int32_t n_order, const uint6
     std::vector<int32_t> types(ns, LMGPU_POSE3);
     if ((rc = ip_inner(ip, ip->hP, lmgpu_set_variables(ip->hP, ns, slot_keys.data(), types.data())))) return fail(rc);
     for (int kind : {LMGPU_N_UNIT, LMGPU_N_DIAG, LMGPU_N_GAUSS}) {
-      const int nl = kind == LMGPU_N_DIAG ? 6 : (kind == LMGPU_N_GAUSS ? 36 : 0);
+      const int nl = factor_noise_doubles(LMGPU_F_BETWEEN_POSE3, kind);
       std::vector<int32_t> gi, slots;
       std::vector<double> meas, noise;
       for (int i = 0; i < m; i++) {

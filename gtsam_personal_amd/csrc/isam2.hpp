@@ -460,7 +460,7 @@ void is_pool_free(lmgpu_isam2* S, int64_t off, size_t n) {
 // the variables of the factor in slot i (a typed factor's first `arity` variables; a marginal factor's own list)
 std::vector<int32_t> is_fac_vids(const lmgpu_isam2* S, const lmgpu_isam2::Fac& f) {
   if (f.marg >= 0) return S->margs[f.marg].vids;
-  return std::vector<int32_t>(f.v, f.v + kFactorArity[f.type]);
+  return std::vector<int32_t>(f.v, f.v + factor_arity(f.type));
 }
 void is_free_marg(lmgpu_isam2* S, int32_t mi) {
   lmgpu_isam2::Marg& m = S->margs[mi];
@@ -567,31 +567,25 @@ BucketDev is_bucket_dev(const lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, int n, 
   d.sel = sel;
   return d;
 }
-// launch the factor kernels of bucket b on the index list sel (device), count entries: Jacobians into the linearization cache
-void is_linearize_sel(lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, const int32_t* d_sel, int count) {
-  if (count <= 0) return;
-  const BucketDev d = is_bucket_dev(S, b, count, d_sel, false);
+// the linearization point as the kernels take it
+ValuesDev is_theta_dev(const lmgpu_isam2* S) {
   ValuesDev vals;
   for (int t = 0; t < kNumVarTypes; t++) vals.v[t] = S->theta[t];
-  const int g256 = (count + 255) / 256, g128 = (count + 127) / 128;
-  hipStream_t s = S->stream;
-  double* nob = nullptr;
-  switch (b.type) {
-    case LMGPU_F_SFM: hipLaunchKernelGGL(sfm_linearize_sel_kernel, dim3(g256), dim3(256), 0, s, d, vals); break;
-    case LMGPU_F_BETWEEN_POSE2: hipLaunchKernelGGL((generic_factor_kernel<1, 3, 3, 3, 3, 0, 3, 0, 3, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_BETWEEN_POSE3: hipLaunchKernelGGL((generic_factor_kernel<2, 6, 6, 6, 12, 1, 12, 1, 12, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_POSE2: hipLaunchKernelGGL((generic_factor_kernel<3, 3, 3, 0, 3, 0, 3, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_POSE3: hipLaunchKernelGGL((generic_factor_kernel<4, 6, 6, 0, 12, 1, 12, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_POINT3: hipLaunchKernelGGL((generic_factor_kernel<5, 3, 3, 0, 3, 2, 3, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_CAM: hipLaunchKernelGGL((generic_factor_kernel<6, 9, 9, 0, 15, 3, 15, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PROJECTION: hipLaunchKernelGGL((generic_factor_kernel<7, 2, 6, 3, 7, 1, 12, 2, 3, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PROJECTION_BPS: hipLaunchKernelGGL((generic_factor_kernel<8, 2, 6, 3, 19, 1, 12, 2, 3, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_BEARING_RANGE_2D: hipLaunchKernelGGL((generic_factor_kernel<9, 2, 3, 2, 2, 0, 3, 4, 2, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_SFM2: hipLaunchKernelGGL(sfm2_factor_kernel<true>, dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_CAL3_S2: hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_CHORDAL_BETWEEN: hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-    case LMGPU_F_PRIOR_VEC9: hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, true>), dim3(g128), dim3(128), 0, s, d, vals, nob); break;
-  }
+  return vals;
+}
+int is_no_kernel(lmgpu_isam2* S, int type) {
+  S->err = "ISAM2: no factor kernel for factor type " + std::to_string(type);
+  return LMGPU_INVALID;
+}
+// The two factor types whose linearization has a launch of its own shape (is_linearize_jobs): bucket b on the index list sel (device),
+// count > 0 entries, Jacobians into the linearization cache
+int is_linearize_sel(lmgpu_isam2* S, const lmgpu_isam2::Bkt& b, const int32_t* d_sel, int count) {
+  const BucketDev d = is_bucket_dev(S, b, count, d_sel, false);
+  if (b.type == LMGPU_F_SFM)
+    hipLaunchKernelGGL(sfm_linearize_sel_kernel, dim3((count + 255) / 256), dim3(256), 0, S->stream, d, is_theta_dev(S));
+  else if (!launch_generic_bucket<true>(d, is_theta_dev(S), nullptr, S->stream))  // LMGPU_F_SFM2
+    return is_no_kernel(S, b.type);
+  return LMGPU_OK;
 }
 
 // several (bucket, index list) linearizations behind ONE flush and -- for the factor types of the generic kernel -- in ONE launch
@@ -602,8 +596,7 @@ int is_linearize_jobs(lmgpu_isam2* S, const std::vector<std::pair<int, std::vect
   for (size_t q = 0; q < jobs.size(); q++)
     if (!jobs[q].second.empty() && (rc = is_stage(S, jobs[q].second, &d[q]))) return rc;
   if ((rc = is_flush(S))) return rc;
-  ValuesDev vals;
-  for (int t = 0; t < kNumVarTypes; t++) vals.v[t] = S->theta[t];
+  const ValuesDev vals = is_theta_dev(S);
   MultiLin ml{};
   int blocks = 0;
   auto launch = [&]() {
@@ -618,9 +611,10 @@ int is_linearize_jobs(lmgpu_isam2* S, const std::vector<std::pair<int, std::vect
     const int count = (int)jobs[q].second.size();
     if (count == 0) continue;
     if (b.type == LMGPU_F_SFM || b.type == LMGPU_F_SFM2) {  // kernels of their own shape
-      is_linearize_sel(S, b, d[q], count);
+      if ((rc = is_linearize_sel(S, b, d[q], count))) return rc;
       continue;
     }
+    if (!for_generic_type(b.type, [](auto) {})) return is_no_kernel(S, b.type);  // linearize_multi_kernel would leave its Jacobians stale
     ml.b[ml.nb] = is_bucket_dev(S, b, count, d[q], false);
     ml.first[ml.nb] = blocks;
     blocks += (count + 127) / 128;
@@ -1697,9 +1691,8 @@ int is_graph_error(lmgpu_isam2* S, bool at_estimate, double* out) {
   hipStream_t s = S->stream;
   if ((rc = is_flush(S))) return rc;
   ISCHECK(hipMemsetAsync(S->d_ebuf, 0, (nfac + 1) * sizeof(double), s));
-  ValuesDev vals;
+  ValuesDev vals = is_theta_dev(S);
   for (int t = 0; t < kNumVarTypes; t++) {
-    vals.v[t] = S->theta[t];
     if (at_estimate && S->type_count[t] > 0) {
       hipLaunchKernelGGL(retract_kernel, dim3((S->type_count[t] + 255) / 256), dim3(256), 0, s, t, S->type_count[t], (const double*)S->theta[t], S->est[t],
                          (const int32_t*)S->d_type_xoff[t], (const double*)S->delta, (const int32_t*)nullptr);
@@ -1709,24 +1702,10 @@ int is_graph_error(lmgpu_isam2* S, bool at_estimate, double* out) {
   for (const lmgpu_isam2::Bkt& b : S->bkts) {
     if (b.n == 0) continue;
     const BucketDev d = is_bucket_dev(S, b, b.n, nullptr, true);
-    const int g256 = (b.n + 255) / 256, g128 = (b.n + 127) / 128;
-    double* eb = S->d_ebuf;
-    switch (b.type) {
-      case LMGPU_F_SFM: hipLaunchKernelGGL(sfm_error_kernel, dim3(g256), dim3(256), 0, s, d, vals, eb); break;
-      case LMGPU_F_BETWEEN_POSE2: hipLaunchKernelGGL((generic_factor_kernel<1, 3, 3, 3, 3, 0, 3, 0, 3, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_BETWEEN_POSE3: hipLaunchKernelGGL((generic_factor_kernel<2, 6, 6, 6, 12, 1, 12, 1, 12, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_POSE2: hipLaunchKernelGGL((generic_factor_kernel<3, 3, 3, 0, 3, 0, 3, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_POSE3: hipLaunchKernelGGL((generic_factor_kernel<4, 6, 6, 0, 12, 1, 12, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_POINT3: hipLaunchKernelGGL((generic_factor_kernel<5, 3, 3, 0, 3, 2, 3, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_CAM: hipLaunchKernelGGL((generic_factor_kernel<6, 9, 9, 0, 15, 3, 15, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PROJECTION: hipLaunchKernelGGL((generic_factor_kernel<7, 2, 6, 3, 7, 1, 12, 2, 3, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PROJECTION_BPS: hipLaunchKernelGGL((generic_factor_kernel<8, 2, 6, 3, 19, 1, 12, 2, 3, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_BEARING_RANGE_2D: hipLaunchKernelGGL((generic_factor_kernel<9, 2, 3, 2, 2, 0, 3, 4, 2, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_SFM2: hipLaunchKernelGGL(sfm2_factor_kernel<false>, dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_CAL3_S2: hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_CHORDAL_BETWEEN: hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-      case LMGPU_F_PRIOR_VEC9: hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, false>), dim3(g128), dim3(128), 0, s, d, vals, eb); break;
-    }
+    if (b.type == LMGPU_F_SFM)
+      hipLaunchKernelGGL(sfm_error_kernel, dim3((b.n + 255) / 256), dim3(256), 0, s, d, vals, S->d_ebuf);
+    else if (!launch_generic_bucket<false>(d, vals, S->d_ebuf, s))
+      return is_no_kernel(S, b.type);
   }
   const int g = std::min(256, std::max(1, ((int)nfac + 255) / 256));
   hipLaunchKernelGGL(reduce_stage1, dim3(g), dim3(256), 0, s, (const double*)(S->d_ebuf + 1), (int)nfac, S->d_epart);
@@ -2012,7 +1991,7 @@ int is_check_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up) {
     }
   }
   for (const lmgpu_isam2::NewFac& nf : S->new_facs)
-    for (int k = 0; k < kFactorArity[nf.type]; k++) {
+    for (int k = 0; k < factor_arity(nf.type); k++) {
       int32_t t = -1;
       auto it = S->vid_of.find(nf.k[k]);
       if (it != S->vid_of.end()) {
@@ -2022,7 +2001,7 @@ int is_check_update(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up) {
         if (pt == pending_type.end()) return refuse("ISAM2: a new factor references a variable that has no value");
         t = pt->second;
       }
-      if (t != factor_var_type(nf.type, k)) return refuse("factor/variable type mismatch");
+      if (t != var_type(nf.type, k)) return refuse("factor/variable type mismatch");
     }
   if (up.has_constrained)
     for (auto& kg : up.constrained)
@@ -2122,12 +2101,12 @@ int is_bucket_of(lmgpu_isam2* S, const lmgpu_isam2::NewFac& nf) {
   b.noise_kind = nf.noise_kind;
   b.robust = nf.robust;
   b.rk = nf.rk;
-  b.rows = kFactorRows[nf.type];
-  b.ar = kFactorArity[nf.type];
-  b.ml = kFactorMeas[nf.type];
-  b.nl = nf.noise_kind == LMGPU_N_DIAG ? b.rows : (nf.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
-  b.cols = 1;
-  for (int k = 0; k < b.ar; k++) b.cols += kVarDim[factor_var_type(nf.type, k)];
+  const BucketShape sh = bucket_shape(nf.type, nf.noise_kind);
+  b.rows = sh.rows;
+  b.cols = sh.cols;
+  b.ar = sh.ar;
+  b.ml = sh.ml;
+  b.nl = sh.nl;
   S->bkts.push_back(b);
   return (int)S->bkts.size() - 1;
 }
@@ -2163,7 +2142,7 @@ int is_push_back_factors(lmgpu_isam2* S, const lmgpu_isam2::UpParams& up, Update
   std::map<int, NewRows> new_rows;
   int rc;
   for (const lmgpu_isam2::NewFac& nf : W.new_facs) {
-    const int ar = kFactorArity[nf.type];
+    const int ar = factor_arity(nf.type);
     lmgpu_isam2::Fac f{nf.type, -1, -1, {-1, -1, -1}, false, -1};
     const size_t slot = is_take_slot(S, &slot_scan);
     for (int k = 0; k < ar; k++) {
@@ -2311,7 +2290,7 @@ int is_linearize_new_factors(lmgpu_isam2* S, const UpdateWork& W) {
   const int rc = is_linearize_jobs(S, jobs);
   if (rc) return rc;
   for (int32_t i : W.new_idx)
-    for (int k = 0; k < kFactorArity[S->facs[i].type]; k++) S->vindex[S->facs[i].v[k]].push_back(i);
+    for (int k = 0; k < factor_arity(S->facs[i].type); k++) S->vindex[S->facs[i].v[k]].push_back(i);
   return LMGPU_OK;
 }
 
@@ -2914,8 +2893,8 @@ int lmgpu_isam2_add_factors(lmgpu_isam2* S, int32_t factor_type, int32_t n, cons
   if (noise_kind != LMGPU_N_UNIT && noise_kind != LMGPU_N_DIAG && noise_kind != LMGPU_N_GAUSS) return LMGPU_INVALID;
   if (n == 0) return LMGPU_OK;
   if (!keys || !meas || (noise_kind != LMGPU_N_UNIT && !noise)) return LMGPU_INVALID;
-  const int ar = kFactorArity[factor_type], rows = kFactorRows[factor_type], ml = kFactorMeas[factor_type];
-  const int nl = noise_kind == LMGPU_N_DIAG ? rows : (noise_kind == LMGPU_N_GAUSS ? rows * rows : 0);
+  const BucketShape sh = bucket_shape(factor_type, noise_kind);
+  const int ar = sh.ar, ml = sh.ml, nl = sh.nl;
   for (int i = 0; i < n; i++) {
     lmgpu_isam2::NewFac f;
     f.type = factor_type;

@@ -13,6 +13,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "factor_types.hpp"
 #include "geometry_dev.hpp"
 
 namespace lmgpu {
@@ -583,9 +586,42 @@ __global__ __launch_bounds__(128) void sfm2_factor_kernel(BucketDev b, ValuesDev
   }
 }
 
-// Generic bucket kernel.  TYPE selects the evaluator; M rows, D0/D1 tangent dims, S0/S1 stored doubles, T0/T1 value types.
-template <int TYPE, int M, int D0, int D1, int ML, int T0, int S0, int T1, int S1, bool JAC>
+// The generic kernel's constants for a factor type of one or two variables, from its row of the table (factor_types.hpp):
+// M rows, ML measurement doubles, T0/T1 value types, D0/D1 tangent dims, S0/S1 stored doubles (T1 = -1, D1 = S1 = 0: unary).
+constexpr int var_dim_or_0(int t) { return t >= 0 ? kVarDim[t] : 0; }
+constexpr int var_store_or_0(int t) { return t >= 0 ? kVarStore[t] : 0; }
+template <int TYPE>
+struct FactorDims {
+  static_assert(factor_arity(TYPE) == 1 || factor_arity(TYPE) == 2, "generic_factor_kernel serves unary and binary factor types");
+  static constexpr int M = kFactorTypes[TYPE].rows, ML = kFactorTypes[TYPE].meas;
+  static constexpr int T0 = var_type(TYPE, 0), D0 = var_dim_or_0(T0), S0 = var_store_or_0(T0);
+  static constexpr int T1 = var_type(TYPE, 1), D1 = var_dim_or_0(T1), S1 = var_store_or_0(T1);
+};
+// Every derived tuple against its literal <TYPE, M, D0, D1, ML, T0, S0, T1, S1>: an edit of the table that moves a constant of an
+// existing kernel (a stride, a value type) stops the build here instead of changing one kernel on one path.
+template <int TYPE, int M, int D0, int D1, int ML, int T0, int S0, int T1, int S1>
+constexpr bool factor_dims_are() {
+  using F = FactorDims<TYPE>;
+  return F::M == M && F::D0 == D0 && F::D1 == D1 && F::ML == ML && F::T0 == T0 && F::S0 == S0 && F::T1 == T1 && F::S1 == S1;
+}
+static_assert(factor_dims_are<LMGPU_F_BETWEEN_POSE2, 3, 3, 3, 3, 0, 3, 0, 3>(), "BETWEEN_POSE2");
+static_assert(factor_dims_are<LMGPU_F_BETWEEN_POSE3, 6, 6, 6, 12, 1, 12, 1, 12>(), "BETWEEN_POSE3");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_POSE2, 3, 3, 0, 3, 0, 3, -1, 0>(), "PRIOR_POSE2");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_POSE3, 6, 6, 0, 12, 1, 12, -1, 0>(), "PRIOR_POSE3");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_POINT3, 3, 3, 0, 3, 2, 3, -1, 0>(), "PRIOR_POINT3");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_CAM, 9, 9, 0, 15, 3, 15, -1, 0>(), "PRIOR_CAM");
+static_assert(factor_dims_are<LMGPU_F_PROJECTION, 2, 6, 3, 7, 1, 12, 2, 3>(), "PROJECTION");
+static_assert(factor_dims_are<LMGPU_F_PROJECTION_BPS, 2, 6, 3, 19, 1, 12, 2, 3>(), "PROJECTION_BPS");
+static_assert(factor_dims_are<LMGPU_F_BEARING_RANGE_2D, 2, 3, 2, 2, 0, 3, 4, 2>(), "BEARING_RANGE_2D");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_CAL3_S2, 5, 5, 0, 5, 5, 5, -1, 0>(), "PRIOR_CAL3_S2");
+static_assert(factor_dims_are<LMGPU_F_CHORDAL_BETWEEN, 9, 9, 9, 9, 6, 9, 6, 9>(), "CHORDAL_BETWEEN");
+static_assert(factor_dims_are<LMGPU_F_PRIOR_VEC9, 9, 9, 0, 9, 6, 9, -1, 0>(), "PRIOR_VEC9");
+
+// Generic bucket kernel.  TYPE selects the evaluator and, through FactorDims, every size.
+template <int TYPE, bool JAC>
 __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const ValuesDev& vals, double* __restrict__ ebuf, const int fi) {
+  using F = FactorDims<TYPE>;
+  constexpr int M = F::M, D0 = F::D0, D1 = F::D1, ML = F::ML, T0 = F::T0, S0 = F::S0, T1 = F::T1, S1 = F::S1;
   if (fi >= b.n) return;
   if (!JAC && b.skip && *b.skip) return;
   const int f = b.sel ? b.sel[fi] : fi;
@@ -673,9 +709,47 @@ __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const Va
   }
 }
 
-template <int TYPE, int M, int D0, int D1, int ML, int T0, int S0, int T1, int S1, bool JAC>
+template <int TYPE, bool JAC>
 __global__ __launch_bounds__(128) void generic_factor_kernel(BucketDev b, ValuesDev vals, double* __restrict__ ebuf) {
-  generic_factor_body<TYPE, M, D0, D1, ML, T0, S0, T1, S1, JAC>(b, vals, ebuf, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+  generic_factor_body<TYPE, JAC>(b, vals, ebuf, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+
+// THE list of the generic types (those generic_factor_kernel serves): f(std::integral_constant<int, TYPE>) for a run-time type of the
+// list; false, and f not called, for any other.
+#define LMGPU_GENERIC_TYPE(T) \
+  case T: f(std::integral_constant<int, T>{}); return true
+template <class Fn>
+__host__ __device__ __forceinline__ bool for_generic_type(int type, Fn&& f) {
+  switch (type) {
+    LMGPU_GENERIC_TYPE(LMGPU_F_BETWEEN_POSE2);
+    LMGPU_GENERIC_TYPE(LMGPU_F_BETWEEN_POSE3);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_POSE2);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_POSE3);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_POINT3);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_CAM);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PROJECTION);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PROJECTION_BPS);
+    LMGPU_GENERIC_TYPE(LMGPU_F_BEARING_RANGE_2D);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_CAL3_S2);
+    LMGPU_GENERIC_TYPE(LMGPU_F_CHORDAL_BETWEEN);
+    LMGPU_GENERIC_TYPE(LMGPU_F_PRIOR_VEC9);
+  }
+  return false;
+}
+#undef LMGPU_GENERIC_TYPE
+
+// One bucket through the kernel of its type: a generic type or LMGPU_F_SFM2, one lane per factor in blocks of 128.  false: the type has
+// neither (LMGPU_F_SFM and the smart observations have launches of their own shape at their callers), nothing was launched.
+template <bool JAC>
+bool launch_generic_bucket(const BucketDev& d, const ValuesDev& vals, double* ebuf, hipStream_t s) {
+  const dim3 grid((d.n + 127) / 128), block(128);
+  if (d.type == LMGPU_F_SFM2) {
+    hipLaunchKernelGGL(sfm2_factor_kernel<JAC>, grid, block, 0, s, d, vals, ebuf);
+    return true;
+  }
+  return for_generic_type(d.type, [&](auto t) {
+    hipLaunchKernelGGL((generic_factor_kernel<decltype(t)::value, JAC>), grid, block, 0, s, d, vals, ebuf);
+  });
 }
 
 // Linearization of SEVERAL buckets in one launch (ISAM2: an update relinearizes two or three factor types, each a launch of a few
@@ -693,21 +767,8 @@ __global__ __launch_bounds__(128) void linearize_multi_kernel(MultiLin ml, Value
   const BucketDev& b = ml.b[k];
   const int fi = ((int)blockIdx.x - ml.first[k]) * 128 + (int)threadIdx.x;
   double* nob = nullptr;
-  switch (b.type) {
-    case 1: generic_factor_body<1, 3, 3, 3, 3, 0, 3, 0, 3, true>(b, vals, nob, fi); break;
-    case 2: generic_factor_body<2, 6, 6, 6, 12, 1, 12, 1, 12, true>(b, vals, nob, fi); break;
-    case 3: generic_factor_body<3, 3, 3, 0, 3, 0, 3, -1, 0, true>(b, vals, nob, fi); break;
-    case 4: generic_factor_body<4, 6, 6, 0, 12, 1, 12, -1, 0, true>(b, vals, nob, fi); break;
-    case 5: generic_factor_body<5, 3, 3, 0, 3, 2, 3, -1, 0, true>(b, vals, nob, fi); break;
-    case 6: generic_factor_body<6, 9, 9, 0, 15, 3, 15, -1, 0, true>(b, vals, nob, fi); break;
-    case 7: generic_factor_body<7, 2, 6, 3, 7, 1, 12, 2, 3, true>(b, vals, nob, fi); break;
-    case 8: generic_factor_body<8, 2, 6, 3, 19, 1, 12, 2, 3, true>(b, vals, nob, fi); break;
-    case 9: generic_factor_body<9, 2, 3, 2, 2, 0, 3, 4, 2, true>(b, vals, nob, fi); break;
-    case 11: generic_factor_body<11, 5, 5, 0, 5, 5, 5, -1, 0, true>(b, vals, nob, fi); break;
-    case 12: generic_factor_body<12, 9, 9, 9, 9, 6, 9, 6, 9, true>(b, vals, nob, fi); break;
-    case 13: generic_factor_body<13, 9, 9, 0, 9, 6, 9, -1, 0, true>(b, vals, nob, fi); break;
-    default: break;
-  }
+  // (a type outside the list never gets here: is_linearize_jobs refuses it on the host)
+  for_generic_type(b.type, [&](auto t) { generic_factor_body<decltype(t)::value, true>(b, vals, nob, fi); });
 }
 
 
@@ -838,7 +899,7 @@ __global__ __launch_bounds__(256) void reduce_stage2(const double* __restrict__ 
 // Values::retract gtsam/nonlinear/Values.cpp:53-64; one thread per variable of a type.
 // sel (may be null): the n variables to retract as indices into the type array (ISAM2's retractMasked, gtsam/nonlinear/ISAM2.cpp:465);
 // cur == out is allowed (every lane reads its variable before it writes it).
-// tangent dimension of a variable type: the device's copy of kVarDim (plan.hpp); lmgpu.hip static_asserts that the two agree
+// tangent dimension of a variable type: the device's copy of kVarDim (factor_types.hpp); ncg.hpp static_asserts that the two agree
 __host__ __device__ constexpr int var_tangent_dim(int type) {
   return (type == 0 || type == 2) ? 3 : (type == 1 ? 6 : (type == 4 ? 2 : (type == 5 ? 5 : 9)));
 }

@@ -522,70 +522,32 @@ BucketDev bucket_dev(lmgpu_handle* h, const Bucket& b) {
 
 // launch the factor kernels of every bucket: JAC -> Jacobians, else per-factor errors into ebuf0
 template <bool JAC>
-void launch_factors(lmgpu_handle* h, int which) {
+int launch_factors(lmgpu_handle* h, int which) {
   const ValuesDev vals = values_dev(h, which);
   if (h->smart) smart_enqueue_triangulate(h, which);  // SmartProjectionFactor::triangulateSafe at the head of every linearize / error
   for (const Bucket& b : h->buckets) {
     if (b.n_loc == 0) continue;
     const BucketDev d = bucket_dev(h, b);
-    const int g256 = (b.n_loc + 255) / 256, g128 = (b.n_loc + 127) / 128;
     hipStream_t s = h->stream;
-    switch (b.type) {
-      case LMGPU_F_SFM:
-        if (JAC) {
-          // algorithmic bytes: 232 B per factor + each variable once (120 B camera, 24 B point)
-          const int kt = h->kt.begin(LMGPU_KT_LINEARIZE, s);
-          hipLaunchKernelGGL(sfm_linearize_kernel, dim3(g256), dim3(256), 0, s, d, vals);
-          h->kt.end(kt, s, 232.0 * b.n_loc + 120.0 * h->plan.type_count[3] + 24.0 * h->plan.type_count[2]);
-        } else {
-          hipLaunchKernelGGL(sfm_error_kernel, dim3(g256), dim3(256), 0, s, d, vals, h->ebuf0);
-        }
-        break;
-      case LMGPU_F_BETWEEN_POSE2:
-        hipLaunchKernelGGL((generic_factor_kernel<1, 3, 3, 3, 3, 0, 3, 0, 3, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_BETWEEN_POSE3:
-        hipLaunchKernelGGL((generic_factor_kernel<2, 6, 6, 6, 12, 1, 12, 1, 12, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_POSE2:
-        hipLaunchKernelGGL((generic_factor_kernel<3, 3, 3, 0, 3, 0, 3, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_POSE3:
-        hipLaunchKernelGGL((generic_factor_kernel<4, 6, 6, 0, 12, 1, 12, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_POINT3:
-        hipLaunchKernelGGL((generic_factor_kernel<5, 3, 3, 0, 3, 2, 3, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_CAM:
-        hipLaunchKernelGGL((generic_factor_kernel<6, 9, 9, 0, 15, 3, 15, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PROJECTION:
-        hipLaunchKernelGGL((generic_factor_kernel<7, 2, 6, 3, 7, 1, 12, 2, 3, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PROJECTION_BPS:
-        hipLaunchKernelGGL((generic_factor_kernel<8, 2, 6, 3, 19, 1, 12, 2, 3, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_BEARING_RANGE_2D:
-        hipLaunchKernelGGL((generic_factor_kernel<9, 2, 3, 2, 2, 0, 3, 4, 2, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_SFM2:
-        hipLaunchKernelGGL(sfm2_factor_kernel<JAC>, dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_CAL3_S2:
-        hipLaunchKernelGGL((generic_factor_kernel<11, 5, 5, 0, 5, 5, 5, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_CHORDAL_BETWEEN:
-        hipLaunchKernelGGL((generic_factor_kernel<12, 9, 9, 9, 9, 6, 9, 6, 9, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case LMGPU_F_PRIOR_VEC9:
-        hipLaunchKernelGGL((generic_factor_kernel<13, 9, 9, 0, 9, 6, 9, -1, 0, JAC>), dim3(g128), dim3(128), 0, s, d, vals, h->ebuf0);
-        break;
-      case kSmartObsType:
-        smart_launch_factors(h, d, vals, JAC);
-        break;
+    if (b.type == LMGPU_F_SFM) {
+      const int g256 = (b.n_loc + 255) / 256;
+      if (JAC) {
+        // algorithmic bytes: 232 B per factor + each variable once (120 B camera, 24 B point)
+        const int kt = h->kt.begin(LMGPU_KT_LINEARIZE, s);
+        hipLaunchKernelGGL(sfm_linearize_kernel, dim3(g256), dim3(256), 0, s, d, vals);
+        h->kt.end(kt, s, 232.0 * b.n_loc + 120.0 * h->plan.type_count[3] + 24.0 * h->plan.type_count[2]);
+      } else {
+        hipLaunchKernelGGL(sfm_error_kernel, dim3(g256), dim3(256), 0, s, d, vals, h->ebuf0);
+      }
+    } else if (b.type == kSmartObsType) {
+      smart_launch_factors(h, d, vals, JAC);
+    } else if (!launch_generic_bucket<JAC>(d, vals, h->ebuf0, s)) {
+      h->err = "no factor kernel for factor type " + std::to_string(b.type);
+      return LMGPU_INVALID;
     }
   }
   if (JAC && h->smart) smart_enqueue_const(h);
+  return LMGPU_OK;
 }
 
 void reduce_to(lmgpu_handle* h, const double* buf, int n, double* dst, hipStream_t st = nullptr, double* scratch = nullptr) {
@@ -639,10 +601,10 @@ int allreduce_scalars(lmgpu_handle* h, int first, int count) {
 }
 
 int compute_error(lmgpu_handle* h, int which, double* out) {
-  launch_factors<false>(h, which);
-  reduce_to(h, h->ebuf0, h->n_counted, h->dscal);
-  int rc = allreduce_scalars(h, 0, 1);
+  int rc = launch_factors<false>(h, which);
   if (rc) return rc;
+  reduce_to(h, h->ebuf0, h->n_counted, h->dscal);
+  if ((rc = allreduce_scalars(h, 0, 1))) return rc;
   HIPCHECK(hipMemcpyAsync(h->h_scal, h->dscal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   *out = h->h_scal[0];
@@ -651,7 +613,8 @@ int compute_error(lmgpu_handle* h, int which, double* out) {
 
 int do_linearize(lmgpu_handle* h) {
   h->marg_valid = false;
-  launch_factors<true>(h, h->cur);
+  const int rc = launch_factors<true>(h, h->cur);
+  if (rc) return rc;
   HIPCHECK(hipGetLastError());
   h->linearized = true;
   h->have_jacobians = true;
@@ -1705,7 +1668,7 @@ int enqueue_retract_and_error(lmgpu_handle* h) {
   const int kt = h->kt.begin(LMGPU_KT_RETRACT_ERROR, h->stream);
   int rc = do_retract(h, h->cur, h->cur ^ 1);
   if (rc) return rc;
-  launch_factors<false>(h, h->cur ^ 1);
+  if ((rc = launch_factors<false>(h, h->cur ^ 1))) return rc;
   reduce_to(h, h->ebuf0, h->n_counted, h->dscal);
   h->kt.end(kt, h->stream);
   rc = allreduce_scalars(h, 0, 1);
@@ -1816,7 +1779,7 @@ int gn_iterate(lmgpu_handle* h) {
   const int kt = h->kt.begin(LMGPU_KT_RETRACT_ERROR, h->stream);
   rc = do_retract(h, h->cur, h->cur ^ 1);
   if (rc) return rc;
-  launch_factors<false>(h, h->cur ^ 1);
+  if ((rc = launch_factors<false>(h, h->cur ^ 1))) return rc;
   reduce_to(h, h->ebuf0, h->n_counted, h->dscal);
   h->kt.end(kt, h->stream);
   rc = allreduce_scalars(h, 0, 1);
@@ -2279,7 +2242,8 @@ int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, con
   if (noise_kind != LMGPU_N_UNIT && noise_kind != LMGPU_N_DIAG && noise_kind != LMGPU_N_GAUSS) return LMGPU_INVALID;
   if (n == 0) return LMGPU_OK;
   if (!graph_index || !var_slots || !meas || (noise_kind != LMGPU_N_UNIT && !noise)) return LMGPU_INVALID;
-  const int ar = kFactorArity[type], rows = kFactorRows[type], ml = kFactorMeas[type];
+  const BucketShape sh = bucket_shape(type, noise_kind);
+  const int ar = sh.ar;
   for (int i = 0; i < n; i++)
     for (int k = 0; k < ar; k++) {
       const int s = var_slots[i * ar + k];
@@ -2287,8 +2251,7 @@ int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, con
         h->err = "factor references unknown slot";
         return LMGPU_INVALID;
       }
-      const int want = factor_var_type(type, k);
-      if (h->plan.types[s] != want) {
+      if (h->plan.types[s] != var_type(type, k)) {
         h->err = "factor/variable type mismatch";
         return LMGPU_INVALID;
       }
@@ -2301,13 +2264,10 @@ int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, con
   b.robust_k = robust_k;
   b.graph_index.assign(graph_index, graph_index + n);
   b.slots.assign(var_slots, var_slots + (size_t)n * ar);
-  b.meas.assign(meas, meas + (size_t)n * ml);
-  const int nl = noise_kind == LMGPU_N_DIAG ? rows : (noise_kind == LMGPU_N_GAUSS ? rows * rows : 0);
-  if (nl) b.noise.assign(noise, noise + (size_t)n * nl);
-  int cols = 1;
-  for (int k = 0; k < ar; k++) cols += kVarDim[factor_var_type(type, k)];
-  b.rows = rows;
-  b.cols = cols;
+  b.meas.assign(meas, meas + (size_t)n * sh.ml);
+  if (sh.nl) b.noise.assign(noise, noise + (size_t)n * sh.nl);
+  b.rows = sh.rows;
+  b.cols = sh.cols;
   const int bi = (int)h->buckets.size();
   for (int i = 0; i < n; i++) {
     FactorRef f;
@@ -2334,8 +2294,8 @@ static int finalize_vectors(lmgpu_handle* h) {
       if (h->fac_local[i] >= 0) epos[P.factors[i].bucket][h->buckets[P.factors[i].bucket].loc_of[P.factors[i].idx]] = h->fac_local[i];
     for (size_t bi = 0; bi < h->buckets.size(); bi++) {
       Bucket& b = h->buckets[bi];
-      const int ar = kFactorArity[b.type], ml = kFactorMeas[b.type];
-      const int nl = b.noise_kind == LMGPU_N_DIAG ? b.rows : (b.noise_kind == LMGPU_N_GAUSS ? b.rows * b.rows : 0);
+      const BucketShape sh = bucket_shape(b.type, b.noise_kind);
+      const int ar = sh.ar, ml = sh.ml, nl = sh.nl;
       std::vector<int32_t> vidx((size_t)b.n_loc * ar);
       std::vector<double> meas((size_t)b.n_loc * ml), noise((size_t)b.n_loc * nl);
       for (int i = 0; i < b.n; i++) {
@@ -3059,15 +3019,17 @@ int gnc_default_thresholds(lmgpu_handle* h, double alpha) {
 }
 
 // r_k of every factor at values[which] into ebuf0: the error kernels on the unweighted graph (gw = nullptr, robust ignored)
-void gnc_raw_errors(lmgpu_handle* h, int which) {
+int gnc_raw_errors(lmgpu_handle* h, int which) {
   h->gnc_raw = true;
-  launch_factors<false>(h, which);
+  const int rc = launch_factors<false>(h, which);
   h->gnc_raw = false;
+  return rc;
 }
 
 // calculateWeights at values[cur] (queued): weights into gnc_w, max |w - round(w)| into h_gnc_scal[0]
 int gnc_enqueue_weights(lmgpu_handle* h, int loss, double mu) {
-  gnc_raw_errors(h, h->cur);
+  const int rc = gnc_raw_errors(h, h->cur);
+  if (rc) return rc;
   const int g = std::min(GNC_MAX_BLOCKS, std::max(1, (h->nfac + 255) / 256));
   hipLaunchKernelGGL(gnc_weights_kernel, dim3(g), dim3(256), 0, h->stream, h->nfac, (const double*)h->ebuf0, (const double*)h->gnc_b,
                      (const unsigned char*)h->gnc_fixed, mu, loss, h->gnc_w, h->gnc_part);
@@ -3080,7 +3042,8 @@ int gnc_enqueue_weights(lmgpu_handle* h, int loss, double mu) {
 
 // initializeMu at values[cur] (waits for the scalar)
 int gnc_init_mu(lmgpu_handle* h, int loss, double* mu) {
-  gnc_raw_errors(h, h->cur);
+  const int rc = gnc_raw_errors(h, h->cur);
+  if (rc) return rc;
   const int g = std::min(GNC_MAX_BLOCKS, std::max(1, (h->nfac + 255) / 256));
   hipLaunchKernelGGL(gnc_mu_init_kernel, dim3(g), dim3(256), 0, h->stream, h->nfac, (const double*)h->ebuf0, (const double*)h->gnc_b, loss,
                      h->gnc_part);
@@ -3621,6 +3584,20 @@ int lmgpu_selftest_dogleg_step(int which, const double* in, double* out) {
     return 0;
   }
   return -1;
+}
+// Host-only view of the factor-type table (factor_types.hpp): (arity, rows, meas, var0, var1, var2) of a public factor type ...
+int lmgpu_selftest_factor_type(int32_t type, int32_t out[6]) {
+  if (type < 0 || type >= LMGPU_NUM_FACTOR_TYPES || !out) return LMGPU_INVALID;
+  const int32_t rec[6] = {factor_arity(type), kFactorTypes[type].rows, kFactorTypes[type].meas, var_type(type, 0), var_type(type, 1), var_type(type, 2)};
+  std::copy(rec, rec + 6, out);
+  return LMGPU_OK;
+}
+// ... and (tangent dimension, stored doubles) of a variable type
+int lmgpu_selftest_var_type(int32_t type, int32_t out[2]) {
+  if (type < 0 || type >= LMGPU_NUM_VAR_TYPES || !out) return LMGPU_INVALID;
+  out[0] = kVarDim[type];
+  out[1] = kVarStore[type];
+  return LMGPU_OK;
 }
 // Host-only check of the ticket order of a chained launch (kernels_step.hpp: chain_schedule): every logical workgroup of every
 // step exactly once, and every dependency step_body waits for at an earlier ticket.  0 = valid, else the 1-based ticket at fault.

@@ -68,7 +68,7 @@ static_assert(kNumVarTypes == 7 && sizeof(kVarDim) / sizeof(kVarDim[0]) == 7, "v
 static_assert(var_tangent_dim(0) == kVarDim[0] && var_tangent_dim(1) == kVarDim[1] && var_tangent_dim(2) == kVarDim[2] &&
                   var_tangent_dim(3) == kVarDim[3] && var_tangent_dim(4) == kVarDim[4] && var_tangent_dim(5) == kVarDim[5] &&
                   var_tangent_dim(6) == kVarDim[6],
-              "var_tangent_dim (kernels_factors.hpp) and kVarDim (plan.hpp) disagree");
+              "var_tangent_dim (kernels_factors.hpp) and kVarDim (factor_types.hpp) disagree");
 
 // the three states the group refuses
 int ncg_check(lmgpu_handle* h, const char* who) {
@@ -148,8 +148,9 @@ int ncg_line_search(lmgpu_handle* h, int advance) {
     for (int k = 0; k < more; k++) {
       ncg_launch_retract(h, 0);
       h->err_skip = done;  // the error launches of a trial behind the exit test return at once too
-      launch_factors<false>(h, h->cur ^ 1);
+      const int rc = launch_factors<false>(h, h->cur ^ 1);
       h->err_skip = nullptr;
+      if (rc) return rc;
       hipLaunchKernelGGL(ncg_reduce_stage1, dim3(rg), dim3(256), 0, h->stream, (const double*)h->ebuf0, h->n_counted, h->partial, done);
       hipLaunchKernelGGL(ncg_reduce_stage2, dim3(1), dim3(256), 0, h->stream, (const double*)h->partial, rg, h->dscal, done);
       hipLaunchKernelGGL(ncg_ls_control_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->dscal, s->ctl);
@@ -157,7 +158,8 @@ int ncg_line_search(lmgpu_handle* h, int advance) {
     queued += more;
     if (advance) {
       ncg_launch_retract(h, 1);
-      launch_factors<false>(h, h->cur ^ 1);
+      const int rc = launch_factors<false>(h, h->cur ^ 1);
+      if (rc) return rc;
       reduce_to(h, h->ebuf0, h->n_counted, h->dscal);
       hipLaunchKernelGGL(ncg_final_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->dscal, s->ctl);
     }

@@ -7,23 +7,9 @@
 #include <string>
 #include <vector>
 
-namespace lmgpu {
+#include "factor_types.hpp"
 
-static const int kNumVarTypes = 7;
-static constexpr int kVarDim[7] = {3, 6, 3, 9, 2, 5, 9};
-static const int kVarStore[7] = {3, 12, 3, 15, 2, 5, 9};
-static const int kMaxArity = 3;
-// entries 0 .. 13: the public lmgpu_factor_type; entry 14 (kSmartObsType): one observation of a smart projection factor, (POSE3, hidden
-// POINT3) in the shape of LMGPU_F_PROJECTION -- internal to the batch handle (smart.hpp), never accepted at the boundary
-static const int kSmartObsType = 14;
-static const int kFactorArity[15] = {2, 2, 2, 1, 1, 1, 1, 2, 2, 2, 3, 1, 2, 1, 2};
-static const int kFactorRows[15] = {2, 3, 6, 3, 6, 3, 9, 2, 2, 2, 2, 5, 9, 9, 2};
-static const int kFactorMeas[15] = {2, 3, 12, 3, 12, 3, 15, 7, 19, 2, 2, 5, 9, 9, 7};
-// variable types each factor type expects (for validation)
-static const int kFactorVar0[15] = {3, 0, 1, 0, 1, 2, 3, 1, 1, 0, 1, 5, 6, 6, 1};
-static const int kFactorVar1[15] = {2, 0, 1, -1, -1, -1, -1, 2, 2, 4, 2, -1, 6, -1, 2};
-static const int kFactorVar2[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 5, -1, -1, -1, -1};
-inline int factor_var_type(int ftype, int k) { return k == 0 ? kFactorVar0[ftype] : (k == 1 ? kFactorVar1[ftype] : kFactorVar2[ftype]); }
+namespace lmgpu {
 
 struct FactorRef {
   int32_t bucket;   // bucket index

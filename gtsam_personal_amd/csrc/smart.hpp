@@ -3,7 +3,7 @@
 //
 // Integration: lmgpu_finalize_structure turns every smart factor with m >= 2 observations into a hidden POINT3 variable
 // in front of the caller's slots (so the caller's packed vectors are a contiguous suffix of the internal ones) and its observations into
-// factors of one internal bucket of type kSmartObsType (plan.hpp).  Leaf elimination, Schur gather and back-substitution then run unchanged;
+// factors of one internal bucket of type kSmartObsType (factor_types.hpp).  Leaf elimination, Schur gather and back-substitution then run unchanged;
 // the damping weight of the hidden scalars is 0 (fill_dampw), the retract skips them (do_retract), and their value is never read: the
 // point lives in the cache below.  The caller's graph indices are renumbered densely over (graph index, observation) so that every internal
 // factor has an index of its own and the error sum keeps the caller's order.
@@ -130,12 +130,13 @@ static int smart_prepare(lmgpu_handle* h) {
   ib.type = kSmartObsType;
   ib.n = n_int;
   ib.noise_kind = LMGPU_N_DIAG;
-  ib.rows = 2;
-  ib.cols = 10;
+  const BucketShape sh = bucket_shape(kSmartObsType, LMGPU_N_DIAG);  // (pose, point), (z, K), (1 / sigma, 1 / sigma)
+  ib.rows = sh.rows;
+  ib.cols = sh.cols;
   ib.graph_index.resize(n_int);
-  ib.slots.resize((size_t)n_int * 2);
-  ib.meas.resize((size_t)n_int * 7);
-  ib.noise.resize((size_t)n_int * 2);
+  ib.slots.resize((size_t)n_int * sh.ar);
+  ib.meas.resize((size_t)n_int * sh.ml);
+  ib.noise.resize((size_t)n_int * sh.nl);
   s->hp_fptr.assign(nh + 1, 0);
   std::vector<int32_t> first_of(n, -1);
   {

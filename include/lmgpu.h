@@ -586,6 +586,13 @@ int lmgpu_selftest_dense_schedule(int n, int nf, int mode, unsigned forms, int m
  * repeated with it, 0 if the step is dropped at the radius floor else 1).  Returns 0; -1 for a NULL argument or an unknown `which`. */
 int lmgpu_selftest_dogleg_step(int which, const double* in, double* out);
 
+/* Host-only self-test (no GPU work, no handle): the library's one table of factor types, so that the CPU test-suite can hold every
+ * copy of it outside the library against it.  out = (arity, rows of the error, measurement doubles, lmgpu_var_type of variable 0, 1, 2;
+ * -1 beyond the arity) of a public lmgpu_factor_type.  LMGPU_OK; LMGPU_INVALID outside 0 .. LMGPU_NUM_FACTOR_TYPES - 1 or for NULL. */
+int lmgpu_selftest_factor_type(int32_t type, int32_t out[6]);
+/* Its sibling for a lmgpu_var_type: out = (tangent dimension, doubles of a packed value).  LMGPU_INVALID for an unknown type or NULL. */
+int lmgpu_selftest_var_type(int32_t type, int32_t out[2]);
+
 /* ---- triangulation (gtsam/geometry/triangulation.h, triangulation.cpp): triangulatePoint3 / triangulateSafe for PinholeCamera<Cal3Bundler>
  *      and PinholeCamera<Cal3_S2>, batched over landmarks on the device -- one lane per landmark, one launch per degree bin over the
  *      landmarks sorted by their number of observations, results stored at the landmark's own index.  Each camera carries its own

@@ -36,6 +36,37 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(_lib.load(test_hooks=True), name), name
 
 
+def test_python_factor_tables_match_the_library():
+    """graph.py keeps a copy of the library's factor-type table (csrc/factor_types.hpp) for its host-side bookkeeping; a row that
+    drifts would pack a bucket's arrays with the wrong stride.  Every row of the copy against the library's own, through
+    lmgpu_selftest_factor_type / lmgpu_selftest_var_type.  The one intended difference: a PriorFactor<camera> measurement carries u0, v0
+    on the host (17 doubles, like VAR_STORE) and not across the C ABI (15, like VAR_STORE_DEV)."""
+    from gtsam_personal_amd import graph as g
+
+    lib = _lib.load()
+    n_types = len(g.FACTOR_ARITY)
+    assert n_types == 14 == len(g.FACTOR_ROWS) == len(g.FACTOR_MEAS) == len(g.FACTOR_VARS)
+    out = (ct.c_int32 * 6)()
+    for t in range(n_types):
+        assert lib.lmgpu_selftest_factor_type(t, out) == 0, t
+        arity, rows, meas, *var = out
+        assert g.FACTOR_ARITY[t] == arity, t
+        assert g.FACTOR_ROWS[t] == rows, t
+        assert tuple(g.FACTOR_VARS[t]) + (-1,) * (3 - arity) == tuple(var), t
+        assert g.FACTOR_MEAS[t] == meas + (2 if t == g.F_PRIOR_CAM else 0), t
+    out[:] = [7] * 6
+    for t in (-1, n_types):  # the internal smart-observation row is not shown
+        assert lib.lmgpu_selftest_factor_type(t, out) == 2
+    assert lib.lmgpu_selftest_factor_type(0, None) == 2
+    assert list(out) == [7] * 6
+    assert len(g.VAR_DIM) == 7 == len(g.VAR_STORE_DEV)
+    vo = (ct.c_int32 * 2)()
+    for t in range(7):
+        assert lib.lmgpu_selftest_var_type(t, vo) == 0, t
+        assert (g.VAR_DIM[t], g.VAR_STORE_DEV[t]) == tuple(vo), t
+    assert lib.lmgpu_selftest_var_type(-1, vo) == 2 and lib.lmgpu_selftest_var_type(7, vo) == 2
+
+
 def test_compute_without_device_fails_loudly():
     graph, initial, _, ordering = make_bal(n_cam=3, n_pt=5, obs_per_point=2, seed=1)
     opt = LevenbergMarquardtOptimizer(graph, initial, ordering, device=-1)
