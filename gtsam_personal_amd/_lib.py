@@ -100,6 +100,12 @@ class lmgpu_ncg_params(ct.Structure):
                 ("relative_error_tol", ct.c_double), ("absolute_error_tol", ct.c_double), ("error_tol", ct.c_double)]
 
 
+class lmgpu_debug_ncg_ctl(ct.Structure):
+    """test hooks only (liblmgpu_test.so): the device's line-search record, NcgCtl of csrc/kernels_ncg.hpp"""
+    _fields_ = [(f, ct.c_double) for f in ("minStep", "maxStep", "newStep", "newError", "step", "alpha", "error", "beta", "dnorm")] + [
+        (f, ct.c_int32) for f in ("done", "trials", "flag", "first")]
+
+
 LMGPU_TRI_VALID, LMGPU_TRI_DEGENERATE, LMGPU_TRI_BEHIND_CAMERA, LMGPU_TRI_OUTLIER, LMGPU_TRI_FAR_POINT, LMGPU_TRI_CALIBRATE_FAILED = 0, 1, 2, 3, 4, 5
 LMGPU_TRI_CAM_BUNDLER, LMGPU_TRI_CAM_S2 = 0, 1  # camera_model of lmgpu_triangulate_batch
 
@@ -292,6 +298,9 @@ TEST_SYMBOLS = {
     "lmgpu_local_group_destroy": (ct.c_int, [ct.c_void_p]),
     "lmgpu_comm_init_local": (ct.c_int, [_H, ct.c_void_p]),
     "lmgpu_debug_table_digest": (ct.c_int, [_H, ct.c_int32, ct.c_char_p, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint64)]),
+    "lmgpu_debug_ncg_direction": (ct.c_int, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _D, _D, _D, _D, _I, ct.POINTER(lmgpu_debug_ncg_ctl)]),
+    "lmgpu_debug_ncg_ls_control": (ct.c_int, [ct.c_int32, ct.POINTER(lmgpu_debug_ncg_ctl), ct.c_int32, _D, ct.c_int32, ct.POINTER(lmgpu_debug_ncg_ctl)]),
+    "lmgpu_debug_ncg_reduce": (ct.c_int, [ct.c_int32, ct.c_int32, _D, ct.c_int32, ct.c_double, _D]),
 }
 
 KT_NAMES = ("linearize", "lds_front", "hbm_assemble", "panel", "syrk", "backsub_hbm", "backsub_lds", "linear_error", "retract_error", "allreduce", "chain")

@@ -90,7 +90,10 @@ int ncg_check(lmgpu_handle* h, const char* who) {
   return ncg_ensure(h);
 }
 
-int ncg_grid(const lmgpu_handle* h) { return std::min(NCG_MAXPART, std::max(1, (h->ntot + 255) / 256)); }
+// blocks of the direction kernels over ntot scalars = block partials per dot product; the kernels stride beyond NCG_MAXPART blocks
+int ncg_grid(int ntot) { return std::min(NCG_MAXPART, std::max(1, (ntot + 255) / 256)); }
+// blocks of ncg_reduce_stage1 over n error terms: reduce_to's rule (lmgpu.hip), so that the partial sums are the same
+int ncg_reduce_grid(int n) { return std::min(256, std::max(1, (n + 255) / 256)); }
 
 // System::gradient at the current values -> g[cur_g] (queued)
 int ncg_enqueue_gradient(lmgpu_handle* h) {
@@ -107,7 +110,7 @@ int ncg_enqueue_gradient(lmgpu_handle* h) {
 // direction = src (queued), with the partials of its squared norm
 int ncg_enqueue_set_direction(lmgpu_handle* h, const double* src) {
   NcgState* s = h->ncg;
-  hipLaunchKernelGGL(ncg_set_direction_kernel, dim3(ncg_grid(h)), dim3(256), 0, h->stream, h->ntot, src, s->dir, s->part_dd, s->ctl);
+  hipLaunchKernelGGL(ncg_set_direction_kernel, dim3(ncg_grid(h->ntot)), dim3(256), 0, h->stream, h->ntot, src, s->dir, s->part_dd, s->ctl);
   HIPCHECK(hipGetLastError());
   return LMGPU_OK;
 }
@@ -115,7 +118,7 @@ int ncg_enqueue_set_direction(lmgpu_handle* h, const double* src) {
 // beta and direction = currentGradient + beta * direction (queued)
 int ncg_enqueue_direction(lmgpu_handle* h, int method) {
   NcgState* s = h->ncg;
-  const int g = ncg_grid(h);
+  const int g = ncg_grid(h->ntot);
   hipLaunchKernelGGL(ncg_dots_kernel, dim3(g), dim3(256), 0, h->stream, h->ntot, (const double*)s->g[s->cur_g], (const double*)s->g[s->cur_g ^ 1],
                      (const double*)s->dir, s->part);
   hipLaunchKernelGGL(ncg_direction_kernel, dim3(g), dim3(256), 0, h->stream, h->ntot, method, (const double*)s->part, g,
@@ -139,12 +142,12 @@ void ncg_launch_retract(lmgpu_handle* h, int final) {
 // On LMGPU_OK the record is in s->h_ctl; the caller flips h->cur.
 int ncg_line_search(lmgpu_handle* h, int advance) {
   NcgState* s = h->ncg;
-  hipLaunchKernelGGL(ncg_ls_begin_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)s->part_dd, ncg_grid(h), s->ctl);
+  hipLaunchKernelGGL(ncg_ls_begin_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)s->part_dd, ncg_grid(h->ntot), s->ctl);
   int queued = 0;
   while (true) {
     const int more = queued == 0 ? NCG_TRIALS_FIRST : std::min(NCG_TRIALS_MORE, NCG_MAX_TRIALS - queued);
     const int32_t* done = &s->ctl->done;
-    const int rg = std::min(256, std::max(1, (h->n_counted + 255) / 256));  // reduce_to's grid: the same partial sums
+    const int rg = ncg_reduce_grid(h->n_counted);
     for (int k = 0; k < more; k++) {
       ncg_launch_retract(h, 0);
       h->err_skip = done;  // the error launches of a trial behind the exit test return at once too
@@ -328,3 +331,131 @@ int lmgpu_ncg_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows4) 
 int lmgpu_ncg_host_waits(const lmgpu_handle* h) { return (h && h->ncg) ? h->ncg->host_waits : 0; }
 
 }  // extern "C"
+
+#ifdef LMGPU_TEST_HOOKS
+// ---- TEST HOOKS (liblmgpu_test.so only; include/lmgpu.h): the kernels of kernels_ncg.hpp on caller data, launched with the shapes and
+//      the grid rules of the path above (ncg_grid, ncg_reduce_grid, reduce_to).  They need a device and no graph.
+namespace {
+
+static_assert(sizeof(lmgpu_debug_ncg_ctl) == sizeof(NcgCtl) && offsetof(lmgpu_debug_ncg_ctl, step) == offsetof(NcgCtl, step) &&
+                  offsetof(lmgpu_debug_ncg_ctl, alpha) == offsetof(NcgCtl, alpha) && offsetof(lmgpu_debug_ncg_ctl, error) == offsetof(NcgCtl, error) &&
+                  offsetof(lmgpu_debug_ncg_ctl, beta) == offsetof(NcgCtl, beta) && offsetof(lmgpu_debug_ncg_ctl, dnorm) == offsetof(NcgCtl, dnorm) &&
+                  offsetof(lmgpu_debug_ncg_ctl, done) == offsetof(NcgCtl, done) && offsetof(lmgpu_debug_ncg_ctl, trials) == offsetof(NcgCtl, trials) &&
+                  offsetof(lmgpu_debug_ncg_ctl, flag) == offsetof(NcgCtl, flag) && offsetof(lmgpu_debug_ncg_ctl, first) == offsetof(NcgCtl, first),
+              "lmgpu_debug_ncg_ctl (lmgpu.h) is NcgCtl (kernels_ncg.hpp) field for field");
+
+// device memory and the stream of one hook call
+struct NcgDebugMem {
+  std::vector<void*> dev;
+  hipStream_t stream = nullptr;
+  ~NcgDebugMem() {
+    for (void* p : dev) (void)hipFree(p);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  template <typename T>
+  T* alloc(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return nullptr;
+    dev.push_back(p);
+    return (T*)p;
+  }
+};
+
+#define NCG_DEBUG_CHECK(expr)                           \
+  do {                                                  \
+    if ((expr) != hipSuccess) return LMGPU_HIP_ERROR;   \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int lmgpu_debug_ncg_direction(int32_t device, int32_t n, int32_t method, int32_t alias, const double* g, const double* gp, double* dir,
+                              double* parts5, int32_t* npart_out, lmgpu_debug_ncg_ctl* ctl_out) {
+  if (n < 1 || method < -1 || method > LMGPU_NCG_DAI_YUAN || !g || !dir || !parts5 || !npart_out || !ctl_out || (method >= 0 && !gp))
+    return LMGPU_INVALID;
+  NCG_DEBUG_CHECK(hipSetDevice(device));
+  NcgDebugMem m;
+  NCG_DEBUG_CHECK(hipStreamCreate(&m.stream));
+  double *dg = m.alloc<double>(n), *dgp = m.alloc<double>(n), *ddir = m.alloc<double>(n), *dpart = m.alloc<double>(5 * NCG_MAXPART);
+  NcgCtl* dctl = m.alloc<NcgCtl>(1);
+  if (!dg || !dgp || !ddir || !dpart || !dctl) return LMGPU_HIP_ERROR;
+  const size_t nb = (size_t)n * sizeof(double);
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dg, g, nb, hipMemcpyHostToDevice, m.stream));
+  if (method >= 0) NCG_DEBUG_CHECK(hipMemcpyAsync(dgp, gp, nb, hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(ddir, dir, nb, hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemsetAsync(dpart, 0xFF, 5 * NCG_MAXPART * sizeof(double), m.stream));  // a partial nobody wrote reads as NaN
+  NCG_DEBUG_CHECK(hipMemsetAsync(dctl, 0xFF, sizeof(NcgCtl), m.stream));
+  const int grid = ncg_grid(n);
+  double* dpart_dd = dpart + 4 * NCG_MAXPART;
+  if (method < 0) {
+    hipLaunchKernelGGL(ncg_set_direction_kernel, dim3(grid), dim3(256), 0, m.stream, n, alias ? (const double*)ddir : (const double*)dg, ddir, dpart_dd,
+                       dctl);
+  } else {
+    hipLaunchKernelGGL(ncg_dots_kernel, dim3(grid), dim3(256), 0, m.stream, n, (const double*)dg, (const double*)dgp, (const double*)ddir, dpart);
+    hipLaunchKernelGGL(ncg_direction_kernel, dim3(grid), dim3(256), 0, m.stream, n, method, (const double*)dpart, grid, (const double*)dg, ddir,
+                       dpart_dd, dctl);
+  }
+  hipLaunchKernelGGL(ncg_ls_begin_kernel, dim3(1), dim3(256), 0, m.stream, (const double*)dpart_dd, grid, dctl);
+  NCG_DEBUG_CHECK(hipGetLastError());
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dir, ddir, nb, hipMemcpyDeviceToHost, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(parts5, dpart, 5 * NCG_MAXPART * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(ctl_out, dctl, sizeof(NcgCtl), hipMemcpyDeviceToHost, m.stream));
+  NCG_DEBUG_CHECK(hipStreamSynchronize(m.stream));
+  *npart_out = grid;
+  return LMGPU_OK;
+}
+
+int lmgpu_debug_ncg_ls_control(int32_t device, const lmgpu_debug_ncg_ctl* ctl_in, int32_t k, const double* errors, int32_t final,
+                               lmgpu_debug_ncg_ctl* records_out) {
+  if (!ctl_in || k < 0 || k > 4096 || !errors || !records_out || (k == 0 && !final)) return LMGPU_INVALID;
+  NCG_DEBUG_CHECK(hipSetDevice(device));
+  NcgDebugMem m;
+  NCG_DEBUG_CHECK(hipStreamCreate(&m.stream));
+  const int nrec = k + (final ? 1 : 0);
+  double* derr = m.alloc<double>(nrec);
+  NcgCtl *dctl = m.alloc<NcgCtl>(1), *drec = m.alloc<NcgCtl>(nrec);
+  if (!derr || !dctl || !drec) return LMGPU_HIP_ERROR;
+  NCG_DEBUG_CHECK(hipMemcpyAsync(derr, errors, nrec * sizeof(double), hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dctl, ctl_in, sizeof(NcgCtl), hipMemcpyHostToDevice, m.stream));
+  for (int i = 0; i < nrec; i++) {
+    if (i < k)
+      hipLaunchKernelGGL(ncg_ls_control_kernel, dim3(1), dim3(64), 0, m.stream, (const double*)(derr + i), dctl);
+    else
+      hipLaunchKernelGGL(ncg_final_kernel, dim3(1), dim3(64), 0, m.stream, (const double*)(derr + i), dctl);
+    NCG_DEBUG_CHECK(hipMemcpyAsync(drec + i, dctl, sizeof(NcgCtl), hipMemcpyDeviceToDevice, m.stream));
+  }
+  NCG_DEBUG_CHECK(hipGetLastError());
+  NCG_DEBUG_CHECK(hipMemcpyAsync(records_out, drec, nrec * sizeof(NcgCtl), hipMemcpyDeviceToHost, m.stream));
+  NCG_DEBUG_CHECK(hipStreamSynchronize(m.stream));
+  return LMGPU_OK;
+}
+
+int lmgpu_debug_ncg_reduce(int32_t device, int32_t n, const double* buf, int32_t skip, double sentinel, double* out2) {
+  if (n < 1 || !buf || !out2) return LMGPU_INVALID;
+  NCG_DEBUG_CHECK(hipSetDevice(device));
+  NcgDebugMem m;
+  NCG_DEBUG_CHECK(hipStreamCreate(&m.stream));
+  double *dbuf = m.alloc<double>(n), *dpartial = m.alloc<double>(2 * 256), *dout = m.alloc<double>(2);
+  int32_t* dskip = m.alloc<int32_t>(1);
+  if (!dbuf || !dpartial || !dout || !dskip) return LMGPU_HIP_ERROR;
+  const double preset[2] = {sentinel, sentinel};
+  const int32_t skip_value = skip < 0 ? 0 : skip;
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dbuf, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dout, preset, sizeof(preset), hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemcpyAsync(dskip, &skip_value, sizeof(int32_t), hipMemcpyHostToDevice, m.stream));
+  NCG_DEBUG_CHECK(hipMemsetAsync(dpartial, 0xFF, 2 * 256 * sizeof(double), m.stream));
+  const int rg = ncg_reduce_grid(n);
+  const int32_t* skip_ptr = skip < 0 ? nullptr : dskip;  // skip < 0: the kernels' form without a flag
+  hipLaunchKernelGGL(ncg_reduce_stage1, dim3(rg), dim3(256), 0, m.stream, (const double*)dbuf, n, dpartial, skip_ptr);
+  hipLaunchKernelGGL(ncg_reduce_stage2, dim3(1), dim3(256), 0, m.stream, (const double*)dpartial, rg, dout, skip_ptr);
+  reduce_to(nullptr, dbuf, n, dout + 1, m.stream, dpartial + 256);  // stream and scratch given: the handle is not read
+  NCG_DEBUG_CHECK(hipGetLastError());
+  NCG_DEBUG_CHECK(hipMemcpyAsync(out2, dout, 2 * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  NCG_DEBUG_CHECK(hipStreamSynchronize(m.stream));
+  return LMGPU_OK;
+}
+
+}  // extern "C"
+#undef NCG_DEBUG_CHECK
+#endif  // LMGPU_TEST_HOOKS

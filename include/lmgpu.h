@@ -347,6 +347,13 @@ int lmgpu_gnc_get_trace(const lmgpu_handle* h, int32_t max_rows, double* rows6);
  *   lmgpu_gradient          gradientAtZero at the current values, lmgpu_total_dim doubles, tangent-packed by slot
  *   lmgpu_ncg_line_search   lineSearch from the current values along dir_packed (NULL: the gradient at the current values); the handle's
  *                           values are left unchanged.  *trials = error evaluations of the search.
+ *                           A search that has not met the exit test after 128 evaluations returns LMGPU_HIP_ERROR after three waits;
+ *                           lmgpu_last_error names |direction| and the bracket, *alpha and *trials are not written, the values are
+ *                           unchanged and the handle stays usable.  This happens when the minimiser of the bracket is step 0 AND the error
+ *                           resolves ever smaller steps (values at 0 moved along the direction), and for an all-zero direction
+ *                           (|direction| = 0: the bracket is [-inf, 0], every step and every error NaN).  An ascent direction on
+ *                           ordinary values does end, with an alpha of no effect: once the steps fall below the spacing of the values
+ *                           the errors tie, the tie moves maxStep off 0 and the exit test is met (about 100 evaluations).
  *   lmgpu_ncg_iterate       NonlinearConjugateGradientOptimizer::iterate (.cpp:71-80): nonlinearConjugateGradient with singleIteration, i.e.
  *                           a gradient-descent step and ONE conjugate step, started over at every call; state: error, iterations + 1
  *   lmgpu_ncg_optimize      optimize (.cpp:82-90): the full loop; state: error, iterations = the loop's count
@@ -913,6 +920,27 @@ int lmgpu_comm_init_local(lmgpu_handle* h, lmgpu_local_group* g);
  * flags) -- its name (32 bytes, zero-terminated), its number of entries and the FNV-1a of its fields.  Available on structure-only
  * handles too.  Writes at most `max` records; returns the number of records the handle has, or -1 before finalize. */
 int lmgpu_debug_table_digest(lmgpu_handle* h, int32_t max, char* names32, uint64_t* counts, uint64_t* fnv1a);
+/* The kernels of the nonlinear conjugate gradient optimizer (csrc/kernels_ncg.hpp) on caller data, launched as lmgpu_ncg_* launches them
+ * (the same block counts: the grid rule is one function both call).  They need a device and no graph; every call allocates, runs on a
+ * stream of its own, waits and frees.  lmgpu_debug_ncg_ctl is the device's line-search record field for field. */
+typedef struct lmgpu_debug_ncg_ctl {
+  double minStep, maxStep, newStep, newError, step, alpha, error, beta, dnorm;
+  int32_t done, trials, flag, first;
+} lmgpu_debug_ncg_ctl;
+/* method 0..3 (LMGPU_NCG_*): the dot-product partials of (g, gp, dir), beta, dir = g + beta * dir, then the head of the line search.
+ * method -1: dir = src and its squared-norm partials instead (beta = 0), src = g (alias 0; gp is not read) or src = dir itself (alias 1: g is
+ * uploaded and not read).  dir (n doubles) is read and overwritten.  parts5: 5 x 256 doubles, the block partials of g.g, g.(g - gp),
+ * gp.gp, dir.(g - gp) and of the new dir.dir; every entry is preset to NaN, so an entry at or beyond *npart_out (and all of the first four
+ * rows under method -1) reads as NaN.  ctl_out: the record after ncg_ls_begin_kernel, preset to all-ones bytes before the first kernel. */
+int lmgpu_debug_ncg_direction(int32_t device, int32_t n, int32_t method, int32_t alias, const double* g, const double* gp, double* dir,
+                              double* parts5, int32_t* npart_out, lmgpu_debug_ncg_ctl* ctl_out);
+/* ncg_ls_control_kernel k times on one stream from the record *ctl_in, launch i reading errors[i]; records_out[i] = the record after
+ * launch i.  final != 0: ncg_final_kernel afterwards, reading errors[k], its record in records_out[k]. */
+int lmgpu_debug_ncg_ls_control(int32_t device, const lmgpu_debug_ncg_ctl* ctl_in, int32_t k, const double* errors, int32_t final,
+                               lmgpu_debug_ncg_ctl* records_out);
+/* out2[0]: ncg_reduce_stage1 / 2 over buf[0 .. n) with the skip flag set to `skip` (skip < 0: no flag at all); out2[1]: the product's
+ * reduce_to over the same buffer.  Both destinations hold `sentinel` before. */
+int lmgpu_debug_ncg_reduce(int32_t device, int32_t n, const double* buf, int32_t skip, double sentinel, double* out2);
 #endif
 
 /* ---- micro-benchmarks used by bench.py for roofline peaks (device-only, no graph needed) ---- */

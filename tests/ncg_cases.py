@@ -29,6 +29,20 @@ ALPHA_RTOL = 10 * max(SPREAD_MEASURED, BRACKET_RTOL)  # 2e-4
 ERROR_RTOL = 10 * max(SPREAD_MEASURED, BRACKET_RTOL)  # 2e-4
 PERTURB_SEEDS = (1, 2, 3)
 SEARCH_GRAPHS = ("five_pose", "pose3_head", "bal_small")
+# The evaluation count of the first line search, probed the same way at eps = 1e-12 (the figure tests/test_gpu_ncg.py holds graph_error to
+# the NCG error by): the graphs on which the count stays as it is under seeds 1, 2, 3 -- there the device's count must EQUAL the
+# restatement's (measured: all three; tests/test_ncg_reference.py::test_trial_counts_are_robust).
+TRIALS_EPS = 1e-12
+TRIALS_EXACT_GRAPHS = ("five_pose", "pose3_head", "bal_small")
+# beta of every trace row (test_each_direction_method_matches_its_restatement).  The device's alpha of a search lies within BRACKET_RTOL of
+# the restatement's, and every later gradient, hence every later beta, follows the alpha before it.  Probe: the restatement with every
+# search's alpha multiplied by (1 + BRACKET_RTOL), by (1 - BRACKET_RTOL), and by (1 +- BRACKET_RTOL) with the sign drawn per search (seeds
+# 1, 2, 3), four iterations, four methods, five_pose and five_pose_huber.  BETA_SPREAD_MEASURED = the largest |beta' - beta| / max(|beta|,
+# BETA_FLOOR) over all of those rows (tests/test_ncg_reference.py::test_beta_spread_holds measures it again); the tolerance is ten times it.
+BETA_FLOOR = 1e-3  # a beta below this (a clamped or nearly clamped one) is compared absolutely against this scale
+BETA_SPREAD_MEASURED = 2.8e-3  # 2.79e-3, five_pose, Hestenes-Stiefel: beta follows the gradient at a line minimum, where alpha's 2e-5 counts
+BETA_RTOL = 10 * BETA_SPREAD_MEASURED
+BETA_GRAPHS = ("five_pose", "five_pose_huber")
 
 
 
@@ -136,6 +150,36 @@ def restated_line_search(name, seed=None):
     st = {}
     alpha = nr.line_search(s, initial, s.gradient(initial), st)
     return alpha, st["trials"], st["bracket"]
+
+
+@functools.lru_cache(maxsize=None)
+def restated_trials(name, seed=None):
+    """evaluations of the first line search; seed: with every error multiplied by (1 +- TRIALS_EPS)"""
+    graph, initial = problem(name)
+    s = nr.OracleSystem(graph, perturb=None if seed is None else np.random.default_rng(seed), eps=TRIALS_EPS)
+    st = {}
+    nr.line_search(s, initial, s.gradient(initial), st)
+    return st["trials"]
+
+
+BETA_MOVES = ("up", "down", 1, 2, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def restated_betas(name, method, move=None, max_iterations=4):
+    """beta of every trace row; move: every search's alpha times (1 + BRACKET_RTOL) ("up"), (1 - BRACKET_RTOL) ("down"), or with the sign
+    drawn per search from the seed `move`"""
+    graph, initial = problem(name)
+    rng = np.random.default_rng(move) if isinstance(move, int) else None
+    fn = {None: None, "up": lambda a: a * (1 + BRACKET_RTOL), "down": lambda a: a * (1 - BRACKET_RTOL)}.get(
+        move, lambda a: a * (1 + (BRACKET_RTOL if rng.integers(0, 2) else -BRACKET_RTOL)))
+    trace = []
+    nr.nonlinear_conjugate_gradient(nr.OracleSystem(graph), initial, nr.Params(maxIterations=max_iterations), False, method, False, trace, fn)
+    return tuple(r[1] for r in trace)
+
+
+def beta_distance(got, want):
+    return abs(got - want) / max(abs(want), BETA_FLOOR)
 
 
 @functools.lru_cache(maxsize=None)

@@ -61,31 +61,37 @@ def dai_yuan(g, gp, direction):
     return _max0(_div(g @ g, -(direction @ (g - gp))))  # .h:65-69
 
 
-def line_search(system, currentValues, gradient, stats=None):
-    """lineSearch (.h:135-181).  stats (a dict, optional): 'trials' = error evaluations, 'bracket' = (minStep, maxStep) at exit."""
-    g = float(np.linalg.norm(gradient))
+RECORD_FIELDS = ("minStep", "maxStep", "newStep", "newError", "step", "alpha", "error", "beta", "dnorm", "done", "trials", "flag", "first")
+
+
+def ls_begin(g, beta=0.0):
+    """head of lineSearch (.h:138-145) as a record: g = |direction|, the bracket [-1 / g, 0], the first interior point.  The record has
+    the fields of the device's NcgCtl (csrc/kernels_ncg.hpp): `step` is the step whose error the next ls_step takes (newStep first,
+    then every testStep), `first` says that newError is still pending, `flag` is the flag of the testStep under evaluation."""
     phi = 0.5 * (1.0 + math.sqrt(5.0))
-    resphi = 2.0 - phi
-    tau = TAU
     minStep = _div(-1.0, g)
     maxStep = 0.0
     newStep = minStep + (maxStep - minStep) / (phi + 1.0)
-    newValues = system.advance(currentValues, newStep, gradient)
-    newError = system.error(newValues)
-    trials = 1
-    while True:
-        flag = (maxStep - newStep > newStep - minStep)
-        testStep = newStep + resphi * (maxStep - newStep) if flag else newStep - resphi * (newStep - minStep)
-        if (maxStep - minStep) < tau * (abs(testStep) + abs(newStep)):
-            if stats is not None:
-                stats["trials"] = trials
-                stats["bracket"] = (minStep, maxStep)
-            return 0.5 * (minStep + maxStep)
-        if trials >= 100000:
-            raise RuntimeError("lineSearch does not terminate (the reference would loop for ever)")
-        testValues = system.advance(currentValues, testStep, gradient)
-        testError = system.error(testValues)
-        trials += 1
+    return dict(minStep=minStep, maxStep=maxStep, newStep=newStep, newError=0.0, step=newStep, alpha=0.0, error=0.0, beta=beta, dnorm=g,
+                done=0, trials=0, flag=0, first=1)
+
+
+def ls_step(rec, e):
+    """one evaluation of lineSearch: e = the error at rec['step'].  The first call takes it as newError (.h:147-148), every later one as
+    testError and updates the working range (:163-178); then the next testStep and the exit test (:151-157).  Returns a new record;
+    a record that is done comes back unchanged."""
+    rec = dict(rec)
+    if rec["done"]:
+        return rec
+    phi = 0.5 * (1.0 + math.sqrt(5.0))
+    resphi = 2.0 - phi
+    tau = TAU
+    minStep, maxStep, newStep, newError = rec["minStep"], rec["maxStep"], rec["newStep"], rec["newError"]
+    if rec["first"]:
+        newError = e
+        rec["first"] = 0
+    else:
+        testStep, testError, flag = rec["step"], e, rec["flag"]
         if testError >= newError:
             if flag:
                 maxStep = testStep
@@ -98,11 +104,40 @@ def line_search(system, currentValues, gradient, stats=None):
                 maxStep = newStep
             newStep = testStep
             newError = testError
+    rec["trials"] += 1
+    flag = (maxStep - newStep > newStep - minStep)
+    testStep = newStep + resphi * (maxStep - newStep) if flag else newStep - resphi * (newStep - minStep)
+    rec["minStep"], rec["maxStep"], rec["newStep"], rec["newError"] = minStep, maxStep, newStep, newError
+    if (maxStep - minStep) < tau * (abs(testStep) + abs(newStep)):
+        rec["alpha"] = 0.5 * (minStep + maxStep)
+        rec["done"] = 1
+    else:
+        rec["flag"] = int(flag)
+        rec["step"] = testStep
+    return rec
 
 
-def nonlinear_conjugate_gradient(system, initial, params, singleIteration, directionMethod=POLAK_RIBIERE, gradientDescent=False, trace=None):
+def line_search(system, currentValues, gradient, stats=None):
+    """lineSearch (.h:135-181) as ls_begin and a loop of ls_step.  stats (a dict, optional): 'trials' = error evaluations, 'bracket' =
+    (minStep, maxStep) at exit."""
+    rec = ls_begin(float(np.linalg.norm(gradient)))
+    while True:
+        rec = ls_step(rec, system.error(system.advance(currentValues, rec["step"], gradient)))
+        if rec["done"]:
+            if stats is not None:
+                stats["trials"] = rec["trials"]
+                stats["bracket"] = (rec["minStep"], rec["maxStep"])
+            return rec["alpha"]
+        if rec["trials"] >= 100000:
+            raise RuntimeError("lineSearch does not terminate (the reference would loop for ever)")
+
+
+def nonlinear_conjugate_gradient(system, initial, params, singleIteration, directionMethod=POLAK_RIBIERE, gradientDescent=False, trace=None,
+                                 moveAlpha=None):
     """nonlinearConjugateGradient (.h:195-289) -> (values, iterations).  trace (a list, optional) receives one
-    (alpha, beta, error, trials) per line search, the uncounted gradient-descent step first."""
+    (alpha, beta, error, trials) per line search, the uncounted gradient-descent step first.  moveAlpha (a function, optional): every
+    line search's alpha goes through it before the advance -- the probe of how far the bracket tolerance moves what follows."""
+    moveAlpha = moveAlpha or (lambda a: a)
     iteration = 0
     currentError = system.error(initial)
     if currentError <= params.errorTol:
@@ -114,7 +149,7 @@ def nonlinear_conjugate_gradient(system, initial, params, singleIteration, direc
     st = {}
     prevValues = currentValues
     prevError = currentError
-    alpha = line_search(system, currentValues, direction, st)
+    alpha = moveAlpha(line_search(system, currentValues, direction, st))
     currentValues = system.advance(prevValues, alpha, direction)
     currentError = system.error(currentValues)
     if trace is not None:
@@ -137,7 +172,7 @@ def nonlinear_conjugate_gradient(system, initial, params, singleIteration, direc
             else:
                 raise RuntimeError("NonlinearConjugateGradientOptimizer: Invalid directionMethod")
             direction = currentGradient + (beta * direction)
-        alpha = line_search(system, currentValues, direction, st)
+        alpha = moveAlpha(line_search(system, currentValues, direction, st))
         prevValues = currentValues
         prevError = currentError
         currentValues = system.advance(prevValues, alpha, direction)
@@ -169,10 +204,11 @@ class Quadratic1D:
 
 class OracleSystem:
     """NonlinearConjugateGradientOptimizer::System (.h:83-98, .cpp:51-69) over the CPU oracle.  A state is a Values.
-    perturb (a numpy Generator, optional): every error is multiplied by (1 +- 1e-15), sign drawn from it -- the probe of how far the
+    perturb (a numpy Generator, optional): every error is multiplied by (1 +- eps), sign drawn from it -- the probe of how far the
     last bits of the error move the bracket sequence (the branch testError >= newError)."""
 
-    def __init__(self, graph, perturb=None):
+    def __init__(self, graph, perturb=None, eps=1e-15):
+        self.eps = eps
         import oracle_harness as oh
         self._oh = oh
         self.graph = graph
@@ -196,7 +232,7 @@ class OracleSystem:
     def error(self, values):
         e = self._problem(values).error()
         if self.perturb is not None:
-            e *= 1.0 + (1e-15 if self.perturb.integers(0, 2) else -1e-15)
+            e *= 1.0 + (self.eps if self.perturb.integers(0, 2) else -self.eps)
         return e
 
     def gradient(self, values):

@@ -73,6 +73,8 @@ def test_line_search_matches_restatement(name):
     print(name, "alpha", alpha, "restated", want, "rel", abs(alpha - want) / abs(want), "trials", trials, want_trials)
     assert np.array_equal(_packed_values(opt), before)
     assert 0 < trials < nr.MAX_TRIALS
+    if name in nc.TRIALS_EXACT_GRAPHS:  # the restatement's count does not move with the last bits of the errors: the device's is the same
+        assert trials == want_trials
     assert abs(alpha - want) <= ALPHA_RTOL * abs(want)
     assert opt.host_waits() == 1
     # the same search along the caller's copy of the gradient
@@ -136,6 +138,9 @@ def test_each_direction_method_matches_its_restatement(name, method):
     assert abs(opt.error() - want) <= ERROR_RTOL * want
     for k in range(1, 5):
         assert abs(tr[k, 2] - want_trace[k][2]) <= ERROR_RTOL * want_trace[k][2]
+    assert tr[0, 1] == 0.0 == want_trace[0][1]
+    for k in range(1, 5):  # beta of every row: the measured tolerance of tests/ncg_cases.py (alpha moves it through the next gradient)
+        assert nc.beta_distance(tr[k, 1], want_trace[k][1]) <= nc.BETA_RTOL, (k, tr[k, 1], want_trace[k][1])
     opt.close()
 
 

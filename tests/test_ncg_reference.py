@@ -102,6 +102,30 @@ def test_measured_constants_hold(name):
     assert all(b < a for a, b in zip([e0] + errs, errs))
 
 
+def test_trial_counts_are_robust():
+    """the graphs on which tests/test_gpu_ncg.py asserts the device's evaluation count: the restatement's count of the first search is
+    unchanged when every error moves by (1 +- 1e-12)"""
+    robust = tuple(n for n in SEARCH_GRAPHS if all(nc.restated_trials(n, s) == nc.restated_trials(n) for s in PERTURB_SEEDS))
+    print({n: nc.restated_trials(n) for n in SEARCH_GRAPHS})
+    assert robust == nc.TRIALS_EXACT_GRAPHS
+    assert all(nc.restated_trials(n) == nc.restated_line_search(n)[1] for n in SEARCH_GRAPHS)
+
+
+def test_beta_spread_holds():
+    """the spread behind BETA_RTOL, measured again: every trace row's beta with each search's alpha moved by +-BRACKET_RTOL"""
+    worst = (0.0, None)
+    for name in nc.BETA_GRAPHS:
+        for method in (nr.FLETCHER_REEVES, nr.POLAK_RIBIERE, nr.HESTENES_STIEFEL, nr.DAI_YUAN):
+            b0 = nc.restated_betas(name, method)
+            assert b0 == tuple(r[1] for r in nc.restated_run(name, 4, method=method)[2]) and b0[0] == 0.0 and min(b0[1:]) > nc.BETA_FLOOR
+            for move in nc.BETA_MOVES:
+                d = max(nc.beta_distance(x, y) for x, y in zip(nc.restated_betas(name, method, move), b0))
+                worst = max(worst, (d, (name, method, move)))
+    print("beta spread", worst)
+    assert worst[0] <= nc.BETA_SPREAD_MEASURED and nc.BETA_RTOL == 10 * nc.BETA_SPREAD_MEASURED
+    assert worst[0] >= nc.BETA_SPREAD_MEASURED / 2  # the recorded figure is the measurement, not a loose cap
+
+
 def test_python_enums_and_symbols_match_the_header():
     h = open(os.path.join(ROOT, "include", "lmgpu.h")).read()
     for name, want in (("LMGPU_NCG_FLETCHER_REEVES", nr.FLETCHER_REEVES), ("LMGPU_NCG_POLAK_RIBIERE", nr.POLAK_RIBIERE),
