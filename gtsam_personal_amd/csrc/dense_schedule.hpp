@@ -1,5 +1,6 @@
 // The launch schedule of one dense (HBM-class) front on the per-front path: which kernel takes which outer panel, decided once from
-// the front's shape (host only, no HIP call; do_eliminate in lmgpu.hip runs the records in order).  Pinned without a device by
+// the front's shape (host only, no HIP call; run_dense_steps in front_launch.hpp runs the records in order, for the batch path and for
+// ISAM2's wide cliques).  Pinned without a device by
 // tests/test_dense_schedule.py through lmgpu_selftest_dense_schedule.
 //
 // Blocked right-looking partial Cholesky, outer panels of DENSE_NBO = 256 rows.  Panel 0 is one dataflow launch

@@ -1504,15 +1504,15 @@ int is_build_front_tables(lmgpu_isam2* S, const std::vector<IsGF>& gfs, const st
   return LMGPU_OK;
 }
 
+// (into a pointer to const: the members of FrontTablesDev, front_launch.hpp)
+template <typename T>
+int is_stage(lmgpu_isam2* S, const std::vector<T>& src, const T** d, bool device_copy = false) {
+  T* p = nullptr;
+  const int rc = is_stage(S, src, &p, device_copy);
+  *d = p;
+  return rc;
+}
 // the front tables in the device arena (the front kernels walk them with chains of dependent reads: one copy for all of them)
-struct FrontTablesDev {
-  FrontDesc* fds = nullptr;
-  FrontFac* ffac = nullptr;
-  FacDesc* fd = nullptr;
-  ChildRef* childs = nullptr;
-  int32_t *cmap = nullptr, *fxoff = nullptr, *list = nullptr, *rowptr = nullptr;
-  RowSrc* rowsrc = nullptr;
-};
 int is_stage_front_tables(lmgpu_isam2* S, const FrontTables& T, FrontTablesDev* D) {
   int rc;
   if (!T.rowptr.empty()) {
@@ -1537,57 +1537,44 @@ void is_lds_launch_shape(const FrontTables& T, int begin, int count, int* nmax, 
   }
   *jcap = (jc + 7) & ~7;
 }
-// a front of more than 139 columns: assembled by row in its n x ld block, then right-looking over 256-row outer panels, the two-launch
-// panel form + the trailing update (lmgpu.hip: panel_alone / the unfused step)
+// ISAM2 eliminates undamped
+static Damping is_no_damping(const lmgpu_isam2* S) { return Damping{0.0, nullptr, S->ones, nullptr}; }
+// a front of more than 139 columns: assembled by row in its n x ld block, then the dense-front schedule in its plainest form (right-looking
+// over 256-row outer panels: diag_potrf + panel_trsm, then the trailing update), run by the batch path's executor.  (The fused and chained
+// forms are one argument away: a change of its own, with measurements.)
 int is_launch_wide_front(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D, int32_t fi) {
   const FrontDesc& F = T.fds[fi];
   const lmgpu_isam2::Clq& c = S->clq[T.cid[fi]];
   const int ld = c.ld, n = c.n;
   double* A = S->pool + c.f_off;
   ISCHECK(hipMemsetAsync(A, 0, (size_t)n * ld * sizeof(double), S->stream));
-  hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, S->stream, F, c.f_off, ld, (const int32_t*)(D.rowptr + T.row_begin.at(fi)),
-                     (const RowSrc*)D.rowsrc, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const FrontFac*)D.ffac, (const FacDesc*)D.fd, S->pool, 1);
-  const int np = (F.nf + NBO - 1) / NBO;
-  for (int i = 0; i < np; i++) {
-    const int k0 = i * NBO, kb = std::min(F.nf, (i + 1) * NBO) - k0, r0 = k0 + kb, cols = n - r0, m = n - r0;
-    hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, S->stream, A, ld, F.nf, k0, kb, F.id, S->d_status, S->inv16);
-    if (cols > 0) hipLaunchKernelGGL(panel_trsm_kernel, dim3((cols + 63) / 64), dim3(256), 0, S->stream, A, ld, n, k0, kb, (const double*)S->inv16);
-    if (m > 0 && m <= 1024) {
-      const int Sx = (m + 63) / 64;
-      hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * Sx, Sx), dim3(256), 0, S->stream, A, ld, n, k0, kb, r0);
-    } else if (m > 0) {
-      const int Tm = (m + 127) / 128;
-      hipLaunchKernelGGL(syrk_mfma_kernel, dim3(Tm, Tm), dim3(256), kSyrkLds, S->stream, A, ld, n, k0, kb, r0, n);
-    }
-  }
-  return LMGPU_OK;
+  launch_assemble_rows(S->stream, D, S->pool, F, c.f_off, ld, T.row_begin.at(fi), true, nullptr);
+  const std::vector<DenseStep> steps =
+      dense_front_schedule(n, F.nf, DENSE_SINGLE, DENSE_FORM_TWO_LAUNCH | DENSE_FORM_NO_FUSE | DENSE_FORM_NO_CHAIN | DENSE_FORM_NO_TAIL);
+  // (one set of 16 x 16 inverses, overwritten panel by panel; no dataflow launch, so no flags; no chained launch, so no ticket orders)
+  const DenseExec X{S->stream, A, nullptr, ld, n, F.nf, F.id, S->d_status, S->inv16, 0, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, false};
+  return run_dense_steps(X, steps, [](int, int) { return LMGPU_INVALID; }, &S->err);  // (one rank: the schedule has no chunk records)
 }
 // one lds_front_kernel launch for the LDS fronts of level l
 void is_launch_lds_level(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D, int l) {
   const int first = T.lv[l].first, count = T.lv[l].second;
   int nmax, jcap;
   is_lds_launch_shape(T, first, count, &nmax, &jcap);
-  const bool wg1024 = nmax > 72 && count <= 256;  // a handful of wide cliques: sixteen waves each (the batch path's rule)
-  auto* kernel = wg1024 ? lds_front_kernel<false, 1024> : lds_front_kernel<false>;
-  const int threads = wg1024 ? 1024 : (nmax <= 24 ? 64 : 256);
-  hipLaunchKernelGGL(kernel, dim3(count), dim3(threads), lds_front_bytes(jcap, nmax, nmax), S->stream, (const int32_t*)(D.list + first), (const FrontDesc*)D.fds,
-                     (const FrontFac*)D.ffac, (const FacDesc*)D.fd, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const int32_t*)D.fxoff, S->pool, 0.0,
-                     (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, nmax, (double*)nullptr, jcap, (const double*)nullptr,
-                     (const char*)nullptr, 0);
+  // a handful of wide cliques: sixteen waves each.  (The batch path decides per size bin: eliminate_level_bins, lmgpu.hip.)
+  const bool wg1024 = nmax > 72 && count <= 256;
+  launch_lds_fronts(S->stream, D, S->pool, S->d_status, is_no_damping(S), wg1024 ? LDS_FRONT_WIDE16 : LDS_FRONT_PLAIN, first, count, nmax <= 24 ? 64 : 256, nmax,
+                    nmax, jcap, nullptr, nullptr, 0);
 }
 // ONE dataflow launch for all the LDS fronts (lds_front_merged_kernel); it relays the status word to the host itself
 void is_launch_merged(lmgpu_isam2* S, const FrontTables& T, const FrontTablesDev& D) {
   const int count = (int)T.list.size();
   int nmax, jcap;
   is_lds_launch_shape(T, 0, count, &nmax, &jcap);
-  const size_t lds = lds_front_bytes(jcap, nmax, nmax);
   // (four waves unless every clique takes the one-wave register path: the blocked Cholesky of the LDS body needs four -- with two, the 30-40
   //  pivots of VisualISAM2Example's root clique were taken one by one: 33 of the 100 us its launch took)
-  auto* kernel = nmax > 72 ? lds_front_merged_kernel<1024> : lds_front_merged_kernel<256>;
+  // (the batch path sizes its merged launches by level_lds_class, lmgpu.hip)
   const int threads = nmax > 72 ? 1024 : (nmax <= 16 ? 64 : 256);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(threads), lds, S->stream, (const int32_t*)D.list, 0, count, (const FrontDesc*)D.fds,
-                     (const FrontFac*)D.ffac, (const FacDesc*)D.fd, (const ChildRef*)D.childs, (const int32_t*)D.cmap, (const int32_t*)D.fxoff, S->pool, 0.0,
-                     (const double*)nullptr, (const double*)S->ones, S->d_status, nmax, jcap, (const double*)nullptr, S->d_eticket, S->h_status_dev);
+  launch_lds_fronts_merged(S->stream, D, S->pool, S->d_status, is_no_damping(S), 0, count, threads, nmax, jcap, S->d_eticket, S->h_status_dev);
 }
 
 // device: the tables into the arena, the status word / tickets / what the next walk needs as pushes, ONE flush, then the merged launch or
@@ -2814,13 +2801,8 @@ int lmgpu_isam2_create(const lmgpu_config* cfg, const lmgpu_isam2_params* prm, l
   ISCHECK(hipHostGetDevicePointer((void**)&S->h_status_dev, S->h_status, 0));
   ISCHECK(hipHostMalloc((void**)&S->h_val, 32 * sizeof(double), hipHostMallocMapped));
   ISCHECK(hipHostGetDevicePointer((void**)&S->h_val_dev, S->h_val, 0));
-  ISCHECK(hipFuncSetAttribute((const void*)lds_front_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-  ISCHECK(hipFuncSetAttribute((const void*)lds_front_kernel<false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-  ISCHECK(hipFuncSetAttribute((const void*)lds_front_merged_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-  ISCHECK(hipFuncSetAttribute((const void*)lds_front_merged_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
+  ISCHECK(front_kernels_set_attributes());
   ISCHECK(hipFuncSetAttribute((const void*)isam2_wildfire_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (kLdsLimitN * kLdsLimitN + LDSB_TAIL) * 8));
-  ISCHECK(hipFuncSetAttribute((const void*)diag_potrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
-  ISCHECK(hipFuncSetAttribute((const void*)syrk_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSyrkLds));
   return LMGPU_OK;
 }
 

@@ -166,7 +166,7 @@ int add_gather_leaf(lmgpu_handle* h, LaunchTables& T, int fi, int c, const std::
   ents.push_back({fr.n - 1, ch.n - 1, 1});
   // (v, v) and (v, rhs) of a separator variable v come from ONE walk of schur_var_kernel over the leaves that see v: a leaf
   // entry in v's list; the pair lists keep the blocks pa < pb < rhs  (split-diagonal form: every block is a pair block)
-  if (!h->schur_split_diag)
+  if (!h->sw.schur_split_diag)
     for (size_t x = 0; x + 1 < ents.size(); x++) {
       if (ents[x].d + 1 > 16) {
         h->err = "Schur gather: a separator variable of more than 15 dimensions does not fit the 16 x 16 tile of schur_var_kernel";
@@ -178,7 +178,7 @@ int add_gather_leaf(lmgpu_handle* h, LaunchTables& T, int fi, int c, const std::
   for (size_t x = 0; x < ents.size(); x++)
     for (size_t y = x; y < ents.size(); y++) {
       if (x + 1 == ents.size()) continue;  // (rhs, rhs): the corner is a scalar reduction
-      if (!h->schur_split_diag && (y == x || y + 1 == ents.size())) continue;
+      if (!h->sw.schur_split_diag && (y == x || y + 1 == ents.size())) continue;
       Ent a = ents[x], b = ents[y];
       if (a.pc > b.pc) std::swap(a, b);
       gp.push_back(GPairTmp{((int64_t)a.pc << 32) | (uint32_t)b.pc, (int16_t)a.d, (int16_t)b.d,
@@ -234,14 +234,14 @@ void build_gather_lists(lmgpu_handle* h, LaunchTables& T, int fi, std::vector<GP
     for (size_t e = i; e < j; e++)
       if (gv[e].leaf) nleaf++;
     const GVarBlock blk{gv[i].pv, gv[i].dv, 0, (int32_t)T.gvent.size(), (int32_t)(j - i), nleaf};
-    const bool is_short = !h->schur_split_diag && nleaf <= SCHUR_VAR_SHORT && (int)(j - i) - nleaf <= SCHUR_VAR_SHORT;
-    if (is_short || h->schur_split_diag) T.gvblk.push_back(blk); else vlongs.push_back(blk);
+    const bool is_short = !h->sw.schur_split_diag && nleaf <= SCHUR_VAR_SHORT && (int)(j - i) - nleaf <= SCHUR_VAR_SHORT;
+    if (is_short || h->sw.schur_split_diag) T.gvblk.push_back(blk); else vlongs.push_back(blk);
     for (int pass = 0; pass < 2; pass++)
       for (size_t e = i; e < j; e++)
         if (gv[e].leaf == (pass == 0)) T.gvent.push_back(gv[e].ent);
     i = j;
   }
-  G.vblk_short = h->schur_split_diag ? 0 : (int)T.gvblk.size() - G.vblk_begin;
+  G.vblk_short = h->sw.schur_split_diag ? 0 : (int)T.gvblk.size() - G.vblk_begin;
   T.gvblk.insert(T.gvblk.end(), vlongs.begin(), vlongs.end());
   G.vblk_count = (int)T.gvblk.size() - G.vblk_begin;
   if (h->h_fronts[fi].child_count == 0) {  // no child adds to this front before its own level: the gather can be the first writer
@@ -255,7 +255,7 @@ void build_gather_lists(lmgpu_handle* h, LaunchTables& T, int fi, std::vector<GP
     covered.reserve(G.pblk_short + G.pblk_long);
     for (int q = 0; q < G.pblk_short + G.pblk_long; q++)
       covered.push_back(((int64_t)T.gpblk[G.pblk_begin + q].pa << 32) | (uint32_t)T.gpblk[G.pblk_begin + q].pb);
-    if (!h->schur_split_diag) {  // a variable block covers (v, v) and (v, rhs); the corner workgroup covers (rhs, rhs)
+    if (!h->sw.schur_split_diag) {  // a variable block covers (v, v) and (v, rhs); the corner workgroup covers (rhs, rhs)
       for (int q = 0; q < G.vblk_count; q++) {
         const int32_t pv = T.gvblk[G.vblk_begin + q].pv;
         covered.push_back(((int64_t)pv << 32) | (uint32_t)pv);
@@ -404,7 +404,7 @@ void build_level_lists(lmgpu_handle* h, LaunchTables& T) {
 // bins, T.lists, h_fronts, T.ffac and T.fd; fills bin_group / bin_group_out / bin_group_maxfac of every level and n_leaf_group_launches.
 void build_leaf_group_bins(lmgpu_handle* h, const LaunchTables& T) {
   h->n_leaf_group_launches = 0;
-  if (dev_switch("LMGPU_NO_LEAF_GROUPS") || dev_switch("LMGPU_NO_LEAFPACK") || h->pcg_structure) return;
+  if (h->sw.no_leaf_groups || h->sw.no_leafpack || h->pcg_structure) return;
   for (LevelWork& L : h->levels)
     for (int b = 6; b < kNumBins; b++) {
       const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
@@ -463,13 +463,13 @@ void build_solve_flags(lmgpu_handle* h, LaunchTables& T) {
   const bool deep = (int)h->levels.size() >= 12, one_rank = h->cfg.world_size == 1;
   h->use_graph = deep;
   h->merge_backsub = deep;
-  if (const char* e = dev_switch("LMGPU_MERGE_BACKSUB")) h->merge_backsub = atoi(e) != 0;
+  if (h->sw.merge_backsub >= 0) h->merge_backsub = h->sw.merge_backsub != 0;
   h->merge_elim = deep && one_rank;
-  if (const char* e = dev_switch("LMGPU_MERGE_ELIM")) h->merge_elim = atoi(e) != 0 && one_rank;
+  if (h->sw.merge_elim >= 0) h->merge_elim = h->sw.merge_elim != 0 && one_rank;
   if (h->elim_segs.empty()) h->merge_elim = false;
-  if (const char* e = getenv("LMGPU_GRAPH")) h->use_graph = atoi(e) != 0;
+  if (h->sw.graph >= 0) h->use_graph = h->sw.graph != 0;
   h->fuse_levels = deep && one_rank;
-  if (const char* e = dev_switch("LMGPU_FUSE_LEVELS")) h->fuse_levels = atoi(e) != 0 && one_rank;
+  if (h->sw.fuse_levels >= 0) h->fuse_levels = h->sw.fuse_levels != 0 && one_rank;
   if (h->merge_elim)
     for (const lmgpu_handle::ElimSeg& E : h->elim_segs)
       for (int q = h->levels[E.lvl_lo].list_begin; q < h->levels[E.lvl_hi].list_begin + h->levels[E.lvl_hi].list_count; q++) {
@@ -483,7 +483,7 @@ void build_solve_flags(lmgpu_handle* h, LaunchTables& T) {
 // offsets and its factors in one 128-byte-aligned record.  Reads the levels' bins, T.lists, h_fronts, T.ffac, T.fd and T.fxoff; fills
 // T.packs and every level's pack_off / pack_stride.  LMGPU_NO_LEAFPACK: none.
 void build_leaf_packs(lmgpu_handle* h, LaunchTables& T) {
-  if (dev_switch("LMGPU_NO_LEAFPACK")) return;
+  if (h->sw.no_leafpack) return;
   std::vector<char>& packs = T.packs;
   for (LevelWork& L : h->levels)
     for (int b = 0; b < kNumBins; b++) {
@@ -609,7 +609,7 @@ void build_fused_levels(lmgpu_handle* h, LaunchTables& T) {
       const Front& fr = P.fronts[fi];
       const FrontDesc& F = h->h_fronts[fi];
       const lmgpu_handle::GatherRange& G = h->gather[fi];
-      if (fr.nf > NBO || (F.pad & 1) || G.leaf_count > 0 || G.pblk_short + G.pblk_long + G.vblk_count > 0 || dev_switch("LMGPU_NO_MED")) continue;
+      if (fr.nf > NBO || (F.pad & 1) || G.leaf_count > 0 || G.pblk_short + G.pblk_long + G.vblk_count > 0 || h->sw.no_med) continue;
       T.med.push_back(fi);
       T.med_fronts.push_back(MedFront{F, h->f_off[fi], h->f_ld[fi], h->row_begin[fi]});
       h->is_med[fi] = 1;
@@ -636,7 +636,7 @@ void build_fused_levels(lmgpu_handle* h, LaunchTables& T) {
     // four waves per workgroup for every role: with sixteen (what a launch of wide LDS fronts alone takes) the kernel is held to 128 VGPRs and the
     // register Cholesky of the dense fronts' diagonal blocks spills (sphere2500: 1.93 vs 1.87 ms)
     L.fuse_threads = 256;
-    if (const char* e = dev_switch("LMGPU_FUSE_THREADS")) L.fuse_threads = atoi(e) == 1024 && threads == 1024 ? 1024 : 256;
+    if (h->sw.fuse_threads) L.fuse_threads = h->sw.fuse_threads == 1024 && threads == 1024 ? 1024 : 256;
     for (int q = 0; q < L.list_count; q++) tasks.push_back(LevelTask{0, L.list_begin + q, 0, 0});
     for (int m = 0; m < L.med_count; m++) {
       const FrontDesc& F = T.med_fronts[L.med_begin + m].F;

@@ -47,7 +47,7 @@
 
 // Development switches (A/B forms of the same arithmetic, cross-checked by tests/test_gpu_lookahead.py): read from the environment by the
 // TEST library only (liblmgpu_test.so, -DLMGPU_TEST_HOOKS).  The product library has two: LMGPU_GRAPH (graph replay on / off) and
-// LMGPU_ISAM2_TRACE (phase times of the incremental path on stderr).
+// LMGPU_ISAM2_TRACE (phase times of the incremental path on stderr).  The batch path's are listed in DevSwitches below.
 static const char* dev_switch(const char* name) {
 #ifdef LMGPU_TEST_HOOKS
   return getenv(name);
@@ -59,6 +59,83 @@ static const char* dev_switch(const char* name) {
 
 
 using namespace lmgpu;
+
+// Every development switch of the batch path, read ONCE, when the handle is created (read_dev_switches): a test sets them before it
+// builds its optimizer.  (ISAM2's LMGPU_ISAM2_* switches are read per call on a live handle: isam2.hpp.)
+// Tri-state switches: -1 = unset, the structure decides (build_solve_flags).
+struct DevSwitches {
+  // ---- dense fronts on the per-front path (dense_schedule.hpp, kernels_potrf.hpp, kernels_step.hpp)
+  bool two_launch_panel = false;  // LMGPU_PANEL_2L=1: diag_potrf + panel_trsm for every outer panel (A/B)
+  bool no_fuse = false;           // LMGPU_NO_FUSE=1: trailing update and next panel as separate launches (A/B)
+  bool no_chain = false;          // LMGPU_NO_CHAIN=1: one launch per fused step instead of one per run of steps (A/B)
+  bool no_tail = false;           // LMGPU_NO_TAIL=1: the end of a front as separate update / panel launches (A/B)
+  bool tail_scalar = false;       // LMGPU_TAIL_SCALAR=1: front_tail_scalar_kernel, the LDS / scalar-FMA form (cross-check)
+  int chain_forms = 0;            // CHAIN_FORM_* bits: LMGPU_CHAIN_FENCED_TILES, LMGPU_CHAIN_PREREAD (kernels_step.hpp)
+  bool chain_merge = true;        // LMGPU_NO_MERGE: update tiles one step per pass instead of pairs of steps (chain_schedule)
+  int chain_split_pct = 60;       // LMGPU_CHAIN_SPLIT: share of a block's update tasks listed in front of its row-panel workgroups
+  int chain_far_pct = 50;         // LMGPU_CHAIN_FAR: tile rows beyond this percentage of the front are scheduled late (chain_schedule)
+  bool no_med = false;            // LMGPU_NO_MED: one-panel fronts on the per-front path instead of the batched launches per level
+  // ---- Schur-form assembly (kernels_schur.hpp)
+  bool no_gather_write = false;   // LMGPU_NO_GATHER_WRITE=1: clear the front and add (A/B)
+  bool schur_split_diag = false;  // LMGPU_SCHUR_SPLIT_DIAG: (v, v) and (v, rhs) as pair blocks + schur_factor_kernel (A/B)
+  bool schur_unmasked = false;    // LMGPU_SCHUR_UNMASKED: operand loads by every lane instead of only the lanes holding an element
+  // ---- LDS fronts (kernels_front.hpp, kernels_leaf.hpp, kernels_level.hpp)
+  bool no_wide16 = false;         // LMGPU_NO_WIDE16=1: LDS fronts always with four waves (A/B)
+  int wide16_max = 256;           // LMGPU_WIDE16_MAX: launches of at most this many wide LDS fronts take sixteen waves per front
+  bool no_leaf_groups = false;    // LMGPU_NO_LEAF_GROUPS: lds_front_kernel<true> where lds_front_group_kernel would run (A/B)
+  bool no_leafpack = false;       // LMGPU_NO_LEAFPACK: no packed leaf records (and so no leaf groups): the general descriptor path
+  int leaf_group_threads = 256;   // LMGPU_LEAF_GROUP_THREADS=64|128|256: workgroup size of lds_front_group_kernel (A/B)
+  int merge_elim = -1;            // LMGPU_MERGE_ELIM=0/1: LDS fronts of consecutive levels in one dataflow launch on the way up
+  int fuse_levels = -1;           // LMGPU_FUSE_LEVELS=0/1: a level's LDS fronts and medium fronts in one launch
+  int fuse_threads = 0;           // LMGPU_FUSE_THREADS=1024: that launch with sixteen waves where its LDS fronts would take them (0: unset)
+  // ---- back-substitution
+  int merge_backsub = -1;         // LMGPU_MERGE_BACKSUB=0/1: LDS fronts of consecutive levels in one dataflow launch on the way down
+  bool no_backsub_groups = false; // LMGPU_NO_BACKSUB_GROUPS: lds_backsub_kernel (a wave per front) where lds_backsub_group_kernel would run (A/B)
+  bool bsd_ticket = false;        // LMGPU_BSD_TICKET=1: the block back-substitution always draws tickets (the path of levels with more blocks than CUs)
+  bool no_bsd_runs = false;       // LMGPU_NO_BSD_RUNS: the block-solved fronts level by level instead of a run of levels per launch
+  bool no_inv16_reuse = false;    // LMGPU_NO_INV16_REUSE: the dense back-solve inverts its diagonal blocks itself (the fallback form)
+  bool backsolve_hop64 = false;   // LMGPU_BACKSOLVE_HOP64: 64-row hops (hbm_backsolve_dataflow2_kernel) in place of the 128-row form
+  // ---- PCG
+  bool pcg_fused = false;         // LMGPU_PCG_FUSED=1: the forward product recomputed inside the transpose gather (A/B)
+  // ---- product library as well (plain getenv)
+  int graph = -1;                 // LMGPU_GRAPH=0/1: replay the solve's launch sequence as a graph; unset: deep trees do
+};
+
+static DevSwitches read_dev_switches() {
+  DevSwitches w;
+  auto on = [](const char* name) { return dev_switch(name) != nullptr; };
+  auto tri = [](const char* e) { return e ? (atoi(e) != 0 ? 1 : 0) : -1; };
+  w.two_launch_panel = on("LMGPU_PANEL_2L");
+  w.no_fuse = on("LMGPU_NO_FUSE");
+  w.no_chain = on("LMGPU_NO_CHAIN");
+  w.no_tail = on("LMGPU_NO_TAIL");
+  w.tail_scalar = on("LMGPU_TAIL_SCALAR");
+  w.chain_forms = (on("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (on("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
+  w.chain_merge = !on("LMGPU_NO_MERGE");
+  if (const char* e = dev_switch("LMGPU_CHAIN_SPLIT")) w.chain_split_pct = std::max(0, std::min(100, atoi(e)));
+  if (const char* e = dev_switch("LMGPU_CHAIN_FAR")) w.chain_far_pct = std::max(10, std::min(100, atoi(e)));
+  w.no_med = on("LMGPU_NO_MED");
+  w.no_gather_write = on("LMGPU_NO_GATHER_WRITE");
+  w.schur_split_diag = on("LMGPU_SCHUR_SPLIT_DIAG");
+  w.schur_unmasked = on("LMGPU_SCHUR_UNMASKED");
+  w.no_wide16 = on("LMGPU_NO_WIDE16");
+  if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) w.wide16_max = atoi(e);
+  w.no_leaf_groups = on("LMGPU_NO_LEAF_GROUPS");
+  w.no_leafpack = on("LMGPU_NO_LEAFPACK");
+  if (const char* e = dev_switch("LMGPU_LEAF_GROUP_THREADS")) w.leaf_group_threads = atoi(e) == 64 ? 64 : (atoi(e) == 128 ? 128 : 256);
+  w.merge_elim = tri(dev_switch("LMGPU_MERGE_ELIM"));
+  w.fuse_levels = tri(dev_switch("LMGPU_FUSE_LEVELS"));
+  if (const char* e = dev_switch("LMGPU_FUSE_THREADS")) w.fuse_threads = atoi(e) == 1024 ? 1024 : 256;
+  w.merge_backsub = tri(dev_switch("LMGPU_MERGE_BACKSUB"));
+  w.no_backsub_groups = on("LMGPU_NO_BACKSUB_GROUPS");
+  w.bsd_ticket = on("LMGPU_BSD_TICKET");
+  w.no_bsd_runs = on("LMGPU_NO_BSD_RUNS");
+  w.no_inv16_reuse = on("LMGPU_NO_INV16_REUSE");
+  w.backsolve_hop64 = on("LMGPU_BACKSOLVE_HOP64");
+  w.pcg_fused = on("LMGPU_PCG_FUSED");
+  w.graph = tri(getenv("LMGPU_GRAPH"));
+  return w;
+}
 
 #define HIPCHECK(expr)                                                                         \
   do {                                                                                         \
@@ -180,6 +257,8 @@ const int kSyrkLds = 2 * 2 * SYRK_KC * SYRK_LDW * 8;
 
 }  // namespace
 
+#include "front_launch.hpp"  // the front kernels' launchers and the dense-front executor (shared with isam2.hpp)
+
 // In-process stand-in for the RCCL communicator: W handles of ONE process (one thread each) sum their buffers through a
 // host rendezvous.  Same call sites and semantics as the ncclAllReduce path; exists so that the sharded LM loop can be
 // exercised end to end on a single GPU (two RCCL ranks may not share a device).  Not a performance path.
@@ -238,6 +317,7 @@ static bool smart_refused(lmgpu_handle* h, const char* who);
 
 struct lmgpu_handle {
   lmgpu_config cfg;
+  DevSwitches sw;  // the development switches, as read by lmgpu_create
   int device = -1;
   std::string err;
   int failed_slot = -1;
@@ -259,8 +339,6 @@ struct lmgpu_handle {
   hipStream_t stream = nullptr;
   double *bs_inv = nullptr, *bs_x = nullptr;  // dataflow back-substitution scratch
   double* inv16 = nullptr;                     // 16 x (16x16) inverses of the current outer panel's diagonal tiles
-  bool two_launch_panel = false;               // LMGPU_PANEL_2L=1: diag_potrf + panel_trsm for every outer panel (A/B)
-  bool no_fuse = false;                        // LMGPU_NO_FUSE=1: trailing update and next panel as separate launches (A/B)
   // per dense front on the per-front path: its launch schedule (dense_schedule.hpp) and, per DENSE_CHAIN record, the ticket order of
   // that launch as a range of d_chain_tasks.  Built by ensure_dense_schedules before a solve is queued; dense_mode = the communicator
   // they were built for (-1: not built)
@@ -268,9 +346,6 @@ struct lmgpu_handle {
   std::vector<DensePlan> dense_plans;
   int2* d_chain_tasks = nullptr;
   int dense_mode = -1;
-  int chain_split_pct = 60;                    // LMGPU_CHAIN_SPLIT (development): share of a block's update tasks listed in front of its row-panel workgroups
-  bool chain_merge = true;                     // LMGPU_NO_MERGE: update tiles one step per pass instead of pairs of steps (chain_schedule)
-  int chain_far_pct = 50;                      // LMGPU_CHAIN_FAR: tile rows beyond this percentage of the front are scheduled late (chain_schedule)
   double* d_lambda = nullptr;   // damping parameter of the solve being queued (device memory: see do_solve_enqueue)
   bool merge_backsub = false;   // LDS fronts of consecutive levels in one dataflow launch (deep trees; LMGPU_MERGE_BACKSUB=0/1)
   // the same on the way up: runs of consecutive levels without dense fronts in between whose LDS fronts go as ONE launch
@@ -293,16 +368,7 @@ struct lmgpu_handle {
   bool use_graph = false;       // replay the solve's launch sequence as a hipGraph (deep trees; LMGPU_GRAPH=0/1 overrides)
   int eager_solves = 0;
   hipGraphExec_t solve_graph[2] = {nullptr, nullptr};  // [1]: with the extra gradient vector of the marginal solves
-  int leaf_group_threads = 256;                // LMGPU_LEAF_GROUP_THREADS=64|128|256: its workgroup size (A/B)
-  bool no_backsub_groups = false;              // LMGPU_NO_BACKSUB_GROUPS: lds_backsub_kernel (a wave per front) where lds_backsub_group_kernel would run (A/B)
   int n_leaf_group_launches = 0;               // gather-leaf bin launches that take lds_front_group_kernel (lmgpu_leaf_group_launches)
-  bool no_wide16 = false;                      // LMGPU_NO_WIDE16=1: LDS fronts always with four waves (A/B)
-  int wide16_max = 256;                        // launches of at most this many wide LDS fronts take sixteen waves per front (LMGPU_WIDE16_MAX)
-  bool bsd_ticket = false;                     // LMGPU_BSD_TICKET=1: the block back-substitution always draws tickets (tests: the path of levels with more blocks than CUs)
-  bool no_tail = false;                        // LMGPU_NO_TAIL=1: the end of a front as separate update / panel launches (A/B)
-  bool tail_scalar = false;                    // LMGPU_TAIL_SCALAR=1: front_tail_scalar_kernel, the LDS / scalar-FMA form (cross-check)
-  bool no_chain = false;                       // LMGPU_NO_CHAIN=1: one launch per fused step instead of one per run of steps (A/B)
-  int chain_forms = 0;                         // test library: CHAIN_FORM_* bits (LMGPU_CHAIN_FENCED_TILES, LMGPU_CHAIN_PREREAD; kernels_step.hpp)
   unsigned int* d_pflags = nullptr;            // hand-off flags of panel_dataflow_kernel, PDF_FLAG_WORDS per outer panel
   int pflags_panels = 0;
   unsigned int* bs_flags = nullptr;
@@ -323,6 +389,7 @@ struct lmgpu_handle {
   FrontFac* d_ffac = nullptr;
   ChildRef* d_childs = nullptr;
   int32_t *d_cmap = nullptr, *d_fxoff = nullptr, *d_sxoff = nullptr, *d_lists = nullptr;
+  FrontTablesDev tabs;  // the same tables as the launchers take them (front_launch.hpp): filled by upload_launch_tables
   int32_t *d_hbm_small = nullptr, *d_f_ld = nullptr, *d_med_list = nullptr;
   MedFront* d_med_fronts = nullptr;     // packed records of the medium fronts, level by level (same order as d_med_list)
   BsdBlock* d_bsd_table = nullptr;      // 64-row blocks of the smaller HBM fronts, per level, each front from its last block to its first
@@ -375,8 +442,6 @@ struct lmgpu_handle {
   GPairBlock* d_gpblk = nullptr;
   GZeroBlock* d_gzero = nullptr;
   int n_hbm_fronts = 0;          // number of HBM-class fronts on this rank (selects the clearing regime in do_eliminate)
-  bool no_gather_write = false;  // LMGPU_NO_GATHER_WRITE=1: clear the front and add (A/B)
-  bool schur_split_diag = false; // LMGPU_SCHUR_SPLIT_DIAG (test library): (v, v) and (v, rhs) as pair blocks + schur_factor_kernel (A/B)
   GPairEntry* d_gpent = nullptr;
   GVarBlock* d_gvblk = nullptr;
   GVarEntry* d_gvent = nullptr;
@@ -424,7 +489,6 @@ struct lmgpu_handle {
   bool pcg_ready = false;       // the PCG buffers below exist
   bool pcg_gram_valid = false;  // pcg_H / pcg_rhs hold the blocks of the current linearization
   bool pcg_have_stats = false;
-  bool pcg_fused = false;       // LMGPU_PCG_FUSED=1 (test library): the forward product recomputed inside the transpose gather (A/B)
   int pcg_cap = 0;              // iterations pcg_gam / pcg_done can hold
   int32_t* pcg_xoff = nullptr;
   int64_t *pcg_loff = nullptr, *pcg_yoff = nullptr;
@@ -656,7 +720,7 @@ int fill_dampw(lmgpu_handle* h, int diagonal, double min_diag, double max_diag) 
 // blocks it does not cover clears.
 static bool gather_writes(const lmgpu_handle* h, int fi) {
   const lmgpu_handle::GatherRange& G = h->gather[fi];
-  if (!(G.write_ok && G.leaf_count > 0 && !h->no_gather_write && h->n_hbm_fronts <= 4)) return false;
+  if (!(G.write_ok && G.leaf_count > 0 && !h->sw.no_gather_write && h->n_hbm_fronts <= 4)) return false;
   if (h->s_off[fi] < 0) return true;
   return (h->h_fronts[fi].pad & 1) != 0 && (h->comm || h->lgroup);  // the partial-assembly buffer is in use (`split` below)
 }
@@ -664,32 +728,6 @@ static bool gather_writes(const lmgpu_handle* h, int fi) {
 static void add_fill(std::vector<FillChunk>& t, const void* p, size_t bytes, uint32_t value) {
   for (size_t o = 0; o < bytes; o += FILL_CHUNK_BYTES)
     t.push_back(FillChunk{(unsigned long long)(uintptr_t)p + o, (uint32_t)std::min<size_t>(FILL_CHUNK_BYTES, bytes - o), value});
-}
-
-// own factors and children's update matrices of HBM front fi, assembled at pool offset aoff: one wave per row of the front walks that
-// row's sources in a fixed order (no atomics, bitwise reproducible); with_factors = false on the ranks that leave the own terms to rank 0
-// Returns whether the launch was made.  damp: the wave that owns a frontal row also adds that row's damping term (and gex) behind the
-// row's last source -- what hbm_damp_kernel adds behind this launch, the same additions in the same order, without the launch.
-static bool launch_assemble_rows(lmgpu_handle* h, int fi, int64_t aoff, bool with_factors, bool damp = false, double lambda_v = 0.0,
-                                 const double* lambda_p = nullptr) {
-  const FrontDesc& F = h->h_fronts[fi];
-  if (!(h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))) return false;
-  if (damp)
-    hipLaunchKernelGGL(hbm_assemble_rows_damp_kernel, dim3((F.n + 3) / 4), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi],
-                       (const int32_t*)(h->d_rowptr + h->row_begin[fi]), (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                       (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0, (const int32_t*)h->d_fxoff, lambda_v, lambda_p,
-                       (const double*)h->dampw, (const double*)h->gex_active);
-  else
-    hipLaunchKernelGGL(hbm_assemble_rows_kernel, dim3((F.n + 3) / 4), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi], (const int32_t*)(h->d_rowptr + h->row_begin[fi]),
-                       (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const FrontFac*)h->d_ffac,
-                       (const FacDesc*)h->d_fd, h->pool, with_factors ? 1 : 0);
-  return true;
-}
-
-static void launch_hbm_damp(lmgpu_handle* h, int fi, int64_t aoff, double lambda_v, const double* lambda_p) {
-  const FrontDesc& F = h->h_fronts[fi];
-  hipLaunchKernelGGL(hbm_damp_kernel, dim3((F.nf + 255) / 256), dim3(256), 0, h->stream, F, aoff, h->f_ld[fi], (const int32_t*)h->d_fxoff, h->pool, lambda_v,
-                     lambda_p, (const double*)h->dampw, (const double*)h->gex_active);
 }
 
 // how the assembled rows of HBM front fi reach its working matrix (dense_schedule.hpp): in place, or -- a replicated front with a
@@ -737,8 +775,8 @@ static int add_chunk(lmgpu_handle* h, double* A, double* Asm, int n, int ld, int
 static int ensure_dense_schedules(lmgpu_handle* h) {
   const int mode = h->comm ? DENSE_SPLIT_EVENTS : h->lgroup ? DENSE_SPLIT_HOST : DENSE_SINGLE;
   if (h->dense_mode == mode) return LMGPU_OK;
-  const unsigned forms = (h->two_launch_panel ? DENSE_FORM_TWO_LAUNCH : 0u) | (h->no_fuse ? DENSE_FORM_NO_FUSE : 0u) |
-                         (h->no_chain ? DENSE_FORM_NO_CHAIN : 0u) | (h->no_tail ? DENSE_FORM_NO_TAIL : 0u);
+  const unsigned forms = (h->sw.two_launch_panel ? DENSE_FORM_TWO_LAUNCH : 0u) | (h->sw.no_fuse ? DENSE_FORM_NO_FUSE : 0u) |
+                         (h->sw.no_chain ? DENSE_FORM_NO_CHAIN : 0u) | (h->sw.no_tail ? DENSE_FORM_NO_TAIL : 0u);
   std::vector<int2> tasks;
   h->dense_plans.assign(h->h_fronts.size(), lmgpu_handle::DensePlan());
   for (const LevelWork& L : h->levels)
@@ -755,7 +793,7 @@ static int ensure_dense_schedules(lmgpu_handle* h) {
       P.task_count.assign(P.steps.size(), 0);
       for (size_t r = 0; r < P.steps.size(); r++) {
         if (P.steps[r].kind != DENSE_CHAIN) continue;
-        const std::vector<int2> t = chain_schedule(F.n, F.nf, P.steps[r].i, P.steps[r].nsteps, h->chain_far_pct, h->chain_merge, h->chain_split_pct);
+        const std::vector<int2> t = chain_schedule(F.n, F.nf, P.steps[r].i, P.steps[r].nsteps, h->sw.chain_far_pct, h->sw.chain_merge, h->sw.chain_split_pct);
         P.task_begin[r] = (int)tasks.size();
         P.task_count[r] = (int)t.size();
         tasks.insert(tasks.end(), t.begin(), t.end());
@@ -871,28 +909,164 @@ static int ensure_fill_tables(lmgpu_handle* h) {
   return LMGPU_OK;
 }
 
+// the clears: the HBM fronts (hbm_clear_regime), the status words and the counters of the merged and fused launches
+static int eliminate_clears(lmgpu_handle* h) {
+  hipStream_t s = h->stream;
+  const int kt0 = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
+  int64_t lo, hi;
+  const int regime = hbm_clear_regime(h, &lo, &hi);
+  if (regime == HBM_CLEAR_RANGES && h->n_zero_ranges > 0)
+    hipLaunchKernelGGL(zero_ranges_kernel, dim3(16, h->n_zero_ranges), dim3(256), 0, s, (const ZeroRange*)h->d_zero_ranges, h->pool);
+  if (regime == HBM_CLEAR_EACH)
+    for (const LevelWork& L : h->levels)
+      for (int fi : L.hbm) {
+        // gather_writes: the upper triangle of the buffer the front is assembled into is written by the gather and a list of
+        // uncovered blocks -- the front itself on one rank, the partial-assembly buffer with several
+        const bool gw = gather_writes(h, fi);
+        const size_t bytes = (size_t)h->h_fronts[fi].n * h->f_ld[fi] * sizeof(double);
+        if (!gw || h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->f_off[fi], 0, bytes, s));
+        if (!gw && h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->s_off[fi], 0, bytes, s));
+      }
+  hipLaunchKernelGGL(fill_chunks_kernel, dim3(h->n_fill_elim), dim3(256), 0, s, (const FillChunk*)h->d_fill_elim);
+  h->kt.end(kt0, s);
+  return LMGPU_OK;
+}
+
+// the LDS fronts of level L, one launch per size bin
+static void eliminate_level_bins(lmgpu_handle* h, const LevelWork& L, const Damping& dmp) {
+  hipStream_t s = h->stream;
+  for (int b = 0; b < kNumBins; b++) {
+    const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
+    if (cnt == 0) continue;
+    const int nmax = kBinN[b % 6], jcap = L.bin_jcap[b];
+    const char* pack = h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr;
+    const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
+    if (L.bin_group[b]) {  // every leaf of the bin qualifies (leaf_group_form): four leaves per wave, one lane per factor
+      launch_leaf_groups(s, h->pool, h->d_status, dmp, L.bin_group[b], h->d_leafpack + L.pack_off[b], L.pack_stride[b], cnt, jcap, L.bin_group_out[b],
+                         L.bin_group_maxfac[b], h->sw.leaf_group_threads, h->d_gcorner);
+    } else {
+      // (the thread rules of ISAM2's launches differ: is_launch_lds_level, isam2.hpp)
+      // gather leaves keep only nf rows: one wave per front (barriers become free, ~2.5x more fronts resident per CU)
+      const int threads = (b >= 6 || b % 6 == 0) ? 64 : (b % 6 == 1 ? 128 : 256);
+      // a handful of wide fronts (the upper levels of a general sparse tree, where a launch lasts as long as its slowest front and the
+      // device is idle): sixteen waves per front -- the rank-4 trailing updates, the extend-add and the emission all scale with them
+      const bool wide16 = b >= 3 && b < 6 && cnt <= h->sw.wide16_max && !h->sw.no_wide16;
+      launch_lds_fronts(s, h->tabs, h->pool, h->d_status, dmp, wide16 ? LDS_FRONT_WIDE16 : (b < 6 ? LDS_FRONT_PLAIN : LDS_FRONT_GATHER_LEAF),
+                        L.list_begin + L.bin_begin[b], cnt, threads, nmax, L.bin_srows[b], jcap, h->d_gcorner, pack, L.pack_stride[b]);
+    }
+    h->kt.end(kt, s);
+  }
+}
+
+// The assembly of HBM front fi into the n x ld block at pool offset aoff: the blocks no gather list covers, its children's update
+// matrices and own factors by row, its leaf children in Schur form, then -- behind a gather that wrote -- the own factors and the damping.
+static void assemble_hbm_front(lmgpu_handle* h, int fi, int64_t aoff, const Damping& dmp) {
+  hipStream_t s = h->stream;
+  const FrontDesc& F = h->h_fronts[fi];
+  const int ld = h->f_ld[fi];
+  const bool own_terms = (F.pad & 2) == 0;
+  const lmgpu_handle::GatherRange& G = h->gather[fi];
+  const bool gwrite = gather_writes(h, fi);
+  // the row assembly, when the front has sources for it: whether the launch was made
+  auto assemble_rows = [&](bool with_factors, bool damp) {
+    if (!(h->row_begin[fi] >= 0 && (F.child_count > 0 || (with_factors && F.fac_count > 0)))) return false;
+    launch_assemble_rows(s, h->tabs, h->pool, F, aoff, ld, h->row_begin[fi], with_factors, damp ? &dmp : nullptr);
+    return true;
+  };
+  if (gwrite && G.zero_count > 0)
+    hipLaunchKernelGGL(zero_blocks_kernel, dim3(G.zero_count), dim3(128), 0, s, (const GZeroBlock*)(h->d_gzero + G.zero_begin), h->pool, aoff, ld);
+  // (the damping rides in the row assembly where there is one; a front without sources here keeps hbm_damp_kernel)
+  const bool damp_here = !gwrite && own_terms;
+  if (!assemble_rows(own_terms && !gwrite, damp_here) && damp_here) launch_hbm_damp(s, h->tabs, h->pool, F, aoff, ld, dmp);
+  // leaf children in Schur form: deterministic gather instead of atomics
+  const int schur_masked = h->sw.schur_unmasked ? 0 : 2;  // (operand loads that only the lanes holding an element take part in)
+  // (LMGPU_SCHUR_UNMASKED reaches schur_pairs_kernel and the split form's schur_factor_kernel; schur_var_kernel has the masked loads only)
+  if (G.pblk_short > 0)
+    hipLaunchKernelGGL((schur_pairs_kernel<1>), dim3((G.pblk_short + 7) & ~7), dim3(64), 0, s, (const GPairBlock*)(h->d_gpblk + G.pblk_begin),
+                       (const GPairEntry*)h->d_gpent, h->pool, aoff, ld, G.pblk_short, (gwrite ? 1 : 0) | schur_masked);
+  if (G.pblk_long > 0)
+    hipLaunchKernelGGL((schur_pairs_kernel<4>), dim3((G.pblk_long + 7) & ~7), dim3(256), 0, s,
+                       (const GPairBlock*)(h->d_gpblk + G.pblk_begin + G.pblk_short), (const GPairEntry*)h->d_gpent, h->pool, aoff, ld,
+                       G.pblk_long, (gwrite ? 1 : 0) | schur_masked);
+#ifdef LMGPU_TEST_HOOKS
+  if (h->sw.schur_split_diag) {
+    if (G.vblk_count > 0)
+      hipLaunchKernelGGL(schur_factor_kernel, dim3(G.vblk_count), dim3(64 * SCHUR_FW), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
+                         (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
+    if (G.leaf_count > 0) {  // the (rhs, rhs) corner
+      double* scal = h->dscal + 4;
+      reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, s, nullptr);
+      hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, s, h->pool + aoff + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
+    }
+  } else
+#endif
+  {
+    // one workgroup per separator variable writes (adds) its (v, v) and (v, rhs); the last launch carries one more workgroup,
+    // which sums the leaves' (rhs, rhs) scalars into the corner
+    const int vlong = G.vblk_count - G.vblk_short;
+    const int corner_short = (G.leaf_count > 0 && vlong == 0) ? 1 : 0, corner_long = (G.leaf_count > 0 && vlong > 0) ? 1 : 0;
+    if (G.vblk_short + corner_short > 0)
+      hipLaunchKernelGGL((schur_var_kernel<1>), dim3(G.vblk_short + corner_short), dim3(64), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
+                         (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, G.vblk_short, gwrite ? 1 : 0,
+                         (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
+    if (vlong + corner_long > 0)
+      hipLaunchKernelGGL((schur_var_kernel<SCHUR_VAR_WAVES>), dim3(vlong + corner_long), dim3(64 * SCHUR_VAR_WAVES), 0, s,
+                         (const GVarBlock*)(h->d_gvblk + G.vblk_begin + G.vblk_short), (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, vlong,
+                         gwrite ? 1 : 0, (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
+  }
+  if (gwrite && own_terms) {  // the front's own factors and the damping are added: after the gather has initialised the entries
+    // (a gather-write front has no update-matrix children: only its factors are added here, the damping behind them in the same launch)
+    if (!(F.fac_count > 0 && assemble_rows(true, true))) launch_hbm_damp(s, h->tabs, h->pool, F, aoff, ld, dmp);
+  }
+}
+
+// HBM front fi on the per-front path: assembly, the all-reduces of a split front's row chunks, then the front's schedule
+// (dense_schedule.hpp, built by ensure_dense_schedules) record by record
+static int eliminate_hbm_front(lmgpu_handle* h, int fi, const Damping& dmp) {
+  hipStream_t s = h->stream;
+  const FrontDesc& F = h->h_fronts[fi];
+  const int ld = h->f_ld[fi];
+  double* A = h->pool + h->f_off[fi];
+  // `split`: the assembled contributions go to a buffer of their own (aoff) and reach the working matrix A (which starts
+  // from zero and collects the trailing updates) in 256-row chunks, each just before its panel is factored.
+  //   multi-rank   : the chunks are summed over the ranks (RCCL on the communication stream / the in-process group)
+  // (gathering the chunks on a second stream beside the factorisation was measured in round 1 -- 13.5 vs 10.4 ms per step: two
+  //  resident workgroups of the update kernel hold every VGPR of a SIMD, the gather waves only get in between -- and removed)
+  const int mode = dense_mode_of(h, fi);
+  const bool split = mode != DENSE_SINGLE;
+  const int64_t aoff = split ? h->s_off[fi] : h->f_off[fi];
+  double* Asm = h->pool + aoff;
+
+  const int kt = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
+  assemble_hbm_front(h, fi, aoff, dmp);
+  h->kt.end(kt, s);
+  if (mode == DENSE_SPLIT_EVENTS) {  // RCCL: all chunks queued on the communication stream, one event each
+    HIPCHECK(hipEventRecord(h->asm_ev, s));
+    HIPCHECK(hipStreamWaitEvent(h->comm_stream, h->asm_ev, 0));
+    for (int c = 0; c < (F.n + NBO - 1) / NBO; c++) {
+      size_t cb, cn;
+      chunk_range(F.n, ld, c, cb, cn);
+      NCCLCHECK(ncclAllReduce(Asm + cb, Asm + cb, cn, ncclDouble, ncclSum, h->comm_data ? h->comm_data : h->comm, h->comm_stream));
+      HIPCHECK(hipEventRecord(h->chunk_ev[c], h->comm_stream));
+    }
+  }
+
+  const lmgpu_handle::DensePlan& plan = h->dense_plans[fi];
+  h->inv16_owner = fi;  // the per-panel 16x16 inverses now belong to this front (read again by its back-substitution)
+  const DenseExec X{s, A, split ? (const double*)Asm : nullptr, ld, F.n, F.nf, F.id, h->d_status, h->inv16, 4096, h->d_pflags, h->pflags_prefilled,
+                    h->d_chain_tasks, plan.task_begin.data(), plan.task_count.data(), &h->kt, h->sw.chain_forms, h->sw.tail_scalar};
+  return run_dense_steps(X, plan.steps, [&](int kind, int c) { return kind == DENSE_ADD_CHUNK ? add_chunk(h, A, Asm, F.n, ld, c) : wait_chunk(h, Asm, F.n, ld, c); },
+                         &h->err);
+}
+
+// The elimination as a list of launches: the clears, then level by level the LDS fronts (merged segment, fused level or bins), the medium
+// fronts and the dense fronts.
 int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  // lambda by value (eager) or in device memory (graph replay)
   hipStream_t s = h->stream;
+  const Damping dmp{lambda_v, lambda_p, h->dampw, h->gex_active};
   const bool merge_el = h->merge_elim && !h->elim_segs.empty();
-  {  // the clears: the HBM fronts (hbm_clear_regime), the status words and the counters of the merged and fused launches
-    const int kt0 = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
-    int64_t lo, hi;
-    const int regime = hbm_clear_regime(h, &lo, &hi);
-    if (regime == HBM_CLEAR_RANGES && h->n_zero_ranges > 0)
-      hipLaunchKernelGGL(zero_ranges_kernel, dim3(16, h->n_zero_ranges), dim3(256), 0, s, (const ZeroRange*)h->d_zero_ranges, h->pool);
-    if (regime == HBM_CLEAR_EACH)
-      for (const LevelWork& L : h->levels)
-        for (int fi : L.hbm) {
-          // gather_writes: the upper triangle of the buffer the front is assembled into is written by the gather and a list of
-          // uncovered blocks -- the front itself on one rank, the partial-assembly buffer with several
-          const bool gw = gather_writes(h, fi);
-          const size_t bytes = (size_t)h->h_fronts[fi].n * h->f_ld[fi] * sizeof(double);
-          if (!gw || h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->f_off[fi], 0, bytes, s));
-          if (!gw && h->s_off[fi] >= 0) HIPCHECK(hipMemsetAsync(h->pool + h->s_off[fi], 0, bytes, s));
-        }
-    hipLaunchKernelGGL(fill_chunks_kernel, dim3(h->n_fill_elim), dim3(256), 0, s, (const FillChunk*)h->d_fill_elim);
-    h->kt.end(kt0, s);
-  }
+  int rc = eliminate_clears(h);
+  if (rc) return rc;
   // (Running a level's LDS fronts on a second stream beside its dense fronts -- they only depend on the levels below -- was measured
   //  with the replayed graph: 4.9 vs 2.5 ms per LM iteration on sphere2500; every cross-stream edge of the graph costs more than the
   //  45 us of LDS-front latency it hides.  Not kept.)
@@ -900,266 +1074,27 @@ int do_eliminate(lmgpu_handle* h, double lambda_v, const double* lambda_p) {  //
     hipLaunchKernelGGL(fill_upper_kernel, dim3(h->n_fill_upper), dim3(256), 0, s, (const FillUpper*)h->d_fill_upper, h->pool);
   for (size_t li = 0; li < h->levels.size(); li++) {
     const LevelWork& L = h->levels[li];
-    const int seg = merge_el ? h->elim_seg_of[li] : -1;
-    if (seg >= 0) {
-      const lmgpu_handle::ElimSeg& E = h->elim_segs[seg];
-      const int b0 = h->levels[E.lvl_lo].list_begin, e0 = h->levels[E.lvl_hi].list_begin + h->levels[E.lvl_hi].list_count;
-      const size_t lds = lds_front_bytes(E.jcap, E.nmax, E.nmax);
-      const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
-      unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + E.lvl_hi;
-      auto* kernel = E.threads == 1024 ? lds_front_merged_kernel<1024> : lds_front_merged_kernel<256>;
-      hipLaunchKernelGGL(kernel, dim3(e0 - b0), dim3(E.threads), lds, s, (const int32_t*)h->d_lists, b0, e0, (const FrontDesc*)h->d_fronts,
-                         (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                         (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, E.nmax, E.jcap,
-                         (const double*)h->gex_active, ticket, (int*)nullptr);  // (no relay: the status word is read back with the solve's scalars)
-      h->kt.end(kt, s);
-    }
+    const int seg = merge_el ? h->elim_seg_of[li] : -1;  // >= 0: a merged segment starts here; -2: the level lies inside one
     const bool fused = h->fuse_levels && L.fuse_task_count > 0;
-    if (fused) {  // the level's LDS fronts and medium fronts in one grid
-      const MedLevel ML{(const MedFront*)(h->d_med_fronts + L.med_begin)};
-      const size_t lds = std::max<size_t>(lds_front_bytes(L.fuse_jcap, L.fuse_nmax, L.fuse_nmax), (size_t)DIAG_LDS_BYTES);
-      unsigned int* ticket = h->d_bs_done + h->h_fronts.size() + li;
-      const int kt = h->kt.begin(LMGPU_KT_PANEL, s);
-      const bool wide = L.fuse_threads == 1024;
-      auto* kernel = wide ? level_fused_kernel<1024> : level_fused_kernel<256>;
-      hipLaunchKernelGGL(kernel, dim3(L.fuse_task_count), dim3(wide ? 1024 : 256), lds, s, (const LevelTask*)(h->d_level_tasks + L.fuse_task_begin), ticket,
-                         (const int32_t*)h->d_lists, (const FrontDesc*)h->d_fronts, (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd,
-                         (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap, (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p,
-                         (const double*)h->dampw, h->d_status, L.fuse_nmax, L.fuse_jcap, (const double*)h->gex_active, ML, (const int32_t*)h->d_rowptr,
-                         (const RowSrc*)h->d_rowsrc, h->inv16_med, h->d_level_sync + L.med_begin);
-      h->kt.end(kt, s);
-    }
-    for (int b = 0; b < kNumBins && seg == -1 && !fused; b++) {
-      const int cnt = L.bin_begin[b + 1] - L.bin_begin[b];
-      if (cnt == 0) continue;
-      const int nmax = kBinN[b % 6], srows = L.bin_srows[b];
-      // gather leaves keep only nf rows: one wave per front (barriers become free, ~2.5x more fronts resident per CU)
-      const int threads = (b >= 6 || b % 6 == 0) ? 64 : (b % 6 == 1 ? 128 : 256);
-      const int jcap = L.bin_jcap[b];
-      const size_t lds = lds_front_bytes(jcap, srows, nmax);
+    const MedLevel ML{(const MedFront*)(h->d_med_fronts + L.med_begin)};
+    if (seg >= 0) {  // the LDS fronts of the segment's levels as one launch (no relay: the status word is read back with the solve's scalars)
+      const lmgpu_handle::ElimSeg& E = h->elim_segs[seg];
       const int kt = h->kt.begin(LMGPU_KT_LDS_FRONT, s);
-      if (L.bin_group[b]) {  // every leaf of the bin qualifies (leaf_group_form): four leaves per wave, one lane per factor
-        auto* gk = L.bin_group[b] == 1 ? lds_front_group_kernel<2, LEAFGRP_MAXSEP, 3> : lds_front_group_kernel<LEAFGRP_MAXROWS, LEAFGRP_MAXSEP, LEAFGRP_MAXNF>;
-        // LDS per leaf: the staged Jacobians and [R S d]; the second over the first where no lane takes a second factor (kernels_leaf.hpp)
-        const int out_off = L.bin_group_maxfac[b] > LEAFGRP_LANES ? jcap : 0;
-        const int lds_leaf = (std::max(jcap, out_off + L.bin_group_out[b]) + 1) & ~1;
-        int gthreads = h->leaf_group_threads;  // (halved until the workgroup's leaves fit 64 KB of LDS)
-        while (gthreads > 64 && (size_t)(gthreads / LEAFGRP_LANES) * lds_leaf * sizeof(double) > 65536) gthreads >>= 1;
-        const int lpw = gthreads / LEAFGRP_LANES;  // leaves per workgroup
-        hipLaunchKernelGGL(gk, dim3((cnt + lpw - 1) / lpw), dim3(gthreads), (size_t)lpw * lds_leaf * sizeof(double), s,
-                           (const char*)(h->d_leafpack + L.pack_off[b]), L.pack_stride[b], cnt, h->pool, lambda_v,
-                           lambda_p, (const double*)h->dampw, h->d_status, h->d_gcorner, (const double*)h->gex_active, lds_leaf, out_off);
-        h->kt.end(kt, s);
-        continue;
-      }
-      // a handful of wide fronts (the upper levels of a general sparse tree, where a launch lasts as long as its slowest front and the
-      // device is idle): sixteen waves per front -- the rank-4 trailing updates, the extend-add and the emission all scale with them
-      const bool wide16 = b >= 3 && b < 6 && cnt <= h->wide16_max && !h->no_wide16;
-      auto* kernel = lds_front_kernel<false, 1024>;
-      if (!wide16) kernel = b < 6 ? lds_front_kernel<false> : lds_front_kernel<true>;
-      hipLaunchKernelGGL(kernel, dim3(cnt), dim3(wide16 ? 1024 : threads), lds, s,
-                         (const int32_t*)(h->d_lists + L.list_begin + L.bin_begin[b]), (const FrontDesc*)h->d_fronts,
-                         (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                         (const int32_t*)h->d_fxoff, h->pool, lambda_v, lambda_p, (const double*)h->dampw, h->d_status, nmax, srows, h->d_gcorner, jcap,
-                         (const double*)h->gex_active, (const char*)(h->d_leafpack && L.pack_stride[b] ? h->d_leafpack + L.pack_off[b] : nullptr),
-                         L.pack_stride[b]);
+      launch_lds_fronts_merged(s, h->tabs, h->pool, h->d_status, dmp, h->levels[E.lvl_lo].list_begin,
+                               h->levels[E.lvl_hi].list_begin + h->levels[E.lvl_hi].list_count, E.threads, E.nmax, E.jcap,
+                               h->d_bs_done + h->h_fronts.size() + E.lvl_hi, nullptr);
       h->kt.end(kt, s);
     }
-    if (L.med_count > 0 && !fused) {  // medium fronts of this level: six launches for all of them
-      const MedLevel ML{(const MedFront*)(h->d_med_fronts + L.med_begin)};
-      const unsigned cnt = (unsigned)L.med_count;
-      int ktm = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
-      if (L.med_max_fac > 0 || L.med_max_child > 0)
-        hipLaunchKernelGGL(med_assemble_rows_kernel, dim3((L.med_max_n + 3) / 4, cnt), dim3(256), 0, s, ML, (const int32_t*)h->d_rowptr, (const RowSrc*)h->d_rowsrc, (const ChildRef*)h->d_childs, (const int32_t*)h->d_cmap,
-                           (const FrontFac*)h->d_ffac, (const FacDesc*)h->d_fd, h->pool, (const int32_t*)h->d_fxoff, lambda_v, lambda_p,
-                           (const double*)h->dampw, (const double*)h->gex_active);
-      else  // (the row-owner assembly damps its own rows)
-        hipLaunchKernelGGL(med_damp_kernel, dim3((L.med_max_nf + 255) / 256, cnt), dim3(256), 0, s, ML, (const int32_t*)h->d_fxoff, h->pool, lambda_v,
-                           lambda_p, (const double*)h->dampw, (const double*)h->gex_active);
-      h->kt.end(ktm, s);
-      ktm = h->kt.begin(LMGPU_KT_PANEL, s);
-      hipLaunchKernelGGL(med_diag_potrf_kernel, dim3(cnt), dim3(256), DIAG_LDS_BYTES, s, ML, h->pool, h->d_status, h->inv16_med);
-      if (L.med_max_cols > 0)
-        hipLaunchKernelGGL(med_panel_trsm_kernel, dim3((L.med_max_cols + 63) / 64, cnt), dim3(256), 0, s, ML, h->pool, (const double*)h->inv16_med);
-      h->kt.end(ktm, s);
-      if (L.med_max_cols > 0) {
-        const int S = (L.med_max_cols + 63) / 64;
-        ktm = h->kt.begin(LMGPU_KT_SYRK, s);
-        hipLaunchKernelGGL(med_syrk_kernel, dim3(4 * S, S, cnt), dim3(256), 0, s, ML, h->pool);
-        h->kt.end(ktm, s);
-      }
-    }
-    for (int fi : L.hbm) {
-      if (h->is_med[fi]) continue;
-      const FrontDesc& F = h->h_fronts[fi];
-      const int64_t off = h->f_off[fi];
-      const int ld = h->f_ld[fi];
-      double* A = h->pool + off;
-      const bool own_terms = (F.pad & 2) == 0;
-      const lmgpu_handle::GatherRange& G = h->gather[fi];
-      const int nchunks = (F.n + NBO - 1) / NBO;
-      // `split`: the assembled contributions go to a buffer of their own (aoff) and reach the working matrix A (which starts
-      // from zero and collects the trailing updates) in 256-row chunks, each just before its panel is factored.
-      //   multi-rank   : the chunks are summed over the ranks (RCCL on the communication stream / the in-process group)
-      // (gathering the chunks on a second stream beside the factorisation was measured in round 1 -- 13.5 vs 10.4 ms per step: two
-      //  resident workgroups of the update kernel hold every VGPR of a SIMD, the gather waves only get in between -- and removed)
-      const int mode = dense_mode_of(h, fi);
-      const bool split = mode != DENSE_SINGLE;
-      const int64_t aoff = split ? h->s_off[fi] : off;
-      double* Asm = h->pool + aoff;
-
-      // ---- assembly
-      const int kt = h->kt.begin(LMGPU_KT_HBM_ASSEMBLE, s);
-      const bool gwrite = gather_writes(h, fi);
-      if (gwrite && G.zero_count > 0)
-        hipLaunchKernelGGL(zero_blocks_kernel, dim3(G.zero_count), dim3(128), 0, s, (const GZeroBlock*)(h->d_gzero + G.zero_begin), h->pool, aoff, ld);
-      // (the damping rides in the row assembly where there is one; a front without sources here keeps hbm_damp_kernel)
-      const bool damp_here = !gwrite && own_terms;
-      if (!launch_assemble_rows(h, fi, aoff, own_terms && !gwrite, damp_here, lambda_v, lambda_p) && damp_here) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
-      // leaf children in Schur form: deterministic gather instead of atomics
-      const int schur_masked = dev_switch("LMGPU_SCHUR_UNMASKED") ? 0 : 2;  // (operand loads that only the lanes holding an element take part in)
-      // (LMGPU_SCHUR_UNMASKED reaches schur_pairs_kernel and the split form's schur_factor_kernel; schur_var_kernel has the masked loads only)
-      if (G.pblk_short > 0)
-        hipLaunchKernelGGL((schur_pairs_kernel<1>), dim3((G.pblk_short + 7) & ~7), dim3(64), 0, s, (const GPairBlock*)(h->d_gpblk + G.pblk_begin),
-                           (const GPairEntry*)h->d_gpent, h->pool, aoff, ld, G.pblk_short, (gwrite ? 1 : 0) | schur_masked);
-      if (G.pblk_long > 0)
-        hipLaunchKernelGGL((schur_pairs_kernel<4>), dim3((G.pblk_long + 7) & ~7), dim3(256), 0, s,
-                           (const GPairBlock*)(h->d_gpblk + G.pblk_begin + G.pblk_short), (const GPairEntry*)h->d_gpent, h->pool, aoff, ld,
-                           G.pblk_long, (gwrite ? 1 : 0) | schur_masked);
-#ifdef LMGPU_TEST_HOOKS
-      if (h->schur_split_diag) {
-        if (G.vblk_count > 0)
-          hipLaunchKernelGGL(schur_factor_kernel, dim3(G.vblk_count), dim3(64 * SCHUR_FW), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
-                             (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, schur_masked);
-        if (G.leaf_count > 0) {  // the (rhs, rhs) corner
-          double* scal = h->dscal + 4;
-          reduce_to(h, h->d_gcorner + G.leaf_begin, G.leaf_count, scal, s, nullptr);
-          hipLaunchKernelGGL(add_scalar_kernel, dim3(1), dim3(1), 0, s, Asm + (size_t)(F.n - 1) * ld + F.n - 1, (const double*)scal);
-        }
-      } else
-#endif
-      {
-        // one workgroup per separator variable writes (adds) its (v, v) and (v, rhs); the last launch carries one more workgroup,
-        // which sums the leaves' (rhs, rhs) scalars into the corner
-        const int vlong = G.vblk_count - G.vblk_short;
-        const int corner_short = (G.leaf_count > 0 && vlong == 0) ? 1 : 0, corner_long = (G.leaf_count > 0 && vlong > 0) ? 1 : 0;
-        if (G.vblk_short + corner_short > 0)
-          hipLaunchKernelGGL((schur_var_kernel<1>), dim3(G.vblk_short + corner_short), dim3(64), 0, s, (const GVarBlock*)(h->d_gvblk + G.vblk_begin),
-                             (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, G.vblk_short, gwrite ? 1 : 0,
-                             (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
-        if (vlong + corner_long > 0)
-          hipLaunchKernelGGL((schur_var_kernel<SCHUR_VAR_WAVES>), dim3(vlong + corner_long), dim3(64 * SCHUR_VAR_WAVES), 0, s,
-                             (const GVarBlock*)(h->d_gvblk + G.vblk_begin + G.vblk_short), (const GVarEntry*)h->d_gvent, h->pool, aoff, ld, F.n, vlong,
-                             gwrite ? 1 : 0, (const double*)(h->d_gcorner + G.leaf_begin), G.leaf_count);
-      }
-      if (gwrite && own_terms) {  // the front's own factors and the damping are added: after the gather has initialised the entries
-        // (a gather-write front has no update-matrix children: only its factors are added here, the damping behind them in the same launch)
-        if (!(F.fac_count > 0 && launch_assemble_rows(h, fi, aoff, true, true, lambda_v, lambda_p))) launch_hbm_damp(h, fi, aoff, lambda_v, lambda_p);
-      }
+    if (fused) {  // the level's LDS fronts and medium fronts in one grid
+      const int kt = h->kt.begin(LMGPU_KT_PANEL, s);
+      launch_level_fused(s, h->tabs, h->pool, h->d_status, dmp, h->d_level_tasks + L.fuse_task_begin, L.fuse_task_count,
+                         h->d_bs_done + h->h_fronts.size() + li, L.fuse_threads, L.fuse_nmax, L.fuse_jcap, ML, h->inv16_med, h->d_level_sync + L.med_begin);
       h->kt.end(kt, s);
-      if (mode == DENSE_SPLIT_EVENTS) {  // RCCL: all chunks queued on the communication stream, one event each
-        HIPCHECK(hipEventRecord(h->asm_ev, s));
-        HIPCHECK(hipStreamWaitEvent(h->comm_stream, h->asm_ev, 0));
-        for (int c = 0; c < nchunks; c++) {
-          size_t cb, cn;
-          chunk_range(F.n, ld, c, cb, cn);
-          NCCLCHECK(ncclAllReduce(Asm + cb, Asm + cb, cn, ncclDouble, ncclSum, h->comm_data ? h->comm_data : h->comm, h->comm_stream));
-          HIPCHECK(hipEventRecord(h->chunk_ev[c], h->comm_stream));
-        }
-      }
-
-      // ---- factorisation: the front's schedule (dense_schedule.hpp, built by ensure_dense_schedules), record by record
-      const lmgpu_handle::DensePlan& plan = h->dense_plans[fi];
-      h->inv16_owner = fi;  // the per-panel 16x16 inverses now belong to this front (read again by its back-substitution)
-      int kt_run = -1, run_launches = 0;  // one event pair around a run of consecutive fused-step launches
-      double run_flop = 0;
-      for (size_t r = 0; r < plan.steps.size(); r++) {
-        const DenseStep& st = plan.steps[r];
-        // panel i = rows [k0, r0), m columns behind it (panel records only)
-        const int i = st.i, k0 = i * NBO, kb = std::min(F.nf, k0 + NBO) - k0, r0 = k0 + kb, m = F.n - r0;
-        // the wait of a fused step that folds its chunk in itself stays inside the run; everything else is timed on its own
-        const bool in_run = st.kind == DENSE_STEP_FUSED || (st.kind == DENSE_WAIT_CHUNK && plan.steps[r + 1].kind == DENSE_STEP_FUSED);
-        if (!in_run && run_launches > 0) {
-          h->kt.end(kt_run, s, run_flop, run_launches);
-          run_launches = 0;
-          run_flop = 0;
-        }
-        switch (st.kind) {
-          case DENSE_PANEL_DATAFLOW:
-          case DENSE_PANEL_TWO_LAUNCH: {
-            if (i == 0 && !h->pflags_prefilled) HIPCHECK(hipMemsetAsync(h->d_pflags, 0, (size_t)((F.nf + NBO - 1) / NBO + 1) * PDF_FLAG_WORDS * sizeof(unsigned int), s));
-            double* inv16 = h->inv16 + (size_t)i * 4096;
-            const int ktp = h->kt.begin(LMGPU_KT_PANEL, s);
-            if (st.kind == DENSE_PANEL_DATAFLOW) {
-              hipLaunchKernelGGL(panel_dataflow_kernel, dim3(kb / 64 + (m + 63) / 64), dim3(256), PDF_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id,
-                                 h->d_status, inv16, h->d_pflags + (size_t)i * PDF_FLAG_WORDS);
-            } else {
-              hipLaunchKernelGGL(diag_potrf_kernel, dim3(1), dim3(256), DIAG_LDS_BYTES, s, A, ld, F.nf, k0, kb, F.id, h->d_status, inv16);
-              if (m > 0) hipLaunchKernelGGL(panel_trsm_kernel, dim3((m + 63) / 64), dim3(256), 0, s, A, ld, F.n, k0, kb, (const double*)inv16);
-            }
-            h->kt.end(ktp, s, st.flop);
-            break;
-          }
-          case DENSE_CHAIN: {  // (a split front: behind the wait for the last row chunk the launch folds in)
-            ChainArgs ca{A, ld, F.n, F.nf, i, st.nsteps, F.id, h->d_status, h->inv16, h->d_pflags, h->d_chain_tasks + plan.task_begin[r],
-                         split ? (const double*)Asm : nullptr};
-#ifdef LMGPU_TEST_HOOKS
-            ca.dev_forms = h->chain_forms;
-#endif
-            const int ktc = h->kt.begin(LMGPU_KT_CHAIN, s);
-            hipLaunchKernelGGL(chain_kernel, dim3(plan.task_count[r]), dim3(256), STEP_LDS_BYTES, s, ca);
-            h->kt.end(ktc, s, st.flop, 1);
-            break;
-          }
-          case DENSE_STEP_FUSED: {  // (a split front: behind the wait for the chunk of panel i + 1, which its head tiles fold in)
-            const int kbn = std::min(F.nf, r0 + NBO) - r0;
-            StepArgs a{A, ld, F.n, F.nf, k0, kb, kbn, F.id, h->d_status, h->inv16 + (size_t)(i + 1) * 4096, h->d_pflags + (size_t)(i + 1) * PDF_FLAG_WORDS,
-                       split ? (const double*)Asm : nullptr};
-#ifdef LMGPU_TEST_HOOKS
-            a.dev_forms = h->chain_forms;
-#endif
-            if (run_launches == 0) kt_run = h->kt.begin(LMGPU_KT_SYRK, s);
-            hipLaunchKernelGGL(step_kernel, dim3(step_grid(m, kbn)), dim3(256), STEP_LDS_BYTES, s, a);
-            run_launches++;
-            run_flop += st.flop;
-            break;
-          }
-          case DENSE_UPDATE_QUADRANTS:
-          case DENSE_UPDATE_MFMA: {
-            const int kts = h->kt.begin(LMGPU_KT_SYRK, s);
-            if (st.kind == DENSE_UPDATE_QUADRANTS) {
-              const int S = (m + 63) / 64;
-              hipLaunchKernelGGL(syrk_quadrants_kernel, dim3(4 * S, S), dim3(256), 0, s, A, ld, F.n, k0, kb, r0);
-            } else {
-              const int T = (m + 127) / 128;
-              hipLaunchKernelGGL(syrk_mfma_kernel, dim3(T, T), dim3(256), kSyrkLds, s, A, ld, F.n, k0, kb, r0, F.n);
-            }
-            h->kt.end(kts, s, st.flop);
-            break;
-          }
-          case DENSE_TAIL: {
-            const int ktt = h->kt.begin(LMGPU_KT_PANEL, s);
-#ifdef LMGPU_TEST_HOOKS
-            if (h->tail_scalar)
-              hipLaunchKernelGGL(front_tail_scalar_kernel, dim3(1), dim3(256), TAIL_LDS_BYTES, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
-                                 h->inv16 + (size_t)(i + 1) * 4096);
-            else
-#endif
-            hipLaunchKernelGGL(front_tail_kernel, dim3(1), dim3(256), 0, s, A, ld, F.n, F.nf, k0, kb, F.id, h->d_status,
-                               h->inv16 + (size_t)(i + 1) * 4096);
-            h->kt.end(ktt, s, st.flop);
-            break;
-          }
-          case DENSE_ADD_CHUNK:
-          case DENSE_WAIT_CHUNK: {
-            const int rcc = st.kind == DENSE_ADD_CHUNK ? add_chunk(h, A, Asm, F.n, ld, st.chunk) : wait_chunk(h, Asm, F.n, ld, st.chunk);
-            if (rcc) return rcc;
-            break;
-          }
-        }
-      }
-      if (run_launches > 0) h->kt.end(kt_run, s, run_flop, run_launches);
     }
+    if (seg == -1 && !fused) eliminate_level_bins(h, L, dmp);
+    if (L.med_count > 0 && !fused) launch_med_level(s, h->tabs, h->pool, h->d_status, dmp, h->kt, L, ML, h->inv16_med);
+    for (int fi : L.hbm)
+      if (!h->is_med[fi] && (rc = eliminate_hbm_front(h, fi, dmp))) return rc;
   }
   HIPCHECK(hipGetLastError());
   return LMGPU_OK;
@@ -1212,16 +1147,88 @@ static bool level_lds_class(const lmgpu_handle* h, int l, int* nmax, int* jcap, 
     }
   *nmax = kBinN[top];
   *jcap = jc;
-  const bool wide16 = top >= 3 && cnt_top <= h->wide16_max && !h->no_wide16;
+  const bool wide16 = top >= 3 && cnt_top <= h->sw.wide16_max && !h->sw.no_wide16;
   *threads = wide16 ? 1024 : (top == 0 ? 64 : 256);  // (four waves from 25 columns on: the blocked Cholesky of the LDS body needs them)
+  // (ISAM2 sizes its merged launch by a rule of its own: is_launch_merged, isam2.hpp)
   return true;
 }
 
 // Which kernel the plain per-level back-substitution launch of level L takes.  0: lds_backsub_kernel / lds_backsub_wide_kernel; 1:
 // lds_backsub_group_kernel<3, 6> (every front nf <= 3, separators of at most 96 columns); 2: lds_backsub_group_kernel<LDSBG_MAXNF, 9>.
 static int backsub_group_form(const lmgpu_handle* h, const LevelWork& L) {
-  if (L.list_count == 0 || L.lds_nf_max > LDSBG_MAXNF || h->no_backsub_groups) return 0;
+  if (L.list_count == 0 || L.lds_nf_max > LDSBG_MAXNF || h->sw.no_backsub_groups) return 0;
   return (L.lds_nf_max <= 3 && L.lds_ns_max <= 6 * LEAFGRP_LANES) ? 1 : 2;
+}
+
+// ---- back-substitution, top-down (a14)
+// the LDS fronts of one level as a launch of their own
+static void backsub_lds_level(lmgpu_handle* h, const LevelWork& L) {
+  const int group = backsub_group_form(h, L);
+  const LdsBacksubForm form = L.lds_nf_max > LDSB_SMALL_NF ? LDS_BACKSUB_WIDE
+                              : group == 1                 ? LDS_BACKSUB_GROUP_SMALL
+                              : group == 2                 ? LDS_BACKSUB_GROUP
+                                                           : LDS_BACKSUB_PLAIN;
+  launch_lds_backsub(h->stream, h->tabs, h->pool, h->delta, h->d_status, form, L.list_begin, L.list_count, L.lds_rsd_max);
+}
+
+// the LDS fronts of levels lo .. hi (bottom, top) of the merged back-substitution: one level as its own launch, several as ONE dataflow launch
+static void backsub_lds_segment(lmgpu_handle* h, int lo, int hi) {
+  hipStream_t s = h->stream;
+  const int kt = h->kt.begin(LMGPU_KT_BACKSUB_LDS, s);
+  if (hi == lo) {
+    backsub_lds_level(h, h->levels[hi]);
+  } else {
+    const int b = h->levels[lo].list_begin, e = h->levels[hi].list_begin + h->levels[hi].list_count;
+    int rsdmax = 0;
+    for (int l = lo; l <= hi; l++) rsdmax = std::max(rsdmax, h->levels[l].lds_rsd_max);
+    const BacksubMergeDev M{h->d_bs_parent, h->d_bs_pos, h->d_bs_done, h->d_bs_done + (int)h->h_fronts.size() + hi};
+    launch_lds_backsub(s, h->tabs, h->pool, h->delta, h->d_status, LDS_BACKSUB_MERGED, b, e - b, rsdmax, &M);
+  }
+  h->kt.end(kt, s);
+}
+
+// HBM front fi of more than BSS_MAX_NF rows: y = d - S x_S, then ONE dataflow launch over its row blocks
+static int backsolve_hbm_front(lmgpu_handle* h, int fi) {
+  hipStream_t s = h->stream;
+  const FrontDesc& F = h->h_fronts[fi];
+  const int64_t off = h->f_off[fi];
+  const int ld = h->f_ld[fi];
+  const int kt = h->kt.begin(LMGPU_KT_BACKSUB_HBM, s);
+  const bool has_sep = F.n - F.nf - 1 > 0;
+  if (has_sep)  // y = d - S x_S (a root reads d in place)
+    hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
+                       (const double*)h->delta, h->ywork);
+  // ONE dataflow launch: workgroup b waits for x_j (j > b); the inverses of the diagonal blocks are built inside it when the 16 x 16
+  // inverses of this front's factorisation are still there (else by a launch of their own in front of it).  128-row blocks with
+  // explicit inverses then (hbm_backsolve_wide_kernel); 64-row blocks in the fallback and, test library only, under LMGPU_BACKSOLVE_HOP64
+  const bool reuse = h->inv16_owner == fi && !h->sw.no_inv16_reuse;
+  const bool wide = reuse && !h->sw.backsolve_hop64;
+  const int bw = wide ? BSW_NB : NB, nblk = (F.nf + bw - 1) / bw;
+  if (!h->bs_prefilled) {  // (else cleared by the fill launch at the head of the elimination: ensure_fill_tables)
+    HIPCHECK(hipMemsetAsync(h->bs_flags, 0, (nblk + 1) * sizeof(unsigned int), s));  // flags + ticket
+    HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * bw * sizeof(double), s));  // sentinel: "not published yet"
+  }
+  if (wide) {
+    hipLaunchKernelGGL((hbm_backsolve_wide_kernel<false>), dim3(nblk), dim3(512), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
+                       (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
+                       h->d_status, h->bs_inv, (unsigned long long*)nullptr);
+#ifdef LMGPU_TEST_HOOKS
+  } else if (reuse) {
+    hipLaunchKernelGGL((hbm_backsolve_dataflow2_kernel<false>), dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
+                       (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
+                       h->d_status, (unsigned long long*)nullptr);
+#endif
+  } else {
+    if (!has_sep)
+      hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
+                         (const double*)h->delta, h->ywork);
+    hipLaunchKernelGGL((hbm_invert_diag_kernel<NB>), dim3(nblk), dim3(NB), 0, s, (const double*)(h->pool + off), ld, F.nf, h->bs_inv);
+    hipLaunchKernelGGL((hbm_backsolve_dataflow_kernel<NB>), dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff,
+                       (const double*)h->pool, (const double*)h->bs_inv, (const double*)h->ywork, h->bs_x, h->bs_flags, h->delta,
+                       h->d_status);
+  }
+  h->kt.end(kt, s);
+  return LMGPU_OK;
 }
 
 // ---- back-substitution, top-down (a14)
@@ -1229,117 +1236,42 @@ int do_backsub(lmgpu_handle* h) {
   hipStream_t s = h->stream;
   if (h->cfg.world_size > 1) HIPCHECK(hipMemsetAsync(h->delta, 0, h->ntot * sizeof(double), s));
   const bool merge = backsub_merged(h);
-  const bool no_bsd_runs = dev_switch("LMGPU_NO_BSD_RUNS") != nullptr;
-  const int NFR = (int)h->h_fronts.size();
   if (h->n_fill_backsub > 0) hipLaunchKernelGGL(fill_chunks_kernel, dim3(h->n_fill_backsub), dim3(256), 0, s, (const FillChunk*)h->d_fill_backsub);
   int seg_hi = -1, seg_lo = -1;  // levels of the pending segment (top, bottom)
-  auto run_level = [&](const LevelWork& L) {  // one level as a launch of its own
-    if (L.lds_nf_max > LDSB_SMALL_NF) {
-      hipLaunchKernelGGL(lds_backsub_wide_kernel, dim3(L.list_count), dim3(256), (size_t)(L.lds_rsd_max + LDSB_TAIL) * sizeof(double), s,
-                         (const int32_t*)(h->d_lists + L.list_begin), L.list_count, (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff,
-                         (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta, h->d_status);
-    } else if (const int form = backsub_group_form(h, L)) {  // every front of the launch: four fronts per wave, 16 lanes each
-      auto* gk = form == 1 ? lds_backsub_group_kernel<3, 6> : lds_backsub_group_kernel<LDSBG_MAXNF, 9>;
-      hipLaunchKernelGGL(gk, dim3((L.list_count + 15) / 16), dim3(256), 0, s, (const int32_t*)(h->d_lists + L.list_begin), L.list_count,
-                         (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta,
-                         h->d_status);
-    } else {
-      hipLaunchKernelGGL(lds_backsub_kernel, dim3((L.list_count + 3) / 4), dim3(256), 0, s, (const int32_t*)(h->d_lists + L.list_begin),
-                         L.list_count, (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff,
-                         (const double*)h->pool, h->delta, h->d_status);
-    }
-  };
-  auto flush_segment = [&]() -> int {
-    if (seg_hi < 0) return LMGPU_OK;
-    const int kt = h->kt.begin(LMGPU_KT_BACKSUB_LDS, s);
-    if (seg_hi == seg_lo) {
-      run_level(h->levels[seg_hi]);
-    } else {
-      const int b = h->levels[seg_lo].list_begin, e = h->levels[seg_hi].list_begin + h->levels[seg_hi].list_count;
-      int rsdmax = 0;
-      for (int l = seg_lo; l <= seg_hi; l++) rsdmax = std::max(rsdmax, h->levels[l].lds_rsd_max);
-      hipLaunchKernelGGL(lds_backsub_merged_kernel, dim3(e - b), dim3(256), (size_t)(rsdmax + LDSB_TAIL) * sizeof(double), s, (const int32_t*)h->d_lists, b, e,
-                         (const FrontDesc*)h->d_fronts, (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta,
-                         h->d_status, (const int32_t*)h->d_bs_parent, (const int32_t*)h->d_bs_pos, h->d_bs_done, h->d_bs_done + NFR + seg_hi);
-    }
-    h->kt.end(kt, s);
+  auto flush_segment = [&] {
+    if (seg_hi >= 0) backsub_lds_segment(h, seg_lo, seg_hi);
     seg_hi = seg_lo = -1;
-    return LMGPU_OK;
   };
   for (int li = (int)h->levels.size() - 1; li >= 0; li--) {
     const LevelWork& L = h->levels[li];
-    if (merge && !L.hbm.empty()) {  // this level's HBM fronts need every ancestor: finish the pending LDS levels first
-      const int rcf = flush_segment();
-      if (rcf) return rcf;
-    }
-    const int brun = (merge && !h->bsd_run_of.empty() && !no_bsd_runs) ? h->bsd_run_of[li] : -1;
+    if (merge && !L.hbm.empty()) flush_segment();  // this level's HBM fronts need every ancestor: finish the pending LDS levels first
+    const int brun = (merge && !h->bsd_run_of.empty() && !h->sw.no_bsd_runs) ? h->bsd_run_of[li] : -1;
     if (brun >= 0) {  // this level and the ones below it that hold nothing but block-solved fronts: one launch, separator values awaited by value
       const lmgpu_handle::BsdRun& R = h->bsd_runs[brun];
       const int kt = h->kt.begin(LMGPU_KT_BACKSUB_HBM, s);
-      hipLaunchKernelGGL(hbm_backsolve_blocks_kernel, dim3(R.count), dim3(256), 0, s, (const BsdBlock*)(h->d_bsd_run_table + R.begin), h->d_bsd_ticket + li,
-                         (const int32_t*)h->d_fxoff, (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta, h->d_bsd_x, h->d_status, 1);
+      launch_backsolve_blocks(s, h->tabs, h->pool, h->delta, h->d_bsd_x, h->d_status, h->d_bsd_run_table + R.begin, R.count, h->d_bsd_ticket + li, 1);
       h->kt.end(kt, s);
     }
     if (L.bsd_count > 0 && brun == -1) {  // the smaller HBM fronts of the level: one workgroup per 64-row block, one launch
       const int kt = h->kt.begin(LMGPU_KT_BACKSUB_HBM, s);
-      hipLaunchKernelGGL(hbm_backsolve_blocks_kernel, dim3(L.bsd_count), dim3(256), 0, s, (const BsdBlock*)(h->d_bsd_table + L.bsd_begin),
-                         (L.bsd_count <= h->num_cus && !h->bsd_ticket) ? (unsigned int*)nullptr : h->d_bsd_ticket + li, (const int32_t*)h->d_fxoff,
-                         (const int32_t*)h->d_sxoff, (const double*)h->pool, h->delta, h->d_bsd_x, h->d_status);
+      launch_backsolve_blocks(s, h->tabs, h->pool, h->delta, h->d_bsd_x, h->d_status, h->d_bsd_table + L.bsd_begin, L.bsd_count,
+                              (L.bsd_count <= h->num_cus && !h->sw.bsd_ticket) ? nullptr : h->d_bsd_ticket + li, 0);
       h->kt.end(kt, s);
     }
-    for (int fi : L.hbm) {
-      const FrontDesc& F = h->h_fronts[fi];
-      if (F.nf <= BSS_MAX_NF) continue;  // done above
-      const int64_t off = h->f_off[fi];
-      const int ld = h->f_ld[fi];
-      const int kt = h->kt.begin(LMGPU_KT_BACKSUB_HBM, s);
-      const bool has_sep = F.n - F.nf - 1 > 0;
-      if (has_sep)  // y = d - S x_S (a root reads d in place)
-        hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
-                           (const double*)h->delta, h->ywork);
-      // ONE dataflow launch: workgroup b waits for x_j (j > b); the inverses of the diagonal blocks are built inside it when the 16 x 16
-      // inverses of this front's factorisation are still there (else by a launch of their own in front of it).  128-row blocks with
-      // explicit inverses then (hbm_backsolve_wide_kernel); 64-row blocks in the fallback and, test library only, under LMGPU_BACKSOLVE_HOP64
-      const bool reuse = h->inv16_owner == fi && !dev_switch("LMGPU_NO_INV16_REUSE");
-      const bool wide = reuse && !dev_switch("LMGPU_BACKSOLVE_HOP64");
-      const int bw = wide ? BSW_NB : NB, nblk = (F.nf + bw - 1) / bw;
-      if (!h->bs_prefilled) {  // (else cleared by the fill launch at the head of the elimination: ensure_fill_tables)
-        HIPCHECK(hipMemsetAsync(h->bs_flags, 0, (nblk + 1) * sizeof(unsigned int), s));  // flags + ticket
-        HIPCHECK(hipMemsetAsync(h->bs_x, 0xff, (size_t)nblk * bw * sizeof(double), s));  // sentinel: "not published yet"
+    for (int fi : L.hbm)
+      if (h->h_fronts[fi].nf > BSS_MAX_NF) {  // (the others: done above)
+        const int rc = backsolve_hbm_front(h, fi);
+        if (rc) return rc;
       }
-      if (wide) {
-        hipLaunchKernelGGL((hbm_backsolve_wide_kernel<false>), dim3(nblk), dim3(512), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
-                           (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
-                           h->d_status, h->bs_inv, (unsigned long long*)nullptr);
-#ifdef LMGPU_TEST_HOOKS
-      } else if (reuse) {
-        hipLaunchKernelGGL((hbm_backsolve_dataflow2_kernel<false>), dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff, (const double*)h->pool,
-                           (const double*)h->inv16, has_sep ? (const double*)h->ywork : (const double*)nullptr, h->bs_x, h->bs_flags, h->delta,
-                           h->d_status, (unsigned long long*)nullptr);
-#endif
-      } else {
-        if (!has_sep)
-          hipLaunchKernelGGL(hbm_rhs_init_kernel, dim3(F.nf), dim3(64), 0, s, F, off, ld, (const int32_t*)h->d_sxoff, (const double*)h->pool,
-                             (const double*)h->delta, h->ywork);
-        hipLaunchKernelGGL((hbm_invert_diag_kernel<NB>), dim3(nblk), dim3(NB), 0, s, (const double*)(h->pool + off), ld, F.nf, h->bs_inv);
-        hipLaunchKernelGGL((hbm_backsolve_dataflow_kernel<NB>), dim3(nblk), dim3(256), 0, s, F, off, ld, (const int32_t*)h->d_fxoff,
-                           (const double*)h->pool, (const double*)h->bs_inv, (const double*)h->ywork, h->bs_x, h->bs_flags, h->delta,
-                           h->d_status);
-      }
-      h->kt.end(kt, s);
-    }
     if (merge) {  // accumulated; flushed before the next HBM front or at the end
       if (L.list_count > 0) {
         if (seg_hi < 0) seg_hi = li;
         seg_lo = li;
       }
-      if (li == 0 || !h->levels[li - 1].hbm.empty()) {
-        const int rcf = flush_segment();
-        if (rcf) return rcf;
-      }
+      if (li == 0 || !h->levels[li - 1].hbm.empty()) flush_segment();
     } else if (L.list_count > 0) {
       const int kt = h->kt.begin(LMGPU_KT_BACKSUB_LDS, s);
-      run_level(L);
+      backsub_lds_level(h, L);
       h->kt.end(kt, s);
     }
   }
@@ -1446,7 +1378,7 @@ int pcg_solve_enqueue(lmgpu_handle* h, double lambda) {
   hipLaunchKernelGGL(pcg_start_kernel, dim3(1), dim3(256), 0, s, (const double*)part_rs, gv, pp.epsilon_rel, pp.epsilon_abs, pp.minIterations,
                      pp.maxIterations, h->pcg_gam, h->pcg_done, h->pcg_ctl);
   int waits = 0;
-  const bool fz = h->pcg_fused;
+  const bool fz = h->sw.pcg_fused;
   for (int k = 1; k <= pp.maxIterations;) {
     const int kend = std::min(pp.maxIterations, k + 15);
     for (; k <= kend; k++) {
@@ -2089,23 +2021,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
   h->cfg = *cfg;
   if (h->cfg.world_size < 1) h->cfg.world_size = 1;
   h->device = cfg->device;
-  h->two_launch_panel = dev_switch("LMGPU_PANEL_2L") != nullptr;
-  h->no_fuse = dev_switch("LMGPU_NO_FUSE") != nullptr;
-  h->no_chain = dev_switch("LMGPU_NO_CHAIN") != nullptr;
-  h->chain_forms = (dev_switch("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (dev_switch("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
-  h->no_tail = dev_switch("LMGPU_NO_TAIL") != nullptr;
-  h->tail_scalar = dev_switch("LMGPU_TAIL_SCALAR") != nullptr;
-  h->no_wide16 = dev_switch("LMGPU_NO_WIDE16") != nullptr;
-  if (const char* e = dev_switch("LMGPU_LEAF_GROUP_THREADS")) h->leaf_group_threads = atoi(e) == 64 ? 64 : (atoi(e) == 128 ? 128 : 256);
-  h->no_backsub_groups = dev_switch("LMGPU_NO_BACKSUB_GROUPS") != nullptr;
-  if (const char* e = dev_switch("LMGPU_WIDE16_MAX")) h->wide16_max = atoi(e);
-  h->bsd_ticket = dev_switch("LMGPU_BSD_TICKET") != nullptr;
-  h->no_gather_write = dev_switch("LMGPU_NO_GATHER_WRITE") != nullptr;
-  h->schur_split_diag = dev_switch("LMGPU_SCHUR_SPLIT_DIAG") != nullptr;
-  h->pcg_fused = dev_switch("LMGPU_PCG_FUSED") != nullptr;
-  if (dev_switch("LMGPU_NO_MERGE")) h->chain_merge = false;
-  if (const char* e = dev_switch("LMGPU_CHAIN_SPLIT")) h->chain_split_pct = std::max(0, std::min(100, atoi(e)));
-  if (const char* e = dev_switch("LMGPU_CHAIN_FAR")) h->chain_far_pct = std::max(10, std::min(100, atoi(e)));
+  h->sw = read_dev_switches();
   *out = h;
   if (h->device >= 0) {
     HIPCHECK(hipSetDevice(h->device));
@@ -2127,24 +2043,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
     HIPCHECK(hipHostMalloc((void**)&h->h_status, 2 * sizeof(int), hipHostMallocDefault));
     HIPCHECK(hipMalloc((void**)&h->d_lambda, sizeof(double)));
     HIPCHECK(hipMemset(h->d_lambda, 0, sizeof(double)));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_front_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_front_kernel<false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_front_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_front_merged_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_front_merged_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)level_fused_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)level_fused_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitN * kLdsLimitN * 8 + kLdsFrontExtra + 64));
-    HIPCHECK(hipFuncSetAttribute((const void*)syrk_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSyrkLds));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_backsub_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (kLdsLimitN * kLdsLimitN + LDSB_TAIL) * 8));
-    HIPCHECK(hipFuncSetAttribute((const void*)lds_backsub_merged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (kLdsLimitN * kLdsLimitN + LDSB_TAIL) * 8));
-    HIPCHECK(hipFuncSetAttribute((const void*)diag_potrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
-    HIPCHECK(hipFuncSetAttribute((const void*)panel_dataflow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PDF_LDS_BYTES));
-    HIPCHECK(hipFuncSetAttribute((const void*)step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS_BYTES));
-    HIPCHECK(hipFuncSetAttribute((const void*)chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS_BYTES));
-#ifdef LMGPU_TEST_HOOKS
-    HIPCHECK(hipFuncSetAttribute((const void*)front_tail_scalar_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_BYTES));
-#endif
-    HIPCHECK(hipFuncSetAttribute((const void*)med_diag_potrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
+    HIPCHECK(front_kernels_set_attributes());
   }
   return LMGPU_OK;
 }
@@ -2415,6 +2314,7 @@ static int upload_launch_tables(lmgpu_handle* h, const LaunchTables& T) {
   if (T.max_med > 0) HIPCHECK(hipMalloc((void**)&h->inv16_med, (size_t)T.max_med * 16 * 256 * sizeof(double)));
   if (!T.level_tasks.empty()) HIPCHECK(hipMalloc((void**)&h->d_level_sync, std::max<size_t>(1, T.med_fronts.size()) * sizeof(LevelSync)));
   HIPCHECK(hipMalloc((void**)&h->d_gcorner, std::max<size_t>(1, (size_t)T.n_gleaf) * sizeof(double)));
+  h->tabs = FrontTablesDev{h->d_fronts, h->d_ffac, h->d_fd, h->d_childs, h->d_cmap, h->d_fxoff, h->d_sxoff, h->d_lists, h->d_rowptr, h->d_rowsrc};
   return LMGPU_OK;
 }
 

@@ -123,6 +123,28 @@ def test_quadrant_update_up_to_1024_columns():
     assert {1035, 1024, 1025} <= seen
 
 
+@pytest.mark.parametrize("n,nf", [(141, 140), (300, 256), (300, 257), (1290, 540), (1600, 513)])
+def test_plainest_form_is_the_wide_clique_sequence_of_isam2(n, nf):
+    """two_launch | no_fuse | no_chain | no_tail, one rank: the form ISAM2 runs its wide cliques in.  Panel 0, then per panel the
+    update with it (quadrants up to 1024 columns behind it, 128-tiles above) and the next panel; every panel in the two-launch form;
+    the update of the last panel only when separator or right-hand-side columns follow it.  1, 2 and 3 panels; (1290, 540) crosses
+    the 1024-column threshold between its first and its second update."""
+    forms = FORM_BIT["two_launch"] | FORM_BIT["no_fuse"] | FORM_BIT["no_chain"] | FORM_BIT["no_tail"]
+    want = []
+    for i in range(-(-nf // 256)):
+        want.append((PANEL_TWO_LAUNCH, i, 0, -1))
+        m = cols_behind(n, nf, i)
+        if m > 0:
+            want.append((UPDATE_QUADRANTS if m <= 1024 else UPDATE_MFMA, i, 0, -1))
+    assert schedule(n, nf, SINGLE, forms) == want
+    assert want[-1][0] != PANEL_TWO_LAUNCH  # (n > nf in every shape: the right-hand side column at least)
+    kinds = [r[0] for r in want]
+    if (n, nf) == (1290, 540):  # 1034, 778 and 750 columns behind its three panels
+        assert kinds == [PANEL_TWO_LAUNCH, UPDATE_MFMA, PANEL_TWO_LAUNCH, UPDATE_QUADRANTS, PANEL_TWO_LAUNCH, UPDATE_QUADRANTS]
+    if (n, nf) == (1600, 513):  # 1344, 1088 and (behind a panel of one row) 1087 columns
+        assert kinds == [PANEL_TWO_LAUNCH, UPDATE_MFMA] * 3
+
+
 def test_chain_starts_where_its_tile_flags_fit():
     """(30000, 29000): fused steps until the trailing matrix has at most PDF_MAX_CHAIN_T tile rows, then ONE chained launch up to the
     last step whose next panel is full"""
