@@ -56,6 +56,16 @@ static hipError_t front_kernels_set_attributes() {
   return hipSuccess;
 }
 
+// workgroups of chain_kernel the device holds at once: what a chained launch in the resident form starts at most (chain_grid,
+// kernels_step.hpp).  Behind front_kernels_set_attributes (the kernel's LDS size is above the default limit).  Correctness does not
+// depend on the figure.
+static hipError_t chain_resident_blocks(int num_cus, int* out) {
+  int per_cu = 0;
+  if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)chain_kernel, 256, STEP_LDS_BYTES); e != hipSuccess) return e;
+  *out = num_cus * std::max(1, per_cu);
+  return hipSuccess;
+}
+
 // ---- elimination
 
 // the LDS fronts list[first .. first + count), one workgroup each: four waves (or fewer: `threads`), sixteen waves, or the gather-leaf
@@ -163,6 +173,9 @@ struct DenseExec {
   KTimer* kt;                                // (or null)
   int chain_forms;                           // test library: CHAIN_FORM_* bits
   bool tail_scalar;                          // test library: front_tail_scalar_kernel
+  int chain_resident;                        // workgroups of chain_kernel the device holds at once (chain_resident_blocks, once per handle)
+  bool chain_one_task;                       // chained launches with one workgroup per task: always, but in the test library under LMGPU_CHAIN_GRID
+  int chain_grid;                            // test library, resident form: the grid of every chained launch (0: chain_grid decides)
 };
 
 // chunk(kind, c): the caller's DENSE_ADD_CHUNK / DENSE_WAIT_CHUNK of row chunk c (split fronts only); non-zero ends the run and is returned
@@ -207,12 +220,13 @@ static int run_dense_steps(const DenseExec& X, const std::vector<DenseStep>& ste
         break;
       }
       case DENSE_CHAIN: {  // (a split front: behind the wait for the last row chunk the launch folds in)
-        ChainArgs ca{A, ld, n, nf, i, st.nsteps, X.id, X.status, X.inv16, X.pflags, X.chain_tasks + X.task_begin[r], X.Asm};
+        ChainArgs ca{A, ld, n, nf, i, st.nsteps, X.id, X.status, X.inv16, X.pflags, X.chain_tasks + X.task_begin[r], X.Asm, X.task_count[r],
+                     X.chain_one_task ? 1 : 0};
 #ifdef LMGPU_TEST_HOOKS
         ca.dev_forms = X.chain_forms;
 #endif
         const int ktc = kt.begin(LMGPU_KT_CHAIN, s);
-        hipLaunchKernelGGL(chain_kernel, dim3(X.task_count[r]), dim3(256), STEP_LDS_BYTES, s, ca);
+        hipLaunchKernelGGL(chain_kernel, dim3(chain_grid(X.task_count[r], X.chain_resident, X.chain_one_task, X.chain_grid)), dim3(256), STEP_LDS_BYTES, s, ca);
         kt.end(ktc, s, st.flop, 1);
         break;
       }

@@ -1552,7 +1552,7 @@ int is_launch_wide_front(lmgpu_isam2* S, const FrontTables& T, const FrontTables
   const std::vector<DenseStep> steps =
       dense_front_schedule(n, F.nf, DENSE_SINGLE, DENSE_FORM_TWO_LAUNCH | DENSE_FORM_NO_FUSE | DENSE_FORM_NO_CHAIN | DENSE_FORM_NO_TAIL);
   // (one set of 16 x 16 inverses, overwritten panel by panel; no dataflow launch, so no flags; no chained launch, so no ticket orders)
-  const DenseExec X{S->stream, A, nullptr, ld, n, F.nf, F.id, S->d_status, S->inv16, 0, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, false};
+  const DenseExec X{S->stream, A, nullptr, ld, n, F.nf, F.id, S->d_status, S->inv16, 0, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, false, 0, true, 0};
   return run_dense_steps(X, steps, [](int, int) { return LMGPU_INVALID; }, &S->err);  // (one rank: the schedule has no chunk records)
 }
 // one lds_front_kernel launch for the LDS fronts of level l

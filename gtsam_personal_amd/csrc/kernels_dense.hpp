@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kernels_front.hpp"
+#include "task_thread.hpp"
 
 namespace lmgpu {
 
@@ -200,7 +201,7 @@ __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int ld, int n,
   if (tj < ti) return;
   const int it0 = r0 + ti * 128, jt0 = r0 + tj * 128;  // tile origins
   if (it0 >= r1 || jt0 >= n) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tid = task_thread() & 255, wave = tid >> 6, lane = tid & 63;
   const int wr = wave >> 1, wc = wave & 1;
   const bool diag = (ti == tj);
   const bool active = !(diag && wr > wc) && (it0 + wr * 64 < r1) && (jt0 + wc * 64 < n);  // wave has something to store

@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "task_thread.hpp"
+
 namespace lmgpu {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -43,7 +45,7 @@ __device__ __forceinline__ double fast_rsqrt(double p) {
 // factor an identity against zeros: ~0.55 us per group, half of the 8.8 us of a 64-row block for a 30-column front)
 template <bool INV>
 __device__ __forceinline__ bool potrf64_wave_g4(double4_t (&T)[4][4], double4_t (&E)[4], int nrows = 64) {
-  const int lane = threadIdx.x & 63, kk = lane >> 4, cc = lane & 15;
+  const int lane = task_thread() & 63, kk = lane >> 4, cc = lane & 15;
   bool failed = false;
 #pragma unroll
   for (int g = 0; g < 4; g++) {
@@ -849,7 +851,7 @@ __device__ __forceinline__ void panel_role(double* A, int ld, int n, int nf, int
                                            unsigned int* flags, double* dsm, int* s_ok, bool fused, bool publish_strips = false) {
   double(*D)[DP_LDW] = (double(*)[DP_LDW])dsm;
   double(*XB)[DP_LDW] = (double(*)[DP_LDW])(dsm + 64 * DP_LDW);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kk = lane >> 4, cc = lane & 15;
+  const int tid = task_thread() & 255, wave = tid >> 6, lane = tid & 63, kk = lane >> 4, cc = lane & 15;
   const int nblk = kb >> 6;
   const bool diagwg = b < nblk;
   const int c0 = diagwg ? ko + 64 * b + 16 * wave : ko + kb + 64 * (b - nblk) + 16 * wave;
@@ -859,7 +861,12 @@ __device__ __forceinline__ void panel_role(double* A, int ld, int n, int nf, int
   double* Ab = A + (size_t)ko * ld + ko;  // diagonal block
   double* P = A + (size_t)ko * ld;        // row panel
   bool healthy = true;
-  if (diagwg) __builtin_amdgcn_s_setprio(3);  // the chain of the launch: ahead of the update waves sharing its SIMDs
+  // the diagonal workgroups are the chain of the launch: ahead of the update waves sharing their SIMDs.  The row-panel workgroups set
+  // theirs as well: a resident workgroup of chain_kernel may have been a diagonal workgroup or a head tile one task earlier
+  if (diagwg)
+    __builtin_amdgcn_s_setprio(3);
+  else
+    __builtin_amdgcn_s_setprio(0);
   PDF_STAMP(flags, b, 19);
   if (fused) {
     const int sj = diagwg ? b : nblk + (b - nblk);  // 64-column strip of the trailing update (its origin is ko)

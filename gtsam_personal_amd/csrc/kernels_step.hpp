@@ -14,7 +14,7 @@
 
 // development aid (tools/microbench.hip defines them): where the workgroups of a chained launch spend their time
 #ifndef CHAIN_PROF_BEGIN
-#define CHAIN_PROF_BEGIN()
+#define CHAIN_PROF_BEGIN(ticket)
 #define CHAIN_PROF_WAITED()
 #define CHAIN_PROF_STORED()
 #define CHAIN_PROF_END(cls)
@@ -121,7 +121,7 @@ __device__ __forceinline__ void syrk_subtile64(double* __restrict__ A, int ld, i
 // wt (wave-uniform): write-through C stores (kernels_dense.hpp, store_c)
 __device__ __forceinline__ void syrk_quadrant32(double* __restrict__ A, int ld, int n, int p0, int kp, int r0, int si, int sj, int qd,
                                                 const double* __restrict__ Sadd, bool wt = false) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kk = lane >> 4, cc = lane & 15;
+  const int tid = task_thread() & 255, wave = tid >> 6, lane = tid & 63, kk = lane >> 4, cc = lane & 15;
   const int wr = wave >> 1, wc = wave & 1, qr = qd >> 1, qc = qd & 1;
   if (si == sj && (qr > qc || (qr == qc && wr > wc))) return;
   const int i0 = r0 + 64 * si + 32 * qr + 16 * wr, j0 = r0 + 64 * sj + 32 * qc + 16 * wc;
@@ -269,6 +269,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, int t, const ChainL
   }
   if (t < nTA) {  // the rest of the next panel's rows: tile rows 0 and 1, tile columns 2 ..
     const int u = t - nHead, ti = u & 1, tj = 2 + (u >> 1);
+    __builtin_amdgcn_s_setprio(0);  // (every role sets its own: a resident workgroup of chain_kernel comes here from any other role)
 #ifdef LMGPU_TEST_HOOKS
     if (preread) chain_preread(a.A, a.ld, a.n, r0 + 128 * ti, r0 + 128 * tj, 128, 128);
 #endif
@@ -300,6 +301,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, int t, const ChainL
       ti++;
     }
     const int tj = ti + rem;
+    __builtin_amdgcn_s_setprio(0);
 #ifdef LMGPU_TEST_HOOKS
     if (preread) chain_preread(a.A, a.ld, a.n, r0 + 128 * ti, r0 + 128 * tj, 128, 128);
 #endif
@@ -349,8 +351,9 @@ __global__ __launch_bounds__(256, 2) void step_kernel(StepArgs a) {
 // Ticket k runs task tasks[k] = (step, logical workgroup of that step); a workgroup of step s + 1 additionally waits for what a
 // launch boundary used to guarantee: the 128-column blocks of panel s + 1 it multiplies with (counted by the row-panel
 // workgroups of step s) and the tile of step s that holds the entries it updates.  The task list (chain_schedule below,
-// built once per front on the host) is a topological order of those dependencies, and a ticket is drawn when a workgroup
-// starts, so a waiting workgroup only ever waits for workgroups that are resident or done.
+// built once per front on the host) is a topological order of those dependencies, and a ticket is drawn by a workgroup that
+// is running (at its start, and again behind every task it ends), so a waiting workgroup only ever waits for tasks that are held
+// by a running workgroup or done: the progress argument at chain_kernel.
 // What the order buys.  Right-looking step by step, the early steps have 2000+ update tiles each and the late steps almost
 // none, so the late steps run at the speed of their dependency chain (four tile stages + a head tile, ~85 us per 256 columns)
 // with the matrix cores idle.  The schedule instead gives every step about the same number of update tiles: tiles of the
@@ -368,29 +371,75 @@ struct ChainArgs {
   const int2* tasks;    // (step - i0, logical workgroup of that step) per ticket
   const double* S;      // multi-rank: the partial-assembly buffer (summed over the ranks for every row chunk this launch touches: the host
                         // waits for those chunks' events before the launch) whose rows the head tiles fold in; else nullptr
+  int ntasks = 0;       // length of `tasks`
+  int one_task = 1;     // != 0 (wave-uniform): a workgroup ends behind its first task and the launch has ntasks workgroups.  0 (test
+                        // library only): resident workgroups, see chain_kernel
 #ifdef LMGPU_TEST_HOOKS
   int dev_forms = 0;  // CHAIN_FORM_* (wave-uniform)
 #endif
 };
 
-__global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs ca) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ int s_bid, s_ok;
-  CHAIN_PROF_BEGIN();
-  if (threadIdx.x == 0) s_bid = (int)atomicAdd(&ca.flags[(size_t)(ca.i0 + 1) * PDF_FLAG_WORDS], 1u);
-  __syncthreads();
-  const int2 task = ca.tasks[s_bid];
+// the task of ticket `ticket`
+__device__ __forceinline__ void chain_task(const ChainArgs& ca, int ticket, double* sm, int* s_ok) {
+  const int2 task = ca.tasks[ticket];
   const bool merged = (task.x & CHAIN_TASK_MERGED) != 0;
   const int s = task.x & ~CHAIN_TASK_MERGED, i = ca.i0 + s;
   const int kbn = min(ca.nf, (i + 2) * 256) - (i + 1) * 256;
-  StepArgs a{ca.A, ca.ld, ca.n, ca.nf, 256 * i, 256, kbn, ca.front_id, ca.status, ca.inv16 + (size_t)(i + 1) * 4096,
+  double* A = ca.A;
+  int ld = ca.ld, n = ca.n;
+#ifdef LMGPU_TEST_HOOKS
+  // Resident form: the matrix and its shape are the same for every task of the loop, and the compiler knows it: it would compute every
+  // role's per-lane offsets (products with ld, clamps with n) once in front of the loop and keep them alive across the update tile,
+  // which has no register to spare (256 VGPRs, 128 of them accumulators) -- ~290 VGPR spills and 1.1 KB of scratch per lane.  Handed
+  // through an empty asm per task they are new values to it, and a task computes its offsets itself (task_thread.hpp: the same for
+  // what derives from threadIdx.x alone).  With both, the loop form has 1 VGPR spill and 8 bytes of scratch (one task per launch: 4, 12).
+  asm volatile("" : "+s"(A), "+s"(ld), "+s"(n));
+#endif
+  StepArgs a{A, ld, n, ca.nf, 256 * i, 256, kbn, ca.front_id, ca.status, ca.inv16 + (size_t)(i + 1) * 4096,
              ca.flags + (size_t)(i + 1) * PDF_FLAG_WORDS, ca.S};
 #ifdef LMGPU_TEST_HOOKS
   a.dev_forms = ca.dev_forms;
 #endif
   const ChainLink c{s > 0 ? ca.flags + (size_t)i * PDF_FLAG_WORDS : nullptr, s + 1 < ca.nsteps, merged,
                     (merged && s > 1) ? ca.flags + (size_t)(i - 1) * PDF_FLAG_WORDS : nullptr};
-  step_body(a, task.y, c, sm, &s_ok);
+  step_body(a, task.y, c, sm, s_ok);  // (sets the wave priority of its role)
+}
+
+// The product runs one task per workgroup: the launch has ntasks workgroups, each draws one ticket.
+//
+// The TEST library compiles the kernel as a loop (round 16): with one_task = 0 a workgroup draws tickets until the
+// list is exhausted, so the launch needs no more workgroups than the device holds at once (chain_grid below) and a slot is not torn
+// down and dispatched again between two tasks.  Any grid >= 1 completes the launch.  Measured and NOT shipped: the slots no longer
+// stand empty between workgroups, and the launch is 0.28 ms slower for it -- it is as long as its panel chain, and the diagonal
+// workgroups share their CUs with more update tiles.  The loop stays here as the A/B partner of that measurement.
+// Progress of the loop.  Tickets are drawn in list order, and only by workgroups that are running.  The list is a topological order
+// of the waits (lmgpu_selftest_chain_schedule checks that; tests/test_chain_ticket_order_product.py with the product's parameters).
+// So every task that the holder of the LOWEST unfinished ticket waits for has a lower ticket and is finished: that holder waits for
+// nothing and ends its task, then the next lowest does, and so on -- every wait ends.  Nothing here assumes that two workgroups are
+// resident together: a workgroup that has not started holds no ticket, and one that waits holds a ticket above the lowest unfinished
+// one.  (The same argument covers one task per workgroup; a workgroup that loops draws its next ticket only behind the end of its
+// task, so it never holds two.)
+__global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs ca) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ int s_bid, s_ok;
+#ifndef LMGPU_TEST_HOOKS
+  if (threadIdx.x == 0) s_bid = (int)atomicAdd(&ca.flags[(size_t)(ca.i0 + 1) * PDF_FLAG_WORDS], 1u);
+  __syncthreads();
+  chain_task(ca, s_bid, sm, &s_ok);
+#else
+  for (;;) {
+    // every wave is done with the task before: with s_bid and s_ok, and with the LDS stage buffers (several roles end without a
+    // publish barrier: tiles of the last step, row-panel workgroups that publish no strips, waves that leave syrk_tile early)
+    __syncthreads();
+    if (threadIdx.x == 0) s_bid = (int)atomicAdd(&ca.flags[(size_t)(ca.i0 + 1) * PDF_FLAG_WORDS], 1u);
+    __syncthreads();
+    const int ticket = s_bid;
+    if (ticket >= ca.ntasks) break;
+    CHAIN_PROF_BEGIN(ticket);
+    chain_task(ca, ticket, sm, &s_ok);
+    if (ca.one_task) break;
+  }
+#endif
 }
 
 }  // namespace lmgpu
@@ -399,6 +448,18 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs ca) {
 #include <algorithm>
 #include <vector>
 namespace lmgpu {
+
+// workgroups of a chained launch of `ntasks` tasks: one per task, or -- resident form, test library -- as many as the device holds of
+// chain_kernel at once (`resident` = compute units x hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once per handle; forced > 0:
+// LMGPU_CHAIN_GRID)
+__host__ inline int chain_grid(int ntasks, int resident, bool one_task, int forced = 0) {
+#ifndef LMGPU_TEST_HOOKS
+  one_task = true;  // (the product's kernel has no loop)
+#endif
+  if (one_task) return ntasks;
+  if (forced > 0) return forced;
+  return std::max(1, std::min(ntasks, resident));
+}
 
 // n, nf: front size and frontal rows; steps i0 .. i0 + nsteps - 1.  Per step s the logical workgroups are laid out as in
 // step_body: [head tiles][diagonal workgroups][update tiles, tile rows 2.. row-major][row-panel workgroups].

@@ -71,6 +71,8 @@ struct DevSwitches {
   bool no_tail = false;           // LMGPU_NO_TAIL=1: the end of a front as separate update / panel launches (A/B)
   bool tail_scalar = false;       // LMGPU_TAIL_SCALAR=1: front_tail_scalar_kernel, the LDS / scalar-FMA form (cross-check)
   int chain_forms = 0;            // CHAIN_FORM_* bits: LMGPU_CHAIN_FENCED_TILES, LMGPU_CHAIN_PREREAD (kernels_step.hpp)
+  bool chain_one_task = true;     // a chained launch as one workgroup per task (the product's form; LMGPU_CHAIN_ONE_TASK=1 says so explicitly) ...
+  int chain_grid = 0;             // ... LMGPU_CHAIN_GRID=<n>: as resident workgroups that draw tickets in a loop, n of them (0: min(tasks, resident workgroups)) (A/B)
   bool chain_merge = true;        // LMGPU_NO_MERGE: update tiles one step per pass instead of pairs of steps (chain_schedule)
   int chain_split_pct = 60;       // LMGPU_CHAIN_SPLIT: share of a block's update tasks listed in front of its row-panel workgroups
   int chain_far_pct = 50;         // LMGPU_CHAIN_FAR: tile rows beyond this percentage of the front are scheduled late (chain_schedule)
@@ -111,6 +113,10 @@ static DevSwitches read_dev_switches() {
   w.no_tail = on("LMGPU_NO_TAIL");
   w.tail_scalar = on("LMGPU_TAIL_SCALAR");
   w.chain_forms = (on("LMGPU_CHAIN_FENCED_TILES") ? CHAIN_FORM_FENCED_TILES : 0) | (on("LMGPU_CHAIN_PREREAD") ? CHAIN_FORM_PREREAD : 0);
+  if (const char* e = dev_switch("LMGPU_CHAIN_GRID")) {
+    w.chain_one_task = on("LMGPU_CHAIN_ONE_TASK");
+    w.chain_grid = std::max(0, atoi(e));
+  }
   w.chain_merge = !on("LMGPU_NO_MERGE");
   if (const char* e = dev_switch("LMGPU_CHAIN_SPLIT")) w.chain_split_pct = std::max(0, std::min(100, atoi(e)));
   if (const char* e = dev_switch("LMGPU_CHAIN_FAR")) w.chain_far_pct = std::max(10, std::min(100, atoi(e)));
@@ -410,6 +416,7 @@ struct lmgpu_handle {
   ZeroRange* d_zero_ranges = nullptr;   // the HBM fronts a solve clears first, when they are many and scattered (zero_ranges_kernel)
   int n_zero_ranges = 0;
   int num_cus = 0;                      // compute units of the device (a grid of at most this many small workgroups is resident at once)
+  int chain_resident = 0;               // workgroups of chain_kernel the device holds at once: the grid of a chained launch (chain_grid)
   // deterministic assembly of HBM fronts (kernels_dense.hpp: hbm_assemble_rows_kernel): per front the start of its n + 1 row
   // pointers in d_rowptr (-1: none), the pointers (offsets into d_rowsrc) and the sources
   std::vector<int32_t> row_begin;
@@ -1054,7 +1061,8 @@ static int eliminate_hbm_front(lmgpu_handle* h, int fi, const Damping& dmp) {
   const lmgpu_handle::DensePlan& plan = h->dense_plans[fi];
   h->inv16_owner = fi;  // the per-panel 16x16 inverses now belong to this front (read again by its back-substitution)
   const DenseExec X{s, A, split ? (const double*)Asm : nullptr, ld, F.n, F.nf, F.id, h->d_status, h->inv16, 4096, h->d_pflags, h->pflags_prefilled,
-                    h->d_chain_tasks, plan.task_begin.data(), plan.task_count.data(), &h->kt, h->sw.chain_forms, h->sw.tail_scalar};
+                    h->d_chain_tasks, plan.task_begin.data(), plan.task_count.data(), &h->kt, h->sw.chain_forms, h->sw.tail_scalar,
+                    h->chain_resident, h->sw.chain_one_task, h->sw.chain_grid};
   return run_dense_steps(X, plan.steps, [&](int kind, int c) { return kind == DENSE_ADD_CHUNK ? add_chunk(h, A, Asm, F.n, ld, c) : wait_chunk(h, Asm, F.n, ld, c); },
                          &h->err);
 }
@@ -2044,6 +2052,7 @@ int lmgpu_create(const lmgpu_config* cfg, lmgpu_handle** out) {
     HIPCHECK(hipMalloc((void**)&h->d_lambda, sizeof(double)));
     HIPCHECK(hipMemset(h->d_lambda, 0, sizeof(double)));
     HIPCHECK(front_kernels_set_attributes());
+    HIPCHECK(chain_resident_blocks(h->num_cus, &h->chain_resident));
   }
   return LMGPU_OK;
 }

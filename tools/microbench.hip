@@ -3,6 +3,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../gtsam_personal_amd/csrc tools/microbench.hip -o tools/microbench
 // With -DLMGPU_TEST_HOOKS the kernels carry the test library's hand-off forms as well and   microbench <n> <far_pct> <merge> <forms>
 // selects them for the chained launch (CHAIN_FORM_* bits of kernels_step.hpp: 1 = tiles published behind a release fence).
+//   microbench <n> <far_pct> <merge> <forms> <one_task 0|1> [grid]   the chained launch as resident workgroups that draw tickets in a
+// loop (0, the default; grid: forced, else min(tasks, resident workgroups)) or as one workgroup per task (1).  Stamps are per TASK.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,15 +28,20 @@
 // of the publish; g_fence[3 cls] = release fences, [3 cls + 1] = the signaller's ticks inside them (fence + its wait)
 __device__ unsigned long long g_prof[16], g_hist[256], g_t0, g_begin[1 << 17], g_waited[1 << 17];
 __device__ unsigned long long g_pub[16], g_fence[16], g_stored[1 << 17], g_fence_n[1 << 17], g_fence_t[1 << 17], g_fence_b[1 << 17];
+// per TASK (ticket): start (ticket drawn), inputs there, end, and the workgroup that ran it; g_ticket: the workgroup's current ticket
+#define PROF_MAX_TASKS (1 << 17)
+__device__ unsigned long long g_tb[PROF_MAX_TASKS], g_tw[PROF_MAX_TASKS], g_te[PROF_MAX_TASKS];
+__device__ unsigned int g_twg[PROF_MAX_TASKS], g_ticket[1 << 17];
 __device__ __forceinline__ unsigned long long prof_now() {
   unsigned long long t_;
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");
   return t_;
 }
-#define CHAIN_PROF_BEGIN()                                  \
+#define CHAIN_PROF_BEGIN(ticket)                            \
   do {                                                      \
     if (threadIdx.x == 0) {                                 \
       g_begin[blockIdx.x] = prof_now();                     \
+      g_ticket[blockIdx.x] = (unsigned int)(ticket);        \
       g_waited[blockIdx.x] = 0;                             \
       g_stored[blockIdx.x] = 0;                             \
       g_fence_n[blockIdx.x] = 0;                            \
@@ -64,6 +71,13 @@ __device__ __forceinline__ unsigned long long prof_now() {
       const unsigned long long e_ = prof_now(), b_ = g_begin[blockIdx.x];                \
       g_begin[blockIdx.x] = 0;                                                           \
       const unsigned long long w_ = g_waited[blockIdx.x] ? g_waited[blockIdx.x] : b_;    \
+      const unsigned int k_ = g_ticket[blockIdx.x];                                      \
+      if (k_ < PROF_MAX_TASKS) {                                                         \
+        g_tb[k_] = b_;                                                                   \
+        g_tw[k_] = w_;                                                                   \
+        g_te[k_] = e_;                                                                   \
+        g_twg[k_] = blockIdx.x;                                                          \
+      }                                                                                  \
       atomicAdd(&g_prof[3 * (cls)], 1ull);                                               \
       atomicAdd(&g_prof[3 * (cls) + 1], w_ - b_);                                        \
       atomicAdd(&g_prof[3 * (cls) + 2], e_ - w_);                                        \
@@ -238,6 +252,16 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute((const void*)chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEP_LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)panel_dataflow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PDF_LDS_BYTES));
     auto rows_of = [&](int i) { return std::min(n - 1, (i + 1) * 256) - i * 256; };
+    const bool one_task = argc > 5 && atoi(argv[5]) != 0;
+    const int forced_grid = argc > 6 ? atoi(argv[6]) : 0;
+    int num_cus = 0, per_cu = 0;
+    {
+      hipDeviceProp_t prop;
+      CK(hipGetDeviceProperties(&prop, 0));
+      num_cus = prop.multiProcessorCount;
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)chain_kernel, 256, STEP_LDS_BYTES));
+    }
+    const int resident = num_cus * std::max(1, per_cu);
     for (int first : {0, 17}) {
       int nsteps = 0;
       while (first + nsteps + 1 < np && rows_of(first + nsteps) == 256 && rows_of(first + nsteps + 1) % 64 == 0 && n - (first + nsteps + 1) * 256 > 0) nsteps++;
@@ -245,7 +269,12 @@ int main(int argc, char** argv) {
       int2* d_tasks;
       CK(hipMalloc((void**)&d_tasks, tasks.size() * sizeof(int2)));
       CK(hipMemcpy(d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice));
-      ChainArgs ca{A, ld, n, n - 1, first, nsteps, 0, status, inv16, flags, d_tasks};
+      ChainArgs ca{A, ld, n, n - 1, first, nsteps, 0, status, inv16, flags, d_tasks, nullptr, (int)tasks.size(), one_task ? 1 : 0};
+      if (tasks.size() > PROF_MAX_TASKS) {
+        printf("more than %d tasks: no per-task stamps\n", PROF_MAX_TASKS);
+        return 1;
+      }
+      const int grid = chain_grid((int)tasks.size(), resident, one_task, forced_grid);
 #ifdef LMGPU_TEST_HOOKS
       ca.dev_forms = argc > 4 ? atoi(argv[4]) : 0;
       printf("hand-off forms %d\n", ca.dev_forms);
@@ -266,12 +295,13 @@ int main(int argc, char** argv) {
         CK(hipMemcpyToSymbol(HIP_SYMBOL(g_t0), &big, 8));
       }
       CK(hipEventRecord(e0, 0));
-      hipLaunchKernelGGL(chain_kernel, dim3((int)tasks.size()), dim3(256), STEP_LDS_BYTES, 0, ca);
+      hipLaunchKernelGGL(chain_kernel, dim3(grid), dim3(256), STEP_LDS_BYTES, 0, ca);
       CK(hipEventRecord(e1, 0));
       CK(hipEventSynchronize(e1));
       float ms;
       CK(hipEventElapsedTime(&ms, e0, e1));
-      printf("chain_kernel steps %d..%d (%d workgroups): %.1f us\n", first, first + ca.nsteps - 1, (int)tasks.size(), ms * 1e3);
+      printf("chain_kernel steps %d..%d (%d tasks, %s, grid %d, %d workgroups resident = %d CUs x %d): %.1f us\n", first, first + ca.nsteps - 1,
+             (int)tasks.size(), one_task ? "one task per workgroup" : "resident workgroups draw tickets in a loop", grid, resident, num_cus, per_cu, ms * 1e3);
       std::vector<unsigned int> hf((size_t)(np + 2) * PDF_FLAG_WORDS);
       CK(hipMemcpy(hf.data(), flags, hf.size() * 4, hipMemcpyDeviceToHost));
       auto st = [&](int region, int b, int slot) { return *(unsigned long long*)&hf[(size_t)region * PDF_FLAG_WORDS + 512 + 64 * b + 2 * slot]; };
@@ -295,10 +325,52 @@ int main(int argc, char** argv) {
           printf("  class %-14s: publish %6llu x avg %5.2f us = %8.1f us of slot-time | release fences %6llu x avg %5.2f us = %8.1f us\n", cn[c], pb[3 * c],
                  pb[3 * c] ? pb[3 * c + 1] / 100.0 / pb[3 * c] : 0.0, pb[3 * c + 1] / 100.0, fe[3 * c], fe[3 * c] ? fe[3 * c + 1] / 100.0 / fe[3 * c] : 0.0,
                  fe[3 * c + 1] / 100.0);
-        printf("  slot occupancy (working workgroup-time / (512 slots x launch time)): %.3f\n", tot_work / (512.0 * ms * 1e3));
-        printf("  working slots per 100 us bucket (of 512):");
+        printf("  slot occupancy (working workgroup-time / (%d slots x launch time)): %.3f\n", resident, tot_work / ((double)resident * ms * 1e3));
+        printf("  working slots per 100 us bucket (of %d):", resident);
         for (int b = 0; b < 256 && b * 100.0 < ms * 1e3; b++) printf(" %d", (int)(hi[b] / 10000.0 + 0.5));
         printf("\n");
+      }
+      {
+        // Slot-time per TASK, split at the moment the ticket list is exhausted (the last ticket drawn).  A slot = one of the `resident`
+        // workgroup places of the device.  in task = ticket drawn .. end of the task (waiting for inputs + working); between tasks =
+        // end of a task .. next ticket drawn by the SAME workgroup (barrier, ticket atomic; resident form only); empty = the rest:
+        // no workgroup in the slot, or one that has not drawn its first ticket yet (one-task form: the turnover of the slot).
+        const size_t nt = tasks.size();
+        std::vector<unsigned long long> tb(nt), tw(nt), te(nt);
+        std::vector<unsigned int> twg(nt);
+        CK(hipMemcpyFromSymbol(tb.data(), HIP_SYMBOL(g_tb), nt * 8));
+        CK(hipMemcpyFromSymbol(tw.data(), HIP_SYMBOL(g_tw), nt * 8));
+        CK(hipMemcpyFromSymbol(te.data(), HIP_SYMBOL(g_te), nt * 8));
+        CK(hipMemcpyFromSymbol(twg.data(), HIP_SYMBOL(g_twg), nt * 4));
+        unsigned long long k0 = ~0ull, kx = 0, kend = 0;
+        for (size_t k = 0; k < nt; k++) k0 = std::min(k0, tb[k]), kx = std::max(kx, tb[k]), kend = std::max(kend, te[k]);
+        auto part = [](unsigned long long a, unsigned long long b, unsigned long long lo, unsigned long long hi) {
+          const unsigned long long x = std::max(a, lo), y = std::min(b, hi);
+          return y > x ? (double)(y - x) : 0.0;
+        };
+        double wait[2] = {0, 0}, work[2] = {0, 0}, gap[2] = {0, 0};
+        for (size_t k = 0; k < nt; k++) {
+          wait[0] += part(tb[k], tw[k], k0, kx), wait[1] += part(tb[k], tw[k], kx, kend);
+          work[0] += part(tw[k], te[k], k0, kx), work[1] += part(tw[k], te[k], kx, kend);
+        }
+        std::vector<size_t> order(nt);
+        for (size_t k = 0; k < nt; k++) order[k] = k;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return twg[a] != twg[b] ? twg[a] < twg[b] : tb[a] < tb[b]; });
+        size_t ngaps = 0;
+        for (size_t q = 1; q < nt; q++)
+          if (twg[order[q]] == twg[order[q - 1]]) {
+            gap[0] += part(te[order[q - 1]], tb[order[q]], k0, kx), gap[1] += part(te[order[q - 1]], tb[order[q]], kx, kend);
+            ngaps++;
+          }
+        printf("  ticket list exhausted at %.1f us of %.1f us (first ticket drawn = 0)\n", (kx - k0) / 100.0, (kend - k0) / 100.0);
+        for (int h = 0; h < 2; h++) {
+          const double total = (double)resident * (double)(h ? kend - kx : kx - k0);
+          const double empty = total - wait[h] - work[h] - gap[h];
+          printf("  slot-time %s the list is exhausted: %10.1f ms = working %9.1f + waiting %8.1f + between tasks %7.1f + empty %8.1f ms (empty %.1f %%)\n",
+                 h ? "AFTER " : "BEFORE", total / 1e5, work[h] / 1e5, wait[h] / 1e5, gap[h] / 1e5, empty / 1e5, total > 0 ? 100.0 * empty / total : 0.0);
+        }
+        printf("  between tasks of one workgroup: %zu hand-overs, avg %.2f us; empty slot-time before exhaustion per task: %.2f us\n", ngaps,
+               ngaps ? (gap[0] + gap[1]) / 100.0 / ngaps : 0.0, ((double)resident * (double)(kx - k0) - wait[0] - work[0] - gap[0]) / 100.0 / nt);
       }
       {  // cadence of the whole chain: when panel s + 1 was complete (last diagonal workgroup published), and the flop done by then
         double prev = 0, flop_acc = 0;
