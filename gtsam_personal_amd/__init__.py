@@ -12,6 +12,7 @@ from .optimizer import (BlockJacobiPreconditionerParameters, DirectionMethod, Do
                         NonlinearConjugateGradientOptimizer,
                         PCGSolverParameters)
 from .init_pose3 import InitializePose3  # noqa: F401
+from .translation_recovery import MFAS, BinaryMeasurement, TranslationRecovery  # noqa: F401
 from .triangulation import (TriangulationCheiralityException, TriangulationParameters, TriangulationResult,  # noqa: F401
                             TriangulationUnderconstrainedException, camera_s2_pack, triangulatePoint3, triangulateSafe, triangulateSafeBatch)
 from .smart import SmartProjectionParams, SmartProjectionPoseFactor  # noqa: F401

@@ -141,6 +141,11 @@ class lmgpu_marginals_stats(ct.Structure):
                 ("cross_lds", ct.c_int64), ("cross_scratch", ct.c_int64), ("longest_union", ct.c_int32), ("cross_cap", ct.c_int32)]
 
 
+class lmgpu_mfas_stats(ct.Structure):
+    _fields_ = [("n_nodes", ct.c_int32), ("global_state", ct.c_int32), ("lds_node_capacity", ct.c_int32), ("pad_", ct.c_int32),
+                ("kernel_ms", ct.c_double)]
+
+
 # every symbol include/lmgpu.h declares: name -> (restype, argtypes)
 _H = ct.c_void_p
 _D = ct.POINTER(ct.c_double)
@@ -207,6 +212,26 @@ SYMBOLS = {
     "lmgpu_init_pose3_orientations_gradient": (ct.c_int, [_H, _D, ct.c_int32, ct.c_int32, _D, _I, _D]),
     "lmgpu_init_pose3_compute_poses": (ct.c_int, [_H, _D, ct.c_int32, _D, ct.POINTER(lmgpu_lm_state)]),
     "lmgpu_init_pose3_initialize": (ct.c_int, [_H, _D, ct.c_int32, _D]),
+    "lmgpu_translation_recovery_create": (ct.c_int, [ct.POINTER(lmgpu_config), ct.POINTER(_H)]),
+    "lmgpu_translation_recovery_destroy": (ct.c_int, [_H]),
+    "lmgpu_translation_recovery_last_error": (ct.c_char_p, [_H]),
+    "lmgpu_translation_recovery_seed": (ct.c_int, [_H, ct.c_uint32]),
+    "lmgpu_translation_recovery_set_prior_sigma": (ct.c_int, [_H, ct.c_double]),
+    "lmgpu_translation_recovery_add_directions": (ct.c_int, [_H, ct.c_int32, _I, ct.POINTER(ct.c_uint64), _D, ct.c_int32, _D, ct.c_int32, ct.c_double]),
+    "lmgpu_translation_recovery_add_betweens": (ct.c_int, [_H, ct.c_int32, _I, ct.POINTER(ct.c_uint64), _D, ct.c_int32, _D, ct.c_int32, ct.c_double]),
+    "lmgpu_translation_recovery_finalize": (ct.c_int, [_H, ct.c_double, ct.c_int32, ct.POINTER(ct.c_uint64), _D, ct.c_int32, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_translation_recovery_num_keys": (ct.c_int, [_H]),
+    "lmgpu_translation_recovery_num_factors": (ct.c_int, [_H]),
+    "lmgpu_translation_recovery_get_keys": (ct.c_int, [_H, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint64)]),
+    "lmgpu_translation_recovery_get_slots": (ct.c_int, [_H, ct.POINTER(ct.c_uint64)]),
+    "lmgpu_translation_recovery_get_initial": (ct.c_int, [_H, _D]),
+    "lmgpu_translation_recovery_handle": (ct.c_void_p, [_H]),
+    "lmgpu_translation_recovery_run": (ct.c_int, [_H, ct.POINTER(lmgpu_lm_params), ct.POINTER(lmgpu_lm_state)]),
+    "lmgpu_translation_recovery_get": (ct.c_int, [_H, _D]),
+    "lmgpu_mfas_outlier_weights": (ct.c_int, [ct.c_int32, ct.c_int32, ct.POINTER(ct.c_uint64), _D, ct.c_int32, _D, _D, ct.POINTER(ct.c_uint64), _D, _D,
+                                              ct.POINTER(lmgpu_mfas_stats)]),
+    "lmgpu_mfas_lds_node_capacity": (ct.c_int, []),
+    "lmgpu_mfas_last_error": (ct.c_char_p, []),
     "lmgpu_set_kernel_timing": (ct.c_int, [_H, ct.c_int32]),
     "lmgpu_get_kernel_times": (ct.c_int, [_H, _D, _D, ct.POINTER(ct.c_int64)]),
     "lmgpu_get_jacobian": (ct.c_int, [_H, ct.c_int32, _D, _I, _I]),

@@ -19,8 +19,13 @@ struct FactorType {
 };
 // entries 0 .. 13: the public lmgpu_factor_type; entry 14 (kSmartObsType): one observation of a smart projection factor, (POSE3, hidden
 // POINT3) in the shape of LMGPU_F_PROJECTION -- internal to the batch handle (smart.hpp), never accepted at the boundary
+// entries 15, 16: the two factor kinds of TranslationRecovery (translation_recovery.hpp), both (POINT3, POINT3) with a 3-vector measurement:
+// TranslationFactor (gtsam/sfm/TranslationFactor.h) and BetweenFactor<Point3> -- internal to that session's inner handle in the same way
 static const int kSmartObsType = 14;
-static constexpr FactorType kFactorTypes[15] = {
+static const int kTranslationType = 15;
+static const int kBetweenPoint3Type = 16;
+static const int kNumFactorRows = 17;
+static constexpr FactorType kFactorTypes[kNumFactorRows] = {
     {2, 2, {LMGPU_CAM_BUNDLER, LMGPU_POINT3, -1}},        // LMGPU_F_SFM
     {3, 3, {LMGPU_POSE2, LMGPU_POSE2, -1}},               // LMGPU_F_BETWEEN_POSE2
     {6, 12, {LMGPU_POSE3, LMGPU_POSE3, -1}},              // LMGPU_F_BETWEEN_POSE3
@@ -36,8 +41,10 @@ static constexpr FactorType kFactorTypes[15] = {
     {9, 9, {LMGPU_VEC9, LMGPU_VEC9, -1}},                 // LMGPU_F_CHORDAL_BETWEEN
     {9, 9, {LMGPU_VEC9, -1, -1}},                         // LMGPU_F_PRIOR_VEC9
     {2, 7, {LMGPU_POSE3, LMGPU_POINT3, -1}},              // kSmartObsType
+    {3, 3, {LMGPU_POINT3, LMGPU_POINT3, -1}},             // kTranslationType
+    {3, 3, {LMGPU_POINT3, LMGPU_POINT3, -1}},             // kBetweenPoint3Type
 };
-static_assert(LMGPU_NUM_FACTOR_TYPES == kSmartObsType, "one row per public factor type, then the internal one");
+static_assert(LMGPU_NUM_FACTOR_TYPES == kSmartObsType, "one row per public factor type, then the internal ones");
 
 constexpr int var_type(int type, int k) { return kFactorTypes[type].var[k]; }
 constexpr int factor_arity(int type) {

@@ -517,6 +517,39 @@ __device__ __forceinline__ void eval_prior_vec9(const double* m, const double* v
   if (JAC) set_identity<9>(H1);
 }
 
+// TranslationFactor (gtsam/sfm/TranslationFactor.h:68-78): e = normalize(Tb - Ta) - z, H2 = H, H1 = -H with H the expression of
+// gtsam/geometry/Point3.cpp:52-62 (nine products over pow(x^2 + y^2 + z^2, 1.5)).  Tb = Ta has no guard here as it has none there.
+template <bool JAC>
+__device__ __forceinline__ void eval_translation(const double* m, const double* v0, const double* v1, double* e, double* H1, double* H2) {
+  const double x = v1[0] - v0[0], y = v1[1] - v0[1], z = v1[2] - v0[2];
+  const double x2 = x * x, y2 = y * y, z2 = z * z;
+  const double n = sqrt(x2 + y2 + z2);
+  e[0] = x / n - m[0];
+  e[1] = y / n - m[1];
+  e[2] = z / n - m[2];
+  if (JAC) {
+    const double xy = x * y, xz = x * z, yz = y * z;
+    const double d = pow(x2 + y2 + z2, 1.5);
+    const double H[9] = {y2 + z2, -xy, -xz, -xy, x2 + z2, -yz, -xz, -yz, x2 + y2};
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      H2[i] = H[i] / d;
+      H1[i] = -H2[i];
+    }
+  }
+}
+// BetweenFactor<Point3> (gtsam/slam/BetweenFactor.h:111-124 on a vector space): e = (Tb - Ta) - z, H1 = -I, H2 = I
+template <bool JAC>
+__device__ __forceinline__ void eval_between_point3(const double* m, const double* v0, const double* v1, double* e, double* H1, double* H2) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) e[i] = (v1[i] - v0[i]) - m[i];
+  if (JAC) {
+    set_identity<3>(H2);
+#pragma unroll
+    for (int i = 0; i < 9; i++) H1[i] = -H2[i];
+  }
+}
+
 // GeneralSFMFactor2<Cal3_S2> (gtsam/slam/GeneralSFMFactor.h:208-262): one lane per factor, three variables (Pose3, Point3, Cal3_S2).
 // error = PinholeCamera<Cal3_S2>(pose, K).project(point) - z with H1 (2x6), H2 (2x3) as GenericProjectionFactor's (PinholePose chain) and
 // H3 = Cal3_S2::uncalibrate's Dcal = [u 0 v 1 0; 0 v 0 0 1] at the intrinsic point (u, v) (gtsam/geometry/Cal3_S2.cpp:44-50).  A point
@@ -616,6 +649,8 @@ static_assert(factor_dims_are<LMGPU_F_BEARING_RANGE_2D, 2, 3, 2, 2, 0, 3, 4, 2>(
 static_assert(factor_dims_are<LMGPU_F_PRIOR_CAL3_S2, 5, 5, 0, 5, 5, 5, -1, 0>(), "PRIOR_CAL3_S2");
 static_assert(factor_dims_are<LMGPU_F_CHORDAL_BETWEEN, 9, 9, 9, 9, 6, 9, 6, 9>(), "CHORDAL_BETWEEN");
 static_assert(factor_dims_are<LMGPU_F_PRIOR_VEC9, 9, 9, 0, 9, 6, 9, -1, 0>(), "PRIOR_VEC9");
+static_assert(factor_dims_are<kTranslationType, 3, 3, 3, 3, 2, 3, 2, 3>(), "kTranslationType");
+static_assert(factor_dims_are<kBetweenPoint3Type, 3, 3, 3, 3, 2, 3, 2, 3>(), "kBetweenPoint3Type");
 
 // Generic bucket kernel.  TYPE selects the evaluator and, through FactorDims, every size.
 template <int TYPE, bool JAC>
@@ -651,6 +686,8 @@ __device__ __forceinline__ void generic_factor_body(const BucketDev& b, const Va
   if (TYPE == 11) eval_prior_cal3_s2<JAC>(m, v0, e, H1);
   if (TYPE == 12) eval_chordal_between<JAC>(m, v0, v1, e, H1, H2);
   if (TYPE == 13) eval_prior_vec9<JAC>(m, v0, e, H1);
+  if (TYPE == kTranslationType) eval_translation<JAC>(m, v0, v1, e, H1, H2);
+  if (TYPE == kBetweenPoint3Type) eval_between_point3<JAC>(m, v0, v1, e, H1, H2);
   if (TYPE == 8) {
     // GenericProjectionFactor with body_P_sensor (ProjectionFactor.h:142-149): camera pose = pose o sensor; H1 = H1_cam Ad(sensor^-1)
     const P3 sensor = load_pose3(m + 7);
@@ -736,6 +773,16 @@ __host__ __device__ __forceinline__ bool for_generic_type(int type, Fn&& f) {
   }
   return false;
 }
+// The internal generic types (factor_types.hpp, entries 15 and 16).  A list of their own, consulted by launch_generic_bucket alone:
+// for_generic_type also instantiates ISAM2's linearize_multi_kernel, which must stay the kernel it was.
+template <class Fn>
+__host__ __forceinline__ bool for_internal_generic_type(int type, Fn&& f) {
+  switch (type) {
+    LMGPU_GENERIC_TYPE(kTranslationType);
+    LMGPU_GENERIC_TYPE(kBetweenPoint3Type);
+  }
+  return false;
+}
 #undef LMGPU_GENERIC_TYPE
 
 // One bucket through the kernel of its type: a generic type or LMGPU_F_SFM2, one lane per factor in blocks of 128.  false: the type has
@@ -747,9 +794,8 @@ bool launch_generic_bucket(const BucketDev& d, const ValuesDev& vals, double* eb
     hipLaunchKernelGGL(sfm2_factor_kernel<JAC>, grid, block, 0, s, d, vals, ebuf);
     return true;
   }
-  return for_generic_type(d.type, [&](auto t) {
-    hipLaunchKernelGGL((generic_factor_kernel<decltype(t)::value, JAC>), grid, block, 0, s, d, vals, ebuf);
-  });
+  auto launch = [&](auto t) { hipLaunchKernelGGL((generic_factor_kernel<decltype(t)::value, JAC>), grid, block, 0, s, d, vals, ebuf); };
+  return for_generic_type(d.type, launch) || for_internal_generic_type(d.type, launch);
 }
 
 // Linearization of SEVERAL buckets in one launch (ISAM2: an update relinearizes two or three factor types, each a launch of a few

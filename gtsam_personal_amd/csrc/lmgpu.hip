@@ -2138,6 +2138,9 @@ int lmgpu_add_factor_bucket(lmgpu_handle* h, int32_t type, int32_t n, const int3
   return lmgpu_add_factor_bucket_robust(h, type, n, graph_index, var_slots, meas, noise_kind, noise, LMGPU_ROBUST_NONE, 0.0);
 }
 
+static int add_bucket_of_row(lmgpu_handle* h, int32_t type, int32_t n, const int32_t* graph_index, const int32_t* var_slots, const double* meas,
+                             int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k);
+
 int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, const int32_t* graph_index, const int32_t* var_slots,
                                    const double* meas, int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k) {
   if (!h) return LMGPU_INVALID;
@@ -2145,6 +2148,24 @@ int lmgpu_add_factor_bucket_robust(lmgpu_handle* h, int32_t type, int32_t n, con
     h->err = "lmgpu_add_factor_bucket_robust: refused (h->finalized || type < 0 || type >= LMGPU_NUM_FACTOR_TYPES || n < 0 || h->plan.n_vars == 0)";
     return LMGPU_INVALID;
   }
+  return add_bucket_of_row(h, type, n, graph_index, var_slots, meas, noise_kind, noise, robust_kind, robust_k);
+}
+
+// A bucket of one of the INTERNAL generic rows of the factor-type table (factor_types.hpp: kTranslationType, kBetweenPoint3Type), for the
+// sessions inside the library that own their handle (translation_recovery.hpp).  Not exported: the boundary above keeps refusing them.
+static int add_internal_factor_bucket(lmgpu_handle* h, int32_t type, int32_t n, const int32_t* graph_index, const int32_t* var_slots,
+                                      const double* meas, int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k) {
+  if (!h) return LMGPU_INVALID;
+  if (h->finalized || (type != kTranslationType && type != kBetweenPoint3Type) || n < 0 || h->plan.n_vars == 0) {
+    h->err = "add_internal_factor_bucket: refused (h->finalized || not an internal generic type || n < 0 || h->plan.n_vars == 0)";
+    return LMGPU_INVALID;
+  }
+  return add_bucket_of_row(h, type, n, graph_index, var_slots, meas, noise_kind, noise, robust_kind, robust_k);
+}
+
+// the body shared by the two: `type` is a row of kFactorTypes its caller has admitted
+static int add_bucket_of_row(lmgpu_handle* h, int32_t type, int32_t n, const int32_t* graph_index, const int32_t* var_slots, const double* meas,
+                             int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k) {
   if (robust_kind < LMGPU_ROBUST_NONE || robust_kind > LMGPU_ROBUST_L2_WITH_DEAD_ZONE || (robust_kind != LMGPU_ROBUST_NONE && !(robust_k > 0.0)))
     return LMGPU_INVALID;
   if (noise_kind != LMGPU_N_UNIT && noise_kind != LMGPU_N_DIAG && noise_kind != LMGPU_N_GAUSS) return LMGPU_INVALID;
@@ -3827,6 +3848,8 @@ int lmgpu_peak_hbm_copy(int32_t device, int64_t bytes, int32_t iters, double* gb
 
 #include "isam2.hpp"
 #include "init_pose3.hpp"
+#include "translation_recovery.hpp"
+#include "mfas.hpp"
 #include "ncg.hpp"
 #include "triangulation.hpp"
 #include "marginals.hpp"

@@ -434,6 +434,88 @@ int lmgpu_init_pose3_orientations_gradient(lmgpu_init_pose3* ip, const double* g
 int lmgpu_init_pose3_compute_poses(lmgpu_init_pose3* ip, const double* R, int32_t single_iter, double* poses_out, lmgpu_lm_state* gn_state_out);
 int lmgpu_init_pose3_initialize(lmgpu_init_pose3* ip, const double* guess_R, int32_t use_gradient, double* poses_out);
 
+/* ---- TranslationRecovery (gtsam/sfm/TranslationRecovery.{h,cpp}, TranslationFactor.h): positions from relative translation DIRECTIONS ----
+ * A session object like lmgpu_init_pose3: it owns one inner lmgpu_handle whose variables are all LMGPU_POINT3.  Its two factor kinds,
+ * TranslationFactor (e = normalize(Tb - Ta) - z) and BetweenFactor<Point3> (e = (Tb - Ta) - z), are INTERNAL rows of the library's
+ * factor-type table: lmgpu_factor_type keeps its 14 entries and every lmgpu_add_factor_bucket* / ISAM2 / init_pose3 entry point keeps
+ * refusing type >= LMGPU_NUM_FACTOR_TYPES.  Coincident translations (Tb == Ta) of a TranslationFactor are OUTSIDE THE CONTRACT: the
+ * reference's normalize has no guard for them and neither has the kernel (the error and the Jacobian are then not finite).
+ *   create          cfg->world_size > 1 is refused (multi-rank is out of scope).  cfg->device < 0: the host logic only (finalize, get_keys,
+ *                   get_initial work; run returns LMGPU_HIP_ERROR).
+ *   add_directions  n edges (keys[2 i], keys[2 i + 1]) with measured unit direction dirs[3 i ..] and one noise model: noise_kind / noise as
+ *                   in lmgpu_add_factor_bucket (3 inverse sigmas, or R row-major 3 x 3), robust_kind / robust_k as in
+ *                   lmgpu_add_factor_bucket_robust.  index[i] = the edge's position in the caller's list of relativeTranslations: the
+ *                   calls group edges by noise model, the list order decides "the first edge" and the order of first appearance.
+ *   add_betweens    the same for betweenTranslations (meas = the Point3 measurement).
+ *   set_prior_sigma addPrior's priorNoiseModel = Isotropic(3, sigma); default 0.01.
+ *   seed            the session's 32-bit Mersenne Twister (seeded 42 at create).  DEVIATION: the reference's generator is process-wide.
+ *   finalize        TranslationRecovery::run up to the optimizer (:191-223):
+ *                   - nodes joined by an edge whose measured direction is (0, 0, 0) -- every component within 1e-9 of zero, the default
+ *                     tolerance of Unit3::equals -- are merged; the representative of a set is its
+ *                     SMALLEST key (DEVIATION from DSFMap's root; the results are the same); edges inside a set are dropped;
+ *                   - graph: one TranslationFactor per remaining direction edge, PRIOR_POINT3 at 0 on the first remaining edge's key1, then
+ *                     without betweens PRIOR_POINT3 at scale * z on its key2 with that edge's model, else one BetweenFactor<Point3> each.
+ *                     Without a remaining direction edge the graph is EMPTY (addPrior returns at once, :125-126) and run returns the
+ *                     initial values;
+ *                   - initial values: init_keys / init_vals (n_init x 3) where given, else three draws per node in initializeRandomly's
+ *                     order of first appearance, each coordinate 2 ((x1 + x2 2^32) / 2^64) - 1 from two consecutive 32-bit draws; no
+ *                     remaining edge but zero-direction edges: every representative at the origin (:218-223);
+ *                   - ordering (n_order keys, a boundary input over the ORIGINAL keys; non-representatives are ignored; n_order = 0:
+ *                     first appearance).  LMGPU_INVALID, nothing changed: duplicate index, duplicate key in the ordering, a variable
+ *                     missing from it, a merged set without any remaining edge (the reference throws there), a key that appears only
+ *                     in between-translations whose two ends are the same node (the reference returns no value for it).  A failure
+ *                     while the inner handle is built leaves the session unfinalized; the generator advances only on success.
+ *   run             lmgpu_optimize on the inner handle from the initial values with the caller's LM parameters, direct solver (PCG selected
+ *                   on the inner handle: LMGPU_INVALID); merged-away nodes then receive their representative's value.
+ *   get_keys        every key of the input by first appearance with its representative; get = the result in that order (n x 3);
+ *                   get_slots = the inner handle's variables by slot; get_initial = their initial values (slots x 3).
+ *   handle          the inner handle (owned by the session; NULL for an empty graph) for the parity taps: graph index i < m is direction
+ *                   edge i of the m remaining ones, m the origin prior, then the scale prior or the betweens. */
+typedef struct lmgpu_translation_recovery lmgpu_translation_recovery;
+int lmgpu_translation_recovery_create(const lmgpu_config* cfg, lmgpu_translation_recovery** out);
+int lmgpu_translation_recovery_destroy(lmgpu_translation_recovery* tr);
+const char* lmgpu_translation_recovery_last_error(const lmgpu_translation_recovery* tr);
+int lmgpu_translation_recovery_seed(lmgpu_translation_recovery* tr, uint32_t seed);
+int lmgpu_translation_recovery_set_prior_sigma(lmgpu_translation_recovery* tr, double sigma);
+int lmgpu_translation_recovery_add_directions(lmgpu_translation_recovery* tr, int32_t n, const int32_t* index, const uint64_t* keys, const double* dirs,
+                                              int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k);
+int lmgpu_translation_recovery_add_betweens(lmgpu_translation_recovery* tr, int32_t n, const int32_t* index, const uint64_t* keys, const double* meas,
+                                            int32_t noise_kind, const double* noise, int32_t robust_kind, double robust_k);
+int lmgpu_translation_recovery_finalize(lmgpu_translation_recovery* tr, double scale, int32_t n_init, const uint64_t* init_keys, const double* init_vals,
+                                        int32_t n_order, const uint64_t* ordering);
+int lmgpu_translation_recovery_num_keys(const lmgpu_translation_recovery* tr);    /* -1 before finalize */
+int lmgpu_translation_recovery_num_factors(const lmgpu_translation_recovery* tr); /* of the inner graph, priors included */
+int lmgpu_translation_recovery_get_keys(const lmgpu_translation_recovery* tr, uint64_t* keys_out, uint64_t* representative_out);
+int lmgpu_translation_recovery_get_slots(const lmgpu_translation_recovery* tr, uint64_t* keys_out);
+int lmgpu_translation_recovery_get_initial(const lmgpu_translation_recovery* tr, double* out);
+lmgpu_handle* lmgpu_translation_recovery_handle(lmgpu_translation_recovery* tr);
+int lmgpu_translation_recovery_run(lmgpu_translation_recovery* tr, const lmgpu_lm_params* p, lmgpu_lm_state* state_out);
+int lmgpu_translation_recovery_get(const lmgpu_translation_recovery* tr, double* out);
+
+/* ---- MFAS (gtsam/sfm/MFAS.{h,cpp}): outlier weights of translation directions, D projection directions in one launch ----
+ * n_edges edges (keys[2 e], keys[2 e + 1]); EITHER measured (n_edges x 3) with dirs (n_dirs x 3): weight = measured . dir, computed as
+ * x dx + y dy + z dz with every product and sum rounded once (no contraction); OR edge_weights (n_dirs x n_edges) as in MFAS(edgeWeights).
+ * An edge runs first -> second for weight >= 0, second -> first otherwise.  Outputs (any may be NULL): ordering_out (n_dirs x V keys, V =
+ * the number of distinct keys), weights_out (n_dirs x n_edges: |weight| where the edge's destination precedes its source in the
+ * ordering, else 0), sum_out (n_edges: the sum over the directions, added in direction order by one thread per edge, bitwise
+ * reproducible; what a 1dSfM caller thresholds).
+ * TIE RULE (ours): the reference walks an unordered_map, so which of several root nodes (inWeightSum < 1e-8) it takes, and which of
+ * several nodes of equal heuristic, is unspecified.  Here the LOWEST KEY wins both.  In/out weight sums are accumulated in edge order.
+ * REFUSED (LMGPU_INVALID, lmgpu_mfas_last_error): an unordered pair of nodes given twice (the reference's absWeightOfEdge silently reads
+ * one of the two entries), an edge from a node to itself, a non-finite input.
+ * One workgroup per direction; the node state lives in LDS up to lmgpu_mfas_lds_node_capacity() nodes, above that in global scratch. */
+typedef struct lmgpu_mfas_stats {
+  int32_t n_nodes;           /* V */
+  int32_t global_state;      /* 1: the node state was kept in global scratch */
+  int32_t lds_node_capacity;
+  int32_t pad_;
+  double kernel_ms;          /* device time of the two launches */
+} lmgpu_mfas_stats;
+int lmgpu_mfas_outlier_weights(int32_t device, int32_t n_edges, const uint64_t* keys, const double* measured, int32_t n_dirs, const double* dirs,
+                               const double* edge_weights, uint64_t* ordering_out, double* weights_out, double* sum_out, lmgpu_mfas_stats* stats);
+int lmgpu_mfas_lds_node_capacity(void);
+const char* lmgpu_mfas_last_error(void); /* of the calling thread's last lmgpu_mfas_outlier_weights */
+
 /* Per-kernel device time (HIP events on the handle's stream around each launch), accumulated since
  * lmgpu_set_kernel_timing(h, 1).  work[] is the ALGORITHMIC work of the launches in the category:
  * bytes for LINEARIZE (232 B per SFM factor + every camera / point row once) and ALLREDUCE,

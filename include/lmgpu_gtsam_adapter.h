@@ -53,12 +53,15 @@
 #include <gtsam/nonlinear/internal/LevenbergMarquardtState.h>
 #include <gtsam/nonlinear/internal/NonlinearOptimizerState.h>
 #include <gtsam/sam/BearingRangeFactor.h>
+#include <gtsam/sfm/BinaryMeasurement.h>
+#include <gtsam/geometry/Unit3.h>
 #include <gtsam/slam/BetweenFactor.h>
 #include <gtsam/slam/GeneralSFMFactor.h>
 #include <gtsam/slam/ProjectionFactor.h>
 #include <gtsam/slam/SmartProjectionPoseFactor.h>
 
 #include <algorithm>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -1153,6 +1156,181 @@ class GpuInitializePose3 {
       return out;
     }
   };
+};
+
+/// TranslationRecovery (gtsam/sfm/TranslationRecovery.h) on the device: construct a gtsam::GpuTranslationRecovery where the program constructed
+/// a TranslationRecovery and call run the same way.  The graph (TranslationFactor per edge, the two priors or the BetweenFactor<Point3>s),
+/// the merging of nodes joined by zero-direction edges, the initial values and the Levenberg-Marquardt solve run behind
+/// lmgpu_translation_recovery_*.  Deviations, as documented in lmgpu.h: the random initial values come from a generator owned by this
+/// object (seed 42; seed() resets it), a merged set is represented by its smallest key, the BilinearAngleTranslationFactor form is refused.
+/// `ordering`: elimination order over the keys of the measurements (default: first appearance).
+class GpuTranslationRecovery {
+ public:
+  using KeyPair = std::pair<Key, Key>;
+  using TranslationEdges = std::vector<BinaryMeasurement<Unit3>>;
+
+  explicit GpuTranslationRecovery(const LevenbergMarquardtParams& lmParams = LevenbergMarquardtParams(), bool use_bilinear_translation_factor = false,
+                                  int device = 0)
+      : lmParams_(lmParams), device_(device) {
+    if (use_bilinear_translation_factor)
+      throw std::invalid_argument("GpuTranslationRecovery: use_bilinear_translation_factor needs a 1-D variable type (not bound)");
+    lmgpu_pcg_params pcg;
+    if (lmgpu_detail::toPcg(lmParams, &pcg)) throw std::invalid_argument("GpuTranslationRecovery: solves with the direct solver (PCG is refused)");
+  }
+
+  void seed(uint32_t s) { seed_ = s; }
+
+  /// TranslationRecovery::run (TranslationRecovery.cpp:191-228)
+  Values run(const TranslationEdges& relativeTranslations, const double scale = 1.0,
+             const std::vector<BinaryMeasurement<Point3>>& betweenTranslations = {}, const Values& initialValues = Values(),
+             const Ordering* ordering = nullptr) const {
+    Session s(device_);
+    s.check(lmgpu_translation_recovery_seed(s.tr, seed_));
+    for (size_t i = 0; i < relativeTranslations.size(); i++) {
+      const auto& e = relativeTranslations[i];
+      const Point3 z = e.measured().point3();
+      s.add(lmgpu_translation_recovery_add_directions, i, e.key1(), e.key2(), z, e.noiseModel());
+    }
+    for (size_t i = 0; i < betweenTranslations.size(); i++) {
+      const auto& e = betweenTranslations[i];
+      s.add(lmgpu_translation_recovery_add_betweens, i, e.key1(), e.key2(), e.measured(), e.noiseModel());
+    }
+    std::vector<uint64_t> ikeys, order;
+    std::vector<double> ivals;
+    for (const Key k : initialValues.keys()) {
+      const Point3 p = initialValues.at<Point3>(k);
+      ikeys.push_back(k);
+      ivals.insert(ivals.end(), {p.x(), p.y(), p.z()});
+    }
+    if (ordering) order.assign(ordering->begin(), ordering->end());
+    s.check(lmgpu_translation_recovery_finalize(s.tr, scale, static_cast<int32_t>(ikeys.size()), ikeys.data(), ivals.data(),
+                                                static_cast<int32_t>(order.size()), order.data()));
+    const lmgpu_lm_params p = lmgpu_detail::toC(lmParams_);
+    lmgpu_lm_state st;
+    s.check(lmgpu_translation_recovery_run(s.tr, &p, &st));
+    const int n = lmgpu_translation_recovery_num_keys(s.tr);
+    std::vector<uint64_t> keys(static_cast<size_t>(n));
+    std::vector<double> out(3 * static_cast<size_t>(n));
+    lmgpu_translation_recovery_get_keys(s.tr, keys.data(), nullptr);
+    s.check(lmgpu_translation_recovery_get(s.tr, out.data()));
+    Values result;
+    for (size_t i = 0; i < keys.size(); i++) result.insert<Point3>(keys[i], Point3(out[3 * i], out[3 * i + 1], out[3 * i + 2]));
+    return result;
+  }
+
+ private:
+  struct Session {
+    lmgpu_translation_recovery* tr = nullptr;
+    explicit Session(int device) {
+      lmgpu_config cfg{device, 0, 1, 0};
+      if (lmgpu_translation_recovery_create(&cfg, &tr) != LMGPU_OK) throw std::runtime_error("lmgpu_translation_recovery_create failed");
+    }
+    ~Session() { lmgpu_translation_recovery_destroy(tr); }
+    Session(const Session&) = delete;
+    Session& operator=(const Session&) = delete;
+    void check(int rc) const {
+      if (rc == LMGPU_OK) return;
+      const std::string msg = std::string("GpuTranslationRecovery: ") + lmgpu_translation_recovery_last_error(tr);
+      if (rc == LMGPU_INDETERMINATE) {  // the first frontal variable of the failing front, like the optimizers' adapters
+        lmgpu_handle* h = lmgpu_translation_recovery_handle(tr);
+        const int n = lmgpu_translation_recovery_get_slots(tr, nullptr);
+        std::vector<uint64_t> slots(n > 0 ? static_cast<size_t>(n) : 0);
+        if (n > 0) lmgpu_translation_recovery_get_slots(tr, slots.data());
+        const int slot = h ? lmgpu_last_failed_slot(h) : -1;
+        throw IndeterminantLinearSystemException(slot >= 0 && slot < n ? Key(slots[static_cast<size_t>(slot)]) : Key(0));
+      }
+      if (rc == LMGPU_INVALID) throw std::invalid_argument(msg);
+      throw std::runtime_error(msg);  // LMGPU_HIP_ERROR: the device, not the caller's input
+    }
+    template <class ADD>
+    void add(ADD fn, size_t i, Key k1, Key k2, const Point3& z, const SharedNoiseModel& model) const {
+      const lmgpu_detail::Noise nz = lmgpu_detail::extractNoise(model);  // throws on a constrained model
+      const int32_t index = static_cast<int32_t>(i);
+      const uint64_t keys[2] = {k1, k2};
+      const double m[3] = {z.x(), z.y(), z.z()};
+      check(fn(tr, 1, &index, keys, m, nz.kind, nz.data.empty() ? nullptr : nz.data.data(), nz.robust, nz.robustK));
+    }
+  };
+  LevenbergMarquardtParams lmParams_;
+  int device_;
+  uint32_t seed_ = 42;
+};
+
+/// MFAS (gtsam/sfm/MFAS.h) on the device: computeOrdering / computeOutlierWeights for one projection direction or one map of edge
+/// weights, and outlierWeightSums for many directions at once (what 1dSfM thresholds).  Ties go to the lowest key and an unordered pair
+/// given twice is refused (lmgpu.h).
+class GpuMFAS {
+ public:
+  using KeyPair = std::pair<Key, Key>;
+  using TranslationEdges = std::vector<BinaryMeasurement<Unit3>>;
+
+  GpuMFAS(const TranslationEdges& relativeTranslations, const Unit3& projectionDirection, int device = 0) : device_(device) {
+    for (const auto& e : relativeTranslations) {
+      pairs_.emplace_back(e.key1(), e.key2());
+      const Point3 z = e.measured().point3();
+      meas_.insert(meas_.end(), {z.x(), z.y(), z.z()});
+    }
+    const Point3 d = projectionDirection.point3();
+    dirs_ = {d.x(), d.y(), d.z()};
+  }
+  explicit GpuMFAS(const std::map<KeyPair, double>& edgeWeights, int device = 0) : device_(device) {
+    for (const auto& kw : edgeWeights) {
+      pairs_.push_back(kw.first);
+      weights_.push_back(kw.second);
+    }
+  }
+
+  KeyVector computeOrdering() const {
+    run();
+    return KeyVector(order_.begin(), order_.end());
+  }
+  std::map<KeyPair, double> computeOutlierWeights() const {
+    run();
+    std::map<KeyPair, double> out;
+    for (size_t e = 0; e < pairs_.size(); e++) out[pairs_[e]] = wout_[e];
+    return out;
+  }
+
+  /// the per-edge sum of the outlier weights over `directions`, in the order of relativeTranslations
+  static std::vector<double> outlierWeightSums(const TranslationEdges& relativeTranslations, const std::vector<Unit3>& directions, int device = 0) {
+    GpuMFAS m(relativeTranslations, directions.empty() ? Unit3() : directions.front(), device);
+    m.dirs_.clear();
+    for (const Unit3& u : directions) {
+      const Point3 d = u.point3();
+      m.dirs_.insert(m.dirs_.end(), {d.x(), d.y(), d.z()});
+    }
+    std::vector<double> sum(m.pairs_.size());
+    m.call(nullptr, nullptr, sum.data());
+    return sum;
+  }
+
+ private:
+  void call(uint64_t* order, double* wout, double* sum) const {
+    std::vector<uint64_t> keys;
+    for (const KeyPair& p : pairs_) keys.insert(keys.end(), {p.first, p.second});
+    const bool given = !weights_.empty();
+    const int32_t D = given ? 1 : static_cast<int32_t>(dirs_.size() / 3);
+    const int rc = lmgpu_mfas_outlier_weights(device_, static_cast<int32_t>(pairs_.size()), keys.data(), given ? nullptr : meas_.data(), D,
+                                              given ? nullptr : dirs_.data(), given ? weights_.data() : nullptr, order, wout, sum, nullptr);
+    if (rc == LMGPU_INVALID) throw std::invalid_argument(std::string("GpuMFAS: ") + lmgpu_mfas_last_error());
+    if (rc != LMGPU_OK) throw std::runtime_error(std::string("GpuMFAS: ") + lmgpu_mfas_last_error());
+  }
+  void run() const {
+    if (!wout_.empty() || pairs_.empty()) return;
+    KeySet nodes;
+    for (const KeyPair& p : pairs_) {
+      nodes.insert(p.first);
+      nodes.insert(p.second);
+    }
+    order_.resize(nodes.size());
+    wout_.resize(pairs_.size());
+    call(order_.data(), wout_.data(), nullptr);
+  }
+  int device_;
+  std::vector<KeyPair> pairs_;
+  std::vector<double> meas_, dirs_, weights_;
+  mutable std::vector<uint64_t> order_;
+  mutable std::vector<double> wout_;
 };
 
 /// triangulateSafe(cameras, measured, params) (gtsam/geometry/triangulation.h:701-758) on the device, for CameraSet<PinholeCamera<Cal3Bundler>>
